@@ -5,12 +5,16 @@
     python bench.py --gpus N --steps K --warmup W    # launches its N ranks itself (re-exec under torch.distributed.run)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W       # configs[4]: same graph row-partitioned, strong scaling
+    python bench.py --full                           # + every secondary figure and check (see --help)
+    python bench.py --dump-outputs DIR               # + Y of the last timed step (or a fixed row sample of it) in DIR/y.npy
 
 One "step" = one pass of the hot path over the whole graph: [all-gather of the row-sharded embedding over
 RCCL when N > 1] + one fused 1+2-hop SpMM launch per rank (GCNLayer.call, reference
 h2gcn/models/_layers.py:78-81).  Inputs are synthetic (h2gcn_amd/synth.py), generated on the device and
 resident in HBM before the timed region.  Rank 0 prints ONE JSON line; see DESIGN.md "Measurement" for the
-algorithmic-bytes model behind `roofline`.
+algorithmic-bytes model behind `roofline`.  A plain run sets up, warms up, times the K steps (the line's `roofline` comes
+from the HIP events of those steps) and prints; the adjoint, the live PMC traffic, the ceiling probe, the CPU baselines,
+the arxiv and HBM-resident legs and the checksum against the CPU oracle are measured under --full.
 """
 import argparse
 import json
@@ -228,7 +232,7 @@ def secondary_leg(shape, steps=200, warmup=20, timeout_s=300):
     from its own two rocprofv3 passes.  Reported under `secondary` (+ scalars under `roofline`); never part of `value`."""
     import subprocess
 
-    child = [sys.executable, str(ROOT / "bench.py"), "--shape", shape, "--steps", str(steps), "--warmup", str(warmup),
+    child = [sys.executable, str(ROOT / "bench.py"), "--shape", shape, "--steps", str(steps), "--warmup", str(warmup), "--full",
              "--no-cpu-baseline", "--no-adjoint", "--no-hbm-leg", "--no-probe", "--no-secondary"]
     try:
         env = {k: v for k, v in os.environ.items() if k != "H2GCN_BENCH_CHILD"}     # the child collects its own PMC passes
@@ -263,7 +267,7 @@ def hbm_resident_leg(timeout_s=600):
     timed (never inside its timed region): 2 warm-up + HBM_LEG_STEPS timed launches, figures from the median launch."""
     import subprocess
 
-    child = [sys.executable, str(ROOT / "bench.py"), "--shape", "products_x6", "--steps", str(HBM_LEG_STEPS), "--warmup", "2",
+    child = [sys.executable, str(ROOT / "bench.py"), "--shape", "products_x6", "--steps", str(HBM_LEG_STEPS), "--warmup", "2", "--full",
              "--no-cpu-baseline", "--no-adjoint", "--no-traffic", "--no-hbm-leg"]
     try:
         r = subprocess.run(child, env=dict(os.environ, H2GCN_BENCH_CHILD="1"), capture_output=True, text=True, timeout=timeout_s)
@@ -382,6 +386,36 @@ def dry_exchange(a, world, rank, device, backend, to_stderr=False, rccl_log_dir=
     elif rank == 0:
         print(json.dumps(report), flush=True)
     return report
+
+
+DUMP_BYTES = 32 << 20   # --dump-outputs: at most this many bytes of Y are written
+DUMP_SEED = 7
+
+
+def dump_rows(n_rows, d):
+    """Global rows of Y [n_rows, 2, d] that --dump-outputs writes, ascending: every row when Y fits in DUMP_BYTES, else a fixed
+    sample drawn with DUMP_SEED -- the same rows for every run, rank count and build given the same arguments."""
+    k = max(1, DUMP_BYTES // (2 * d * 4))
+    if n_rows <= k:
+        return np.arange(n_rows, dtype=np.int64)
+    return np.sort(np.random.default_rng(DUMP_SEED).choice(n_rows, size=k, replace=False)).astype(np.int64)
+
+
+def dump_outputs(out_dir, y, rows, r0, r1, world, device, rank):
+    """Rows `rows` of the global Y to out_dir/y.npy (float32), written by rank 0; this rank holds rows [r0, r1) as `y`.  N > 1:
+    every rank puts its rows into a zeroed buffer and the buffers are summed as int32 bit patterns (exact: one owner per row)."""
+    if world == 1:
+        sample = y.index_select(0, torch.from_numpy(rows).to(device))
+    else:
+        mine = (rows >= r0) & (rows < r1)
+        buf = torch.zeros((len(rows),) + tuple(y.shape[1:]), dtype=torch.int32, device=device)
+        buf.index_copy_(0, torch.from_numpy(np.nonzero(mine)[0]).to(device),
+                        y.view(torch.int32).index_select(0, torch.from_numpy(rows[mine] - r0).to(device)))
+        dist.all_reduce(buf)
+        sample = buf.view(torch.float32)
+    if rank == 0:
+        Path(out_dir).mkdir(parents=True, exist_ok=True)
+        np.save(Path(out_dir) / "y.npy", sample.cpu().numpy())
 
 
 USAGE_ERROR = 64   # exit code of a command line that cannot run under any schedule (bench_supervisor does not retry it)
@@ -504,13 +538,25 @@ def main():
     ap.add_argument("--pad-rows", action="store_true",
                     help="give X a row stride padded to 32 floats (every row starts on a 128-byte line), as the model's concat buffer has")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the BASELINE configs[2] (arxiv shape) leg that the default products line carries under `secondary` "
+                    help="skip the BASELINE configs[2] (arxiv shape) leg that the --full products line carries under `secondary` "
                          "(--no-hbm-leg skips it too: no child legs at all)")
     ap.add_argument("--no-hbm-leg", action="store_true",
-                    help="skip the HBM-resident leg (products_x6, 12 steps, child process) the default N=1 products line carries")
+                    help="skip the HBM-resident leg (products_x6, 12 steps, child process) the --full N=1 products line carries")
     ap.add_argument("--dry-exchange", action="store_true",
                     help="N > 1: only smoke-test every exchange form with 1 MiB shards and print a table (no big allocation)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: adjoint launch, live PMC traffic, gather / copy ceiling probe, CPU baselines, "
+                         "the arxiv and HBM-resident legs, the checksum against the oracle, the N > 1 first-contact table and "
+                         "exchange-only / SpMM-only timings (the --no-* options switch single parts off).  Without it a run sets up, "
+                         "warms up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write Y of the last step to DIR/y.npy (float32 [rows, 2, d]): every row when Y "
+                         "fits in 32 MiB, else the fixed seeded row sample of dump_rows()")
     a = ap.parse_args()
+    if a.steps < 1:
+        fail_line(a, f"--steps {a.steps}: at least one timed step is needed", int(os.environ.get("RANK", "0")), code=USAGE_ERROR)
+    if not a.full:
+        a.no_adjoint = a.no_cpu_baseline = a.no_probe = a.no_traffic = a.no_hbm_leg = a.no_secondary = True
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # plain `python bench.py --gpus N`: launch the N ranks ourselves (same thing the documented
@@ -581,7 +627,7 @@ def main():
         dist.destroy_process_group()
         return
     first_contact = None
-    if world > 1 and os.environ.get("H2GCN_BENCH_SKIP_DRY") != "1":
+    if world > 1 and a.full and os.environ.get("H2GCN_BENCH_SKIP_DRY") != "1":
         # first contact with the node BEFORE any big allocation: every exchange form with 1 MiB shards (seconds); the table
         # goes to stderr right away -- if a later stage dies, what worked and what did not is already on record -- and
         # into the line's diagnostics
@@ -769,10 +815,11 @@ def main():
         diagnostics["first_contact_dry_exchange"] = first_contact
         # comm-only and compute-only times of the chosen schedule (not part of the metric)
         injected_failure("exchange_only", rank)
-        diagnostics["exchange_only_ms"] = timed_ms(layer.exchange_only, 3)
-        diagnostics["spmm_only_ms"] = timed_ms(
-            lambda: [plan.spmm(layer.full[c][: layer.n_src], out=y[:, :, layer.offsets[c]:layer.offsets[c] + layer.widths[c]])
-                     for c in range(layer.C)], 3)
+        if a.full:
+            diagnostics["exchange_only_ms"] = timed_ms(layer.exchange_only, 3)
+            diagnostics["spmm_only_ms"] = timed_ms(
+                lambda: [plan.spmm(layer.full[c][: layer.n_src], out=y[:, :, layer.offsets[c]:layer.offsets[c] + layer.widths[c]])
+                         for c in range(layer.C)], 3)
         for k, v in cands.items():  # collective: release the exported buffers of the schedules not chosen
             if v[1] is not layer:
                 v[1].close()
@@ -827,11 +874,15 @@ def main():
         dist.all_gather(every, mine)
         per_rank = [{"rank": q, "kernel_ms": float(v[0]), "edges": int(v[1]), "algorithmic_bytes": int(v[2]), "achieved": float(v[2]) / (float(v[0]) * 1e-3) / 1e9,
                      "frac": float(v[2]) / (float(v[0]) * 1e-3) / 1e9 / HBM_PEAK_GBPS} for q, v in enumerate(t_.tolist() for t_ in every)]
-    # order-independent fingerprint of the result (same schedule => same bits for any number of ranks)
-    ck = y.view(torch.int32).to(torch.int64).sum()
-    if world > 1:
-        dist.all_reduce(ck)
-    y_checksum = int(ck.item())
+    y_checksum = None
+    if a.full:
+        # order-independent fingerprint of the result (same schedule => same bits for any number of ranks)
+        ck = y.view(torch.int32).to(torch.int64).sum()
+        if world > 1:
+            dist.all_reduce(ck)
+        y_checksum = int(ck.item())
+    if a.dump_outputs:
+        dump_outputs(a.dump_outputs, y, dump_rows(n, d), r0, r1, world, device, rank)
 
     edges = sum(nnz_global)
     b_alg = algorithmic_bytes(nnz_local, r1 - r0, d, 2)
@@ -858,7 +909,7 @@ def main():
             "n_rows": n, "nnz_per_hop": nnz_global, "d": d,
             "parallelism": f"row-partition x{world}" + (f", exchange of X per step: {exchange}" if world > 1 else ""),
             "kernel_variant": a.variant, "feature_chunks": chunk_label, "dist_backend": backend,
-            "diagnostics": diagnostics, "slice_cols": a.slice_cols or "auto", "y_checksum": y_checksum,
+            "diagnostics": diagnostics, "slice_cols": a.slice_cols or "auto",
             "schedule": plan.schedule(layer.widths[0], ld_src=x_local.stride(0) if world == 1 else None),
             "t_fused_median_ms": kern_ms_median,
             "edges_per_s_from_median_kernel_time": sum(nnz_local) / (kern_ms_median * 1e-3),
@@ -886,10 +937,12 @@ def main():
         # figures, and the whole-job delivered rate over the step time (exchange included):
         out["roofline"]["per_rank"] = per_rank
         out["roofline"]["whole_job_GBps_over_step_time"] = sum(r_["algorithmic_bytes"] for r_ in per_rank) / (elapsed / a.steps) / 1e9
-    want = N1_CHECKSUMS.get((a.shape, d))
-    out["config"]["n1_checksum_expected"] = want
-    out["config"]["checksum_matches_n1"] = None if want is None else (y_checksum == want)
-    out["config"]["checksum_source"] = "CPU oracle (oracle/fullsize.py: every row of the operands rebuilt on the host, documented summation tree in plain C)"
+    if a.full:
+        want = N1_CHECKSUMS.get((a.shape, d))
+        out["config"]["y_checksum"] = y_checksum
+        out["config"]["n1_checksum_expected"] = want
+        out["config"]["checksum_matches_n1"] = None if want is None else (y_checksum == want)
+        out["config"]["checksum_source"] = "CPU oracle (oracle/fullsize.py: every row of the operands rebuilt on the host, documented summation tree in plain C)"
     if not a.no_adjoint:
         # backward launch dX = sum_k A_k^T dY[:, k, :] on the local shard: half of every training step
         # (reference h2gcn/models/H2GCN.py:66-74); secondary figure, not part of the metric
@@ -968,7 +1021,8 @@ def main():
         except Exception as e:  # the baseline is a report, never a reason to lose the GPU number
             out["cpu_baseline"] = {"value": None, "unit": "edges/s", "cores": 1, "kind": "port", "sample": f"failed: {e}"}
     elif rank == 0:
-        out["cpu_baseline"] = {"value": None, "unit": "edges/s", "cores": 1, "kind": "port", "sample": "skipped (--no-cpu-baseline)"}
+        out["cpu_baseline"] = {"value": None, "unit": "edges/s", "cores": 1, "kind": "port",
+                               "sample": "skipped (--no-cpu-baseline)" if a.full else "skipped (measured under --full)"}
     if rank == 0:
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -62,7 +62,10 @@ def test_rccl_log_summary(tmp_path, monkeypatch):
     from h2gcn_amd.partition import enable_rccl_debug_log, summarize_rccl_log
 
     for k in ("NCCL_DEBUG_SUBSYS", "NCCL_DEBUG_FILE"):
-        monkeypatch.delenv(k, raising=False)
+        # setenv first, so that teardown restores the caller's value (or its absence): delenv of an unset variable records
+        # nothing, and what enable_rccl_debug_log sets below would otherwise outlive this test in the session's environment
+        monkeypatch.setenv(k, "")
+        monkeypatch.delenv(k)
     monkeypatch.setenv("NCCL_DEBUG", "VERSION")          # what the GPU image exports: too quiet, and it prints to stdout
     enable_rccl_debug_log(str(tmp_path))
     assert os.environ["NCCL_DEBUG"] == "INFO" and os.environ["NCCL_DEBUG_FILE"].startswith(str(tmp_path))

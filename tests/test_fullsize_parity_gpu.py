@@ -106,3 +106,36 @@ def test_every_row_of_the_baseline_shape_against_the_oracle(shape):
     lhs = float((y.double() * w.double()).sum().item())
     rhs = float((x.double() * dx.double()).sum().item())
     assert abs(lhs - rhs) <= 1e-6 * max(1.0, abs(lhs), float((y.double().abs() * w.double().abs()).sum().item()) * 1e-3)
+
+
+def test_plain_bench_run_and_its_dumped_outputs(tmp_path):
+    """A plain `bench.py` run (no --full) on the arxiv shape: one line with the K timed steps and the headline keys, none of the
+    --full figures; `--dump-outputs` writes Y of the last timed step, for the rows bench.dump_rows names, bit-equal to the
+    oracle's documented summation tree."""
+    import json
+    import subprocess
+
+    from oracle import fullsize as fs
+
+    sys.path.insert(0, str(ROOT))
+    import bench
+
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "H2GCN_SHARE_GPU")}
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--shape", "arxiv", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path / "out")], env=env, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    line = json.loads(lines[0])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["dtype"] == "f32"
+    assert abs(line["value"] - sum(line["config"]["nnz_per_hop"]) / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+    assert not {"adjoint", "secondary"} & set(line) and "checksum_matches_n1" not in line["config"], sorted(line)
+    assert line["cpu_baseline"]["value"] is None and "ceilings" not in line["roofline"]
+    files = sorted((tmp_path / "out").iterdir())
+    assert [f.name for f in files] == ["y.npy"] and files[0].stat().st_size <= 64 << 20
+    y = np.load(files[0])
+    parts, x_host, n, d = fs.host_operands("arxiv")
+    rows = bench.dump_rows(n, d)
+    assert y.dtype == np.float32 and y.shape == (len(rows), 2, d) and 0 < len(rows) < n
+    bad, first = fs.count_bit_mismatches(y, fs.gcn_layer_tree_mt(parts, x_host)[rows])
+    assert bad == 0, f"{bad} of {y.size} dumped elements differ from the canonical tree, first at flat index {first}"

@@ -569,7 +569,7 @@ def _reap(procs):
 
 
 def _run_bench(world, extra, tmp_path, env_extra=None):
-    """bench.py as real subprocesses: `world` ranks sharing the one GPU (gloo bootstrap), returns the parsed JSON line."""
+    """bench.py --full as real subprocesses: `world` ranks sharing the one GPU (gloo bootstrap), returns the parsed JSON line."""
     port = _free_port()
     procs = []
     for rank in range(world):
@@ -582,7 +582,7 @@ def _run_bench(world, extra, tmp_path, env_extra=None):
                 env.pop(k, None)
         env.setdefault("H2GCN_BENCH_SKIP_DRY", "1")   # the first-contact table is covered by the plain-launch and --dry-exchange tests
         env.update(env_extra or {})
-        procs.append(subprocess.Popen([sys.executable, str(ROOT / "bench.py"), "--gpus", str(world), "--no-cpu-baseline",
+        procs.append(subprocess.Popen([sys.executable, str(ROOT / "bench.py"), "--gpus", str(world), "--full", "--no-cpu-baseline",
                                        "--no-probe", "--no-traffic", "--no-hbm-leg"] + extra, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE))
     try:
         outs = [p.communicate(timeout=400) for p in procs]
@@ -616,7 +616,8 @@ def test_bench_multi_rank_branch_runs_and_matches_one_rank(tmp_path, world):
     # recomputed on the CPU in tests/test_oracle_tree_and_classifier.py) -- and so do 1-rank runs with other chunkings / slice widths
     extra_env = ({"H2GCN_BENCH_EXCHANGES": "allgather,ipc_engine,ipc_kernel", "H2GCN_BENCH_CHUNK_SPECS": "1,2"} if world == 3
                  else {"H2GCN_DIST_BACKEND": "nccl"})
-    out = _run_bench(world, ["--shape", "arxiv", "--steps", "3", "--warmup", "1"], tmp_path, env_extra=extra_env)
+    out = _run_bench(world, ["--shape", "arxiv", "--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "dump")], tmp_path,
+                     env_extra=extra_env)
     assert out["n_gpus"] == world and out["value"] > 0 and out["roofline"]["kernel_ms_max_over_ranks"] > 0
     assert out["config"]["dist_backend"] == ("gloo" if world == 3 else "nccl")
     if world != 3:
@@ -630,6 +631,13 @@ def test_bench_multi_rank_branch_runs_and_matches_one_rank(tmp_path, world):
     (tmp_path / f"line{world}.json").write_text(json.dumps(out))
     _keep(f"bench_shared_gpu_arxiv_n{world}.json", out)
     assert out["config"]["checksum_matches_n1"] is True and out["config"]["nnz_per_hop"] == [1203951, 1205200]
+    # --dump-outputs gathers the sampled rows of Y from their owner ranks: the oracle's rows, bit for bit
+    from oracle import fullsize as fs
+    sys.path.insert(0, str(ROOT))
+    import bench
+    parts, x_host, n, d = fs.host_operands("arxiv")
+    bad, first = fs.count_bit_mismatches(np.load(tmp_path / "dump" / "y.npy"), fs.gcn_layer_tree_mt(parts, x_host)[bench.dump_rows(n, d)])
+    assert bad == 0, (bad, first)
     if world == 2:
         for extra in (["--chunks", "4"], ["--chunks", "16+48+64"], ["--slice-cols", "64"], ["--slice-cols", "256"]):
             alt = _run_bench(1, ["--shape", "arxiv", "--steps", "1", "--warmup", "1", "--no-adjoint"] + extra, tmp_path)
@@ -704,7 +712,7 @@ def test_bench_eight_ranks_on_one_gpu(tmp_path, backend):
 def test_bench_plain_launch_spawns_its_own_ranks(tmp_path, backend):
     """`python bench.py --gpus 2 ...` with NO torch.distributed.run environment (the shape of the driver's N = 1 command):
     bench.py re-executes itself under torch.distributed.run, rank 0 prints the one line, and that line carries what the
-    single-GPU line carries -- roofline (rank 0's and every rank's), cpu_baseline (rank 0's row block, after the timed
+    single-GPU --full line carries -- roofline (rank 0's and every rank's), cpu_baseline (rank 0's row block, after the timed
     region), the first-contact exchange table -- and `checksum_matches_n1`-style evidence: the checksum of the 1-rank run."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(H2GCN_SHARE_GPU="1", H2GCN_BENCH_EXCHANGES="allgather,ipc_kernel")
@@ -713,7 +721,7 @@ def test_bench_plain_launch_spawns_its_own_ranks(tmp_path, backend):
         env["H2GCN_DIST_BACKEND"] = "gloo"
     else:
         env.pop("H2GCN_DIST_BACKEND", None)     # the DEFAULT backend: RCCL -- the driver's command, short of a second device
-    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--shape", "arxiv", "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, str(ROOT / "bench.py"), "--gpus", "2", "--shape", "arxiv", "--steps", "2", "--warmup", "1", "--full",
                         "--chunks", "2", "--cpu-seconds", "0.5", "--no-probe", "--no-traffic", "--no-hbm-leg"], env=env,
                        capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -743,7 +751,7 @@ def _run_supervised(world, extra, env_extra, timeout=400):
                    H2GCN_BENCH_EXCHANGES="allgather,ipc_kernel", H2GCN_BENCH_PEER_FAILURE_GRACE_S="2")
         env.update(env_extra)
         procs.append(subprocess.Popen([sys.executable, str(ROOT / "bench.py"), "--gpus", str(world), "--shape", "arxiv", "--steps", "2",
-                                       "--warmup", "1", "--no-cpu-baseline", "--no-probe", "--no-traffic", "--no-hbm-leg", "--no-adjoint"] + extra,
+                                       "--warmup", "1", "--full", "--no-cpu-baseline", "--no-probe", "--no-traffic", "--no-hbm-leg", "--no-adjoint"] + extra,
                                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     try:
         outs = [p.communicate(timeout=timeout) for p in procs]
