@@ -11,7 +11,7 @@ import ctypes as C
 import os
 from pathlib import Path
 
-ABI_VERSION = 4
+ABI_VERSION = 5
 MAX_HOPS = 8
 
 OK = 0
@@ -27,6 +27,9 @@ METRICS_MAX_SETS = 4
 XCHG_BLOB_BYTES = 192
 XCHG_COPY_ENGINE = 0
 XCHG_COPY_KERNEL = 1
+
+DTYPE_F32 = 0
+DTYPE_BF16 = 1
 
 PLAN_BUILD_TRANSPOSE = 0x1
 PLAN_SKIP_VALIDATION = 0x2
@@ -49,6 +52,8 @@ EXPORTED_SYMBOLS = (
     "h2gcn_spmm_workspace_bytes",
     "h2gcn_spmm_hops_opts_f32",
     "h2gcn_spmm_hops_T_opts_f32",
+    "h2gcn_spmm_hops_bf16",
+    "h2gcn_spmm_hops_T_bf16",
     "h2gcn_ring_scratch_bytes",
     "h2gcn_ring_count",
     "h2gcn_ring_fill",
@@ -185,6 +190,17 @@ def lib() -> C.CDLL:
         C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
         C.POINTER(LaunchOpts), C.c_void_p,
     ]
+    if hasattr(L, "h2gcn_spmm_hops_bf16"):   # (absent from pre-ABI-5 builds loaded for A/B runs)
+        L.h2gcn_spmm_hops_bf16.restype = C.c_int
+        L.h2gcn_spmm_hops_bf16.argtypes = [
+            C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
+            C.POINTER(LaunchOpts), C.c_void_p,
+        ]
+        L.h2gcn_spmm_hops_T_bf16.restype = C.c_int
+        L.h2gcn_spmm_hops_T_bf16.argtypes = [
+            C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_int64,
+            C.POINTER(LaunchOpts), C.c_void_p,
+        ]
     L.h2gcn_ring_scratch_bytes.restype = C.c_size_t
     L.h2gcn_ring_scratch_bytes.argtypes = [C.c_int64]
     ring_common = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
@@ -266,11 +282,12 @@ def lib() -> C.CDLL:
     L.h2gcn_xchg_destroy.restype = None
     L.h2gcn_xchg_destroy.argtypes = [C.c_void_p]
     got = L.h2gcn_abi_version()
-    # An explicitly named ABI-3 build (H2GCN_HIP_LIBRARY: the interleaved A/B tools time an older kernel) is accepted.  It lacks
-    # what later rounds ADDED -- h2gcn_plan_segment_classes, h2gcn_adam_keras_l2_f32 / h2gcn_l2_penalty_*,
-    # h2gcn_xchg_allgather_pull_rows -- and every caller of those asks `has()` first: the front end then keeps the l2 penalty in
-    # the autograd graph, pulls whole shards, and HopPlan.segment_classes raises a message instead of an AttributeError.
-    if got != ABI_VERSION and not (os.environ.get("H2GCN_HIP_LIBRARY") and got == 3):
+    # An explicitly named ABI-3 or ABI-4 build (H2GCN_HIP_LIBRARY: the interleaved A/B tools time an older kernel) is accepted.  It
+    # lacks what later rounds ADDED -- h2gcn_plan_segment_classes, h2gcn_adam_keras_l2_f32 / h2gcn_l2_penalty_*,
+    # h2gcn_xchg_allgather_pull_rows (ABI 4), the bf16 launches h2gcn_spmm_hops_bf16 / _T_bf16 (ABI 5) -- and every caller of those
+    # asks `has()` first: the front end then keeps the l2 penalty in the autograd graph, pulls whole shards, and
+    # HopPlan.segment_classes / a bf16 HopPlan launch raise a message instead of an AttributeError.
+    if got != ABI_VERSION and not (os.environ.get("H2GCN_HIP_LIBRARY") and got in (3, 4)):
         raise RuntimeError(f"{path}: ABI version {got}, this front end expects {ABI_VERSION}")
     _LIB = L
     return L

@@ -121,6 +121,7 @@ __global__ void check_colidx_kernel(const int32_t* __restrict__ colidx, int64_t 
 }
 
 void launch_in_tile_short(bool sum, const LaunchParams& p, int slice, bool off32, bool fb4, dim3 grid, hipStream_t stream);
+void launch_bf16(bool sum, bool out_bf16, const LaunchParams& p, const KernelChoice& k, dim3 grid, hipStream_t stream);
 int transpose_csr_device(int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t* rowptr, const int32_t* colidx,
                          const float* vals, int64_t** t_rowptr_out, int32_t** t_colidx_out, float** t_vals_out,
                          uint32_t** perm_out_keep, hipStream_t stream, std::string* err);
@@ -485,8 +486,11 @@ Schedule decide(int variant, bool exact_ok, int d, int rows_per_wave, int n_sel,
     return sc;
 }
 
+// src_bf16 / out_bf16: element types of the gather source and of the output (the schedule is the same as for fp32 operands of
+// the same width and element strides)
 template <bool SUM>
-int launch(LaunchParams& p, const h2gcn_plan* plan, uint32_t mask, LaunchShape& sh, bool off32, int forced_slice, hipStream_t stream) {
+int launch(LaunchParams& p, const h2gcn_plan* plan, uint32_t mask, LaunchShape& sh, bool off32, int forced_slice, hipStream_t stream,
+           bool src_bf16 = false, bool out_bf16 = false) {
     using namespace h2gcn;
     // A/B measurements only (profiles/r04_ab_off64_*.txt): run the 64-bit-offset instantiations on an operand that would
     // qualify for 32-bit gather offsets
@@ -556,54 +560,18 @@ int launch(LaunchParams& p, const h2gcn_plan* plan, uint32_t mask, LaunchShape& 
     const int64_t n_blocks = p.blocks_per_slice * p.n_slices;
     if (n_blocks <= 0) return H2GCN_OK;
     if (n_blocks > 0x7fffffffLL) return fail(H2GCN_ERR_INVALID_ARGUMENT, "grid too large (%lld blocks)", (long long)n_blocks);
-    const dim3 grid((unsigned)n_blocks), block(kBlock);
-#define H2GCN_LAUNCH_LISTS(VEC, LPR)                                                                                              \
-    do {                                                                                                                          \
-        if (off32 && short_fb4)                                                                                                   \
-            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, true, SUM, true, false, false, false, 4, true>), grid, block, 0, stream, p);   \
-        else if (off32)                                                                                                           \
-            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, true, SUM, true, false, false, false, 8, true>), grid, block, 0, stream, p);   \
-        else if (short_fb4)                                                                                                       \
-            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, true, SUM, false, false, false, false, 4, true>), grid, block, 0, stream, p);  \
-        else                                                                                                                      \
-            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, true, SUM, false, false, false, false, 8, true>), grid, block, 0, stream, p);  \
-    } while (0)
-#define H2GCN_LAUNCH(VEC, LPR, EXACT)                                                                             \
-    do {                                                                                                          \
-        if (gen && off32)                                                                                         \
-            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, EXACT, SUM, true, false, false, true>), grid, block, 0, stream, p);  \
-        else if (gen)                                                                                             \
-            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, EXACT, SUM, false, false, false, true>), grid, block, 0, stream, p); \
-        else if (off32 && pipe && EXACT)                                                                               \
-            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, EXACT, SUM, true, true>), grid, block, 0, stream, p);   \
-        else if (off32)                                                                                           \
-            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, EXACT, SUM, true, false>), grid, block, 0, stream, p);  \
-        else if (pipe && EXACT)                                                                                   \
-            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, EXACT, SUM, false, true>), grid, block, 0, stream, p);  \
-        else                                                                                                      \
-            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, EXACT, SUM, false, false>), grid, block, 0, stream, p); \
-    } while (0)
-    if (scalar128) {
-        H2GCN_LAUNCH(2, 64, true);  // one neighbour per load instruction, scalar base addressing
-    } else if (slice == 256) {
-        H2GCN_LAUNCH(4, 64, true);
-    } else if (slice == 128 && lists) {
-        H2GCN_LAUNCH_LISTS(4, 32);
-    } else if (slice == 64 && lists) {
-        H2GCN_LAUNCH_LISTS(4, 16);
+    const dim3 grid((unsigned)n_blocks);
+    const KernelChoice kc{scalar128, lists, shortrow, pipe, gen, off32, short_fb4, slice};
+    if (src_bf16) {
+        // bf16 gather sources: every instantiation lives in spmm_bf16.hip
+        launch_bf16(SUM, out_bf16, p, kc, grid, stream);
     } else if ((slice == 128 || slice == 64) && shortrow) {
         // the in-tile short-row kernels live in a translation unit of their own (spmm_short.hip): compiled next to them,
         // the tile-walk kernels of THIS file come out 2-6 VGPRs heavier and several of them spill (tools/kernel_resources.py)
         launch_in_tile_short(SUM, p, slice, off32, short_fb4, grid, stream);
-    } else if (slice == 128) {
-        H2GCN_LAUNCH(4, 32, true);
-    } else if (slice == 64) {
-        H2GCN_LAUNCH(4, 16, true);
     } else {
-        H2GCN_LAUNCH(1, 64, false);  // d < 4: generic column-tiled path
+        launch_spmm_kernels<SUM, float, float>(p, kc, grid, stream);
     }
-#undef H2GCN_LAUNCH
-#undef H2GCN_LAUNCH_LISTS
     H2GCN_HIP_TRY(hipGetLastError());
     return H2GCN_OK;
 }
@@ -617,12 +585,12 @@ void use_scratch(LaunchParams& p, const LaunchShape& sh, int rs, int64_t ld_src_
     const int64_t total = sh.n_src * (int64_t)n_slices * n_hop * (rs / (vec4 ? 4 : 1));
     const unsigned blocks = (unsigned)std::min<int64_t>((total + 255) / 256, 256 * 64);
     if (vec4)
-        hipLaunchKernelGGL(h2gcn::repack_slice_major_kernel<true>, dim3(blocks), dim3(256), 0, stream, p.src, sh.ld_src,
+        hipLaunchKernelGGL(h2gcn::repack_slice_major_kernel<true>, dim3(blocks), dim3(256), 0, stream, (const float*)p.src, sh.ld_src,
                            ld_src_hop, n_hop, sh.n_src, sh.d, n_slices, rs, (float*)workspace);
     else
-        hipLaunchKernelGGL(h2gcn::repack_slice_major_kernel<false>, dim3(blocks), dim3(256), 0, stream, p.src, sh.ld_src,
+        hipLaunchKernelGGL(h2gcn::repack_slice_major_kernel<false>, dim3(blocks), dim3(256), 0, stream, (const float*)p.src, sh.ld_src,
                            ld_src_hop, n_hop, sh.n_src, sh.d, n_slices, rs, (float*)workspace);
-    p.src = (const float*)workspace;
+    p.src = workspace;
     p.ld_src = rs;
     p.d_src = (sh.d + 3) & ~3;   // zero-padded: the lane that straddles d reads its own float4; lanes beyond re-read the last one
     p.src_slice_stride = sh.n_src * (int64_t)rs * n_hop;
@@ -1046,9 +1014,29 @@ int read_launch_opts(const h2gcn_launch_opts* lopts, h2gcn_launch_opts* lo) {
 }
 }  // namespace
 
-int h2gcn_spmm_hops_opts_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* X, int64_t ldx, int32_t d,
-                             float* Y, int64_t ldy_row, int64_t ldy_hop, const h2gcn_launch_opts* lopts,
-                             void* stream_v) {
+namespace {
+// bf16 arrays: 4-byte aligned base, even strides (elements) and an even width, so that every lane's load / store is dword-aligned
+int check_bf16_layout(const char* what, const void* p, int64_t ld_row, int64_t ld_hop, int32_t d) {
+    if (reinterpret_cast<uintptr_t>(p) & 3u)
+        return fail(H2GCN_ERR_INVALID_ARGUMENT, "bf16 %s: the base address must be 4-byte aligned", what);
+    if ((ld_row & 1) || (ld_hop & 1))
+        return fail(H2GCN_ERR_INVALID_ARGUMENT, "bf16 %s: row / hop strides must be even (got %lld / %lld elements)", what,
+                    (long long)ld_row, (long long)ld_hop);
+    if (d & 1) return fail(H2GCN_ERR_INVALID_ARGUMENT, "bf16 %s: the feature width d must be even (got %d)", what, d);
+    return H2GCN_OK;
+}
+
+int check_dtype(const char* what, int dtype) {
+    if (dtype != H2GCN_DTYPE_F32 && dtype != H2GCN_DTYPE_BF16)
+        return fail(H2GCN_ERR_INVALID_ARGUMENT, "%s = %d: must be H2GCN_DTYPE_F32 (%d) or H2GCN_DTYPE_BF16 (%d)", what, dtype,
+                    H2GCN_DTYPE_F32, H2GCN_DTYPE_BF16);
+    return H2GCN_OK;
+}
+
+// The forward launch for an fp32 (src_bf16 = false, fp32 output) or a bf16 gather source (fp32 or bf16 output).
+int spmm_forward(const h2gcn_plan_t* plan, uint32_t hop_mask, const void* X, bool src_bf16, int64_t ldx, int32_t d, void* Y,
+                 bool out_bf16, int64_t ldy_row, int64_t ldy_hop, const h2gcn_launch_opts* lopts, void* stream_v) {
+    const int64_t esz = src_bf16 ? 2 : 4;   // bytes per gathered element
     try {
         h2gcn_launch_opts lo;
         int st = read_launch_opts(lopts, &lo);
@@ -1058,6 +1046,10 @@ int h2gcn_spmm_hops_opts_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const 
         uint32_t mask;
         st = resolve_mask(plan, hop_mask, &mask);
         if (st != H2GCN_OK) return st;
+        if (src_bf16) {
+            if ((st = check_bf16_layout("X", X, ldx, 0, d)) != H2GCN_OK) return st;
+            if (out_bf16 && (st = check_bf16_layout("Y", Y, ldy_row, ldy_hop, d)) != H2GCN_OK) return st;
+        }
         if ((st = check_device(plan)) != H2GCN_OK) return st;
         if (d < 1) return fail(H2GCN_ERR_INVALID_ARGUMENT, "d = %d", d);
         if (plan->n_rows == 0) return H2GCN_OK;
@@ -1097,22 +1089,36 @@ int h2gcn_spmm_hops_opts_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const 
         p.n_tiles = (p.n_rows + rows_per_tile - 1) / rows_per_tile;
         p.tiles_per_xcd = (p.n_tiles + h2gcn::kNumXcd - 1) / h2gcn::kNumXcd;
         // 32-bit gather offsets when the farthest byte of X is below 4 GiB
-        bool off32 = ((double)(plan->n_cols > 0 ? plan->n_cols - 1 : 0) * (double)ldx + d) * 4.0 < 4294967296.0;
+        bool off32 = ((double)(plan->n_cols > 0 ? plan->n_cols - 1 : 0) * (double)ldx + d) * (double)esz < 4294967296.0;
         int forced_slice = plan->slice_cols;
         sh.ld_src = ldx;
         sh.d = d;
-        sh.src_line_aligned = line_aligned(X, ldx, 0, s, false);
-        const int rs = (lo.workspace_dev && aligned16(lo.workspace_dev)) ? scratch_slice_cols(plan, sh) : 0;
+        sh.src_line_aligned = line_aligned((const float*)X, ldx, 0, s, false);   // (bf16: the fp32 rule on the element stride)
+        const int rs = (!src_bf16 && lo.workspace_dev && aligned16(lo.workspace_dev)) ? scratch_slice_cols(plan, sh) : 0;
         if (rs > 0 && lo.workspace_bytes >= scratch_bytes(sh, rs)) {
             use_scratch(p, sh, rs, 0, lo.workspace_dev, (hipStream_t)stream_v, &off32);
             H2GCN_HIP_TRY(hipGetLastError());
             forced_slice = rs;
         }
         if ((st = fill_short(plan, mask, false, sh)) != H2GCN_OK) return st;
-        return launch<false>(p, plan, mask, sh, off32, forced_slice, (hipStream_t)stream_v);
+        return launch<false>(p, plan, mask, sh, off32, forced_slice, (hipStream_t)stream_v, src_bf16, out_bf16);
     } catch (...) {
-        return fail(H2GCN_ERR_INTERNAL, "unexpected exception in spmm_hops_opts_f32");
+        return fail(H2GCN_ERR_INTERNAL, "unexpected exception in spmm_hops_%s", src_bf16 ? "bf16" : "opts_f32");
     }
+}
+}  // namespace
+
+int h2gcn_spmm_hops_opts_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* X, int64_t ldx, int32_t d,
+                             float* Y, int64_t ldy_row, int64_t ldy_hop, const h2gcn_launch_opts* lopts,
+                             void* stream_v) {
+    return spmm_forward(plan, hop_mask, X, false, ldx, d, Y, false, ldy_row, ldy_hop, lopts, stream_v);
+}
+
+int h2gcn_spmm_hops_bf16(const h2gcn_plan_t* plan, uint32_t hop_mask, const uint16_t* X, int64_t ldx, int32_t d, int y_dtype,
+                         void* Y, int64_t ldy_row, int64_t ldy_hop, const h2gcn_launch_opts* lopts, void* stream_v) {
+    const int st = check_dtype("y_dtype", y_dtype);
+    if (st != H2GCN_OK) return st;
+    return spmm_forward(plan, hop_mask, X, true, ldx, d, Y, y_dtype == H2GCN_DTYPE_BF16, ldy_row, ldy_hop, lopts, stream_v);
 }
 
 int h2gcn_spmm_hops_T_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* dY, int64_t ldg_row,
@@ -1120,21 +1126,29 @@ int h2gcn_spmm_hops_T_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const flo
     return h2gcn_spmm_hops_T_opts_f32(plan, hop_mask, dY, ldg_row, ldg_hop, d, dX, ldx, nullptr, stream_v);
 }
 
-int h2gcn_spmm_hops_T_opts_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* dY, int64_t ldg_row,
-                               int64_t ldg_hop, int32_t d, float* dX, int64_t ldx, const h2gcn_launch_opts* lopts,
-                               void* stream_v) {
+namespace {
+// The adjoint launch for an fp32 (src_bf16 = false, fp32 dX) or a bf16 gradient (fp32 or bf16 dX).
+int spmm_adjoint(const h2gcn_plan_t* plan, uint32_t hop_mask, const void* dY, bool src_bf16, int64_t ldg_row, int64_t ldg_hop,
+                 int32_t d, void* dX, bool out_bf16, int64_t ldx, const h2gcn_launch_opts* lopts, void* stream_v) {
+    const int64_t esz = src_bf16 ? 2 : 4;   // bytes per gathered element
     try {
         h2gcn_launch_opts lo;
         int st = read_launch_opts(lopts, &lo);
         if (st != H2GCN_OK) return st;
         if (lo.bias_dev || (lo.flags & ~H2GCN_LAUNCH_ACCUMULATE))
             return fail(H2GCN_ERR_INVALID_ARGUMENT, "the adjoint launch has no bias / activation epilogue (only H2GCN_LAUNCH_ACCUMULATE is accepted)");
+        if (out_bf16 && (lo.flags & H2GCN_LAUNCH_ACCUMULATE))
+            return fail(H2GCN_ERR_INVALID_ARGUMENT, "H2GCN_LAUNCH_ACCUMULATE needs an fp32 dX (a bf16 dX cannot be accumulated into)");
         if (!plan) return fail(H2GCN_ERR_INVALID_ARGUMENT, "plan is NULL");
         if (!plan->has_transpose)
             return fail(H2GCN_ERR_NO_TRANSPOSE, "plan was created without H2GCN_PLAN_BUILD_TRANSPOSE");
         uint32_t mask;
         st = resolve_mask(plan, hop_mask, &mask);
         if (st != H2GCN_OK) return st;
+        if (src_bf16) {
+            if ((st = check_bf16_layout("dY", dY, ldg_row, ldg_hop, d)) != H2GCN_OK) return st;
+            if (out_bf16 && (st = check_bf16_layout("dX", dX, ldx, 0, d)) != H2GCN_OK) return st;
+        }
         if ((st = check_device(plan)) != H2GCN_OK) return st;
         if (d < 1) return fail(H2GCN_ERR_INVALID_ARGUMENT, "d = %d", d);
         if (plan->n_cols == 0) return H2GCN_OK;
@@ -1171,22 +1185,36 @@ int h2gcn_spmm_hops_T_opts_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, cons
         const int64_t rows_per_tile = (int64_t)p.rows_per_wave * h2gcn::kWavesPerBlock;
         p.n_tiles = (p.n_rows + rows_per_tile - 1) / rows_per_tile;
         p.tiles_per_xcd = (p.n_tiles + h2gcn::kNumXcd - 1) / h2gcn::kNumXcd;
-        bool off32 = ((double)(plan->n_rows > 0 ? plan->n_rows - 1 : 0) * (double)ldg_row + (double)(s - 1) * (double)ldg_hop + d) * 4.0 < 4294967296.0;
+        bool off32 = ((double)(plan->n_rows > 0 ? plan->n_rows - 1 : 0) * (double)ldg_row + (double)(s - 1) * (double)ldg_hop + d) * (double)esz < 4294967296.0;
         int forced_slice = plan->slice_cols;
         sh.ld_src = ldg_row;
         sh.d = d;
-        sh.src_line_aligned = line_aligned(dY, ldg_row, ldg_hop, s, true);
-        const int rs = (lo.workspace_dev && aligned16(lo.workspace_dev) && plan->n_rows > 0) ? scratch_slice_cols(plan, sh) : 0;
+        sh.src_line_aligned = line_aligned((const float*)dY, ldg_row, ldg_hop, s, true);   // (bf16: the fp32 rule on the element strides)
+        const int rs = (!src_bf16 && lo.workspace_dev && aligned16(lo.workspace_dev) && plan->n_rows > 0) ? scratch_slice_cols(plan, sh) : 0;
         if (rs > 0 && lo.workspace_bytes >= scratch_bytes(sh, rs)) {
             use_scratch(p, sh, rs, ldg_hop, lo.workspace_dev, (hipStream_t)stream_v, &off32);
             H2GCN_HIP_TRY(hipGetLastError());
             forced_slice = rs;
         }
         if ((st = fill_short(plan, mask, true, sh)) != H2GCN_OK) return st;
-        return launch<true>(p, plan, mask, sh, off32, forced_slice, (hipStream_t)stream_v);
+        return launch<true>(p, plan, mask, sh, off32, forced_slice, (hipStream_t)stream_v, src_bf16, out_bf16);
     } catch (...) {
-        return fail(H2GCN_ERR_INTERNAL, "unexpected exception in spmm_hops_T_f32");
+        return fail(H2GCN_ERR_INTERNAL, "unexpected exception in spmm_hops_T_%s", src_bf16 ? "bf16" : "f32");
     }
+}
+}  // namespace
+
+int h2gcn_spmm_hops_T_opts_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* dY, int64_t ldg_row,
+                               int64_t ldg_hop, int32_t d, float* dX, int64_t ldx, const h2gcn_launch_opts* lopts,
+                               void* stream_v) {
+    return spmm_adjoint(plan, hop_mask, dY, false, ldg_row, ldg_hop, d, dX, false, ldx, lopts, stream_v);
+}
+
+int h2gcn_spmm_hops_T_bf16(const h2gcn_plan_t* plan, uint32_t hop_mask, const uint16_t* dY, int64_t ldg_row, int64_t ldg_hop,
+                           int32_t d, int dx_dtype, void* dX, int64_t ldx, const h2gcn_launch_opts* lopts, void* stream_v) {
+    const int st = check_dtype("dx_dtype", dx_dtype);
+    if (st != H2GCN_OK) return st;
+    return spmm_adjoint(plan, hop_mask, dY, true, ldg_row, ldg_hop, d, dX, dx_dtype == H2GCN_DTYPE_BF16, ldx, lopts, stream_v);
 }
 
 }  // extern "C"

@@ -27,7 +27,8 @@
 // Floating point: fp32 multiply-add per nonzero, ONE CANONICAL SUMMATION TREE per output element:
 //     neighbour j of a (row, hop) segment (j = its position in the row's ascending column order, the reference's
 //     order) is added, in ascending j, into partial  P[j mod 4];  the row's value is  (P0 + P1) + (P2 + P3).
-// Every kernel in this file produces exactly that tree whatever its lane geometry: with 64-column slices the four
+// A bf16 gather source (ABI 5) is widened exactly to fp32 element by element, so it runs through the same tree (a bf16 output
+// is the round-to-nearest-even of the fp32 value).  Every kernel in this file produces exactly that tree whatever its lane geometry: with 64-column slices the four
 // lane groups of a wave each own one partial and the fold is v_permlane16_swap / v_permlane32_swap; with 128-column
 // slices a lane group keeps two partials in registers (even / odd steps), with 256-column slices and in the generic
 // column-tiled kernel a lane keeps all four; the short-row mode keeps four per lane group.  (A segment with >=
@@ -114,11 +115,11 @@ struct LaunchParams {
     int d;           // feature columns of the output
     int d_src;       // readable columns of a gather-source row (== d in place; d rounded up to 4 in the zero-padded scratch)
     int64_t n_rows;  // rows of the output
-    const float* src;
+    const void* src;  // float or bf16 (the kernel's TS)
     int64_t ld_src;
     int64_t src_slice_stride;  // EXACT kernels: element offset of column slice q in the gather source = q * this
                                // (row-major source: slice_cols; slice-major scratch copy: n_src_rows * slice_cols)
-    float* dst;
+    void* dst;        // float or bf16 (the kernel's TD)
     int64_t ld_dst;
     const int64_t* long_list; // forward: (row << 4 | s) per long segment; SUM: row per long row
     int n_long;
@@ -168,6 +169,47 @@ template <>
 struct VecT<4> {
     typedef float type __attribute__((ext_vector_type(4), aligned(4)));
 };
+
+// bf16 storage element: the upper 16 bits of an fp32 (sign, 8 exponent bits, 7 significand bits).  Gathered bf16 values are
+// widened EXACTLY (a 16-bit shift); outputs are rounded to nearest even (v_cvt_pk_bf16_f32), which is torch's
+// .to(torch.bfloat16), ties and overflow to inf included.
+struct bf16 {
+    uint16_t bits;
+};
+
+// What one lane's gather of VEC elements of type TS loads: fp32 -- VEC floats (16 / 8 / 4 bytes); bf16 -- VEC bf16 packed in
+// dwords (8 / 4 bytes; 2 bytes for the column-tiled VEC = 1 kernel).  Every bf16 load of 4 or 8 bytes is dword-aligned
+// (4-byte aligned base, even strides and widths: checked on the host).
+template <typename TS, int VEC>
+struct LoadT {
+    using type = typename VecT<VEC>::type;
+};
+template <>
+struct LoadT<bf16, 4> {
+    typedef uint32_t type __attribute__((ext_vector_type(2), aligned(4)));
+};
+template <>
+struct LoadT<bf16, 2> {
+    using type = uint32_t;
+};
+template <>
+struct LoadT<bf16, 1> {
+    using type = uint16_t;
+};
+
+template <typename TS>
+__device__ __forceinline__ const TS* src_ptr(const void* p) { return reinterpret_cast<const TS*>(p); }
+template <typename TD>
+__device__ __forceinline__ TD* dst_ptr(void* p) { return reinterpret_cast<TD*>(p); }
+
+__device__ __forceinline__ float bf16_lo(uint32_t w) { return __uint_as_float(w << 16); }
+__device__ __forceinline__ float bf16_hi(uint32_t w) { return __uint_as_float(w & 0xffff0000u); }
+// round to nearest even, two at a time: v_cvt_pk_bf16_f32
+__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+    const bf16x2 v = {(__bf16)lo, (__bf16)hi};
+    return __builtin_bit_cast(uint32_t, v);
+}
 
 __device__ __forceinline__ int wave_uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
@@ -237,18 +279,40 @@ __device__ __forceinline__ void zero_acc(float (&acc)[NP][VEC]) {
         for (int i = 0; i < VEC; ++i) acc[k][i] = 0.f;
 }
 
-template <int VEC>
-__device__ __forceinline__ typename VecT<VEC>::type load_vec(const float* p) {
+template <typename TS, int VEC>
+__device__ __forceinline__ typename LoadT<TS, VEC>::type load_vec(const void* p) {
 #ifdef H2GCN_NT_GATHER
-    return __builtin_nontemporal_load(reinterpret_cast<const typename VecT<VEC>::type*>(p));
+    return __builtin_nontemporal_load(reinterpret_cast<const typename LoadT<TS, VEC>::type*>(p));
 #else
-    return *reinterpret_cast<const typename VecT<VEC>::type*>(p);
+    return *reinterpret_cast<const typename LoadT<TS, VEC>::type*>(p);
 #endif
 }
 
-template <int VEC>
-__device__ __forceinline__ void fma_vec(float (&acc)[VEC], float w, typename VecT<VEC>::type x) {
-    if constexpr (VEC == 1) {
+// the value of a gather a padding slot does not issue (it is multiplied by 0)
+template <typename TS, int VEC>
+__device__ __forceinline__ typename LoadT<TS, VEC>::type zero_load() {
+    if constexpr (std::is_same<TS, float>::value && VEC > 1) return (typename VecT<VEC>::type)(0.f);
+    else return (typename LoadT<TS, VEC>::type)0;
+}
+
+// acc[i] += w * x[i] in fp32; a bf16 element is widened exactly first, so the products and sums are those of the fp32
+// kernel on the upcast operand
+template <typename TS, int VEC>
+__device__ __forceinline__ void fma_vec(float (&acc)[VEC], float w, typename LoadT<TS, VEC>::type x) {
+    if constexpr (std::is_same<TS, bf16>::value) {
+        if constexpr (VEC == 1) {
+            acc[0] = fmaf(w, __uint_as_float((uint32_t)x << 16), acc[0]);
+        } else if constexpr (VEC == 2) {
+            acc[0] = fmaf(w, bf16_lo(x), acc[0]);
+            acc[1] = fmaf(w, bf16_hi(x), acc[1]);
+        } else {
+#pragma unroll
+            for (int i = 0; i < VEC / 2; ++i) {
+                acc[2 * i] = fmaf(w, bf16_lo(x[i]), acc[2 * i]);
+                acc[2 * i + 1] = fmaf(w, bf16_hi(x[i]), acc[2 * i + 1]);
+            }
+        }
+    } else if constexpr (VEC == 1) {
         acc[0] = fmaf(w, x, acc[0]);
     } else {
 #pragma unroll
@@ -264,11 +328,11 @@ struct GatherAddr {
     const char* base;                                   // wave-uniform: src + hop offset + column offset
     typename std::conditional<OFF32, uint32_t, int64_t>::type lane_off;  // byte offset of this lane inside a row
     typename std::conditional<OFF32, uint32_t, int64_t>::type ld_bytes;  // row stride in bytes
-    __device__ __forceinline__ const float* row(int col) const {
+    __device__ __forceinline__ const void* row(int col) const {
         if constexpr (OFF32) {
-            return reinterpret_cast<const float*>(base + (uint32_t)(lane_off + (uint32_t)col * ld_bytes));
+            return base + (uint32_t)(lane_off + (uint32_t)col * ld_bytes);
         } else {
-            return reinterpret_cast<const float*>(base + (lane_off + (int64_t)col * ld_bytes));
+            return base + (lane_off + (int64_t)col * ld_bytes);
         }
     }
 };
@@ -278,11 +342,11 @@ struct GatherAddr {
 // The cross-lane reads of (c, v) always run with the full wave active (ds_bpermute returns 0 for a source
 // lane that is masked off); only the gather itself is predicated, by `take` (false on lanes whose slot is
 // padding -- they must not touch src: 0 * Inf would poison the row).
-template <int VEC, int LPR, int U, bool PREDICATED, bool OFF32, int PHASE = 0, int NP>
+template <typename TS, int VEC, int LPR, int U, bool PREDICATED, bool OFF32, int PHASE = 0, int NP>
 __device__ __forceinline__ void gather_batch(int c, float v, int t, int g, const GatherAddr<OFF32>& addr, bool take,
                                              float (&acc)[NP][VEC]) {
     constexpr int G = kWave / LPR;
-    typename VecT<VEC>::type x[U];
+    typename LoadT<TS, VEC>::type x[U];
     float w[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
@@ -296,22 +360,22 @@ __device__ __forceinline__ void gather_batch(int c, float v, int t, int g, const
             cj = lane_gather(c, idx);
             w[u] = lane_gather(v, idx);
         }
-        const float* p = addr.row(cj);
+        const void* p = addr.row(cj);
         if constexpr (PREDICATED) {
             if (take) {
-                x[u] = load_vec<VEC>(p);
+                x[u] = load_vec<TS, VEC>(p);
             } else {
                 w[u] = 0.f;
-                if constexpr (VEC == 1) x[u] = 0.f; else x[u] = (typename VecT<VEC>::type)(0.f);
+                x[u] = zero_load<TS, VEC>();
             }
         } else {
-            x[u] = load_vec<VEC>(p);
+            x[u] = load_vec<TS, VEC>(p);
         }
     }
     // step t+u serves neighbour (t+u)*G + g -> canonical partial ((t+u)*G + g) % 4 = lane-local partial (t+u) % NP;
     // the caller states t % NP as PHASE, so the partial of every step is a compile-time register choice
 #pragma unroll
-    for (int u = 0; u < U; ++u) fma_vec<VEC>(acc[(PHASE + u) % NP], w[u], x[u]);
+    for (int u = 0; u < U; ++u) fma_vec<TS, VEC>(acc[(PHASE + u) % NP], w[u], x[u]);
 }
 
 // (column id, value) of neighbour `lane` of the 64-wide chunk starting at `base` (zero beyond the segment end)
@@ -329,48 +393,48 @@ __device__ __forceinline__ void load_chunk(const int32_t* __restrict__ colidx, c
 // MAXB: deepest load batch (8 in the bandwidth kernels; 4 where register pressure matters more than the last few
 // percent on long segments -- the fallback walk of the short-row kernels).  The batch depth only re-times loads: the
 // accumulation order, hence the bits, do not depend on it.
-template <int VEC, int LPR, bool MASKED, bool OFF32, int MAXB = H2GCN_MAIN_MAXB, int NP>
+template <typename TS, int VEC, int LPR, bool MASKED, bool OFF32, int MAXB = H2GCN_MAIN_MAXB, int NP>
 __device__ __forceinline__ void process_chunk(int c, float v, int n, int g, const GatherAddr<OFF32>& addr,
                                               bool lane_active, float (&acc)[NP][VEC]) {
     constexpr int G = kWave / LPR;
     const int full = n / G;  // steps in which every lane group has a neighbour
     int t = 0;               // batches of 8 / 4 start at t % 4 == 0: partial phase 0
     if constexpr (MAXB >= 8)
-        for (; t + 8 <= full; t += 8) gather_batch<VEC, LPR, 8, MASKED, OFF32>(c, v, t, g, addr, lane_active, acc);
+        for (; t + 8 <= full; t += 8) gather_batch<TS, VEC, LPR, 8, MASKED, OFF32>(c, v, t, g, addr, lane_active, acc);
     if constexpr (MAXB < 8)
-        for (; t + 4 <= full; t += 4) gather_batch<VEC, LPR, 4, MASKED, OFF32>(c, v, t, g, addr, lane_active, acc);
+        for (; t + 4 <= full; t += 4) gather_batch<TS, VEC, LPR, 4, MASKED, OFF32>(c, v, t, g, addr, lane_active, acc);
     if (t + 4 <= full) {
-        gather_batch<VEC, LPR, 4, MASKED, OFF32>(c, v, t, g, addr, lane_active, acc);
+        gather_batch<TS, VEC, LPR, 4, MASKED, OFF32>(c, v, t, g, addr, lane_active, acc);
         t += 4;
     }
     // the last 0..3 full steps and (G > 1) the ragged step in which only the first (n - full*G) groups still have a
     // neighbour, with the phase of every step spelled out
     const int rem = n - full * G;
     if (t + 2 <= full) {
-        gather_batch<VEC, LPR, 2, MASKED, OFF32>(c, v, t, g, addr, lane_active, acc);
+        gather_batch<TS, VEC, LPR, 2, MASKED, OFF32>(c, v, t, g, addr, lane_active, acc);
         t += 2;
         if (t + 1 <= full) {
-            gather_batch<VEC, LPR, 1, MASKED, OFF32, 2 % NP>(c, v, t, g, addr, lane_active, acc);
+            gather_batch<TS, VEC, LPR, 1, MASKED, OFF32, 2 % NP>(c, v, t, g, addr, lane_active, acc);
             if constexpr (G > 1)
-                if (rem > 0) gather_batch<VEC, LPR, 1, true, OFF32, 3 % NP>(c, v, full, g, addr, lane_active && g < rem, acc);
+                if (rem > 0) gather_batch<TS, VEC, LPR, 1, true, OFF32, 3 % NP>(c, v, full, g, addr, lane_active && g < rem, acc);
         } else {
             if constexpr (G > 1)
-                if (rem > 0) gather_batch<VEC, LPR, 1, true, OFF32, 2 % NP>(c, v, full, g, addr, lane_active && g < rem, acc);
+                if (rem > 0) gather_batch<TS, VEC, LPR, 1, true, OFF32, 2 % NP>(c, v, full, g, addr, lane_active && g < rem, acc);
         }
     } else if (t + 1 <= full) {
-        gather_batch<VEC, LPR, 1, MASKED, OFF32>(c, v, t, g, addr, lane_active, acc);
+        gather_batch<TS, VEC, LPR, 1, MASKED, OFF32>(c, v, t, g, addr, lane_active, acc);
         if constexpr (G > 1)
-            if (rem > 0) gather_batch<VEC, LPR, 1, true, OFF32, 1 % NP>(c, v, full, g, addr, lane_active && g < rem, acc);
+            if (rem > 0) gather_batch<TS, VEC, LPR, 1, true, OFF32, 1 % NP>(c, v, full, g, addr, lane_active && g < rem, acc);
     } else {
         if constexpr (G > 1)
-            if (rem > 0) gather_batch<VEC, LPR, 1, true, OFF32>(c, v, full, g, addr, lane_active && g < rem, acc);
+            if (rem > 0) gather_batch<TS, VEC, LPR, 1, true, OFF32>(c, v, full, g, addr, lane_active && g < rem, acc);
     }
 }
 
 // Accumulate sum_j val_j * src[col_j, :] over the nonzeros [seg_begin, seg_end) of one CSR row, taking the
 // 64-wide chunks chunk0, chunk0+chunk_step, ... (regular path: all of them; long path: this wave's share).
 // Each lane group accumulates its neighbours in ascending order into acc.
-template <int VEC, int LPR, bool MASKED, bool OFF32, int MAXB = H2GCN_MAIN_MAXB, int NP>
+template <typename TS, int VEC, int LPR, bool MASKED, bool OFF32, int MAXB = H2GCN_MAIN_MAXB, int NP>
 __device__ __forceinline__ void accumulate_segment(const int32_t* __restrict__ colidx,
                                                    const float* __restrict__ vals, int64_t seg_begin,
                                                    int64_t seg_end, int chunk0, int chunk_step,
@@ -383,7 +447,7 @@ __device__ __forceinline__ void accumulate_segment(const int32_t* __restrict__ c
         int c;
         float v;
         load_chunk(colidx, vals, base, seg_end, lane, c, v);
-        process_chunk<VEC, LPR, MASKED, OFF32, MAXB>(c, v, n, g, addr, lane_active, acc);
+        process_chunk<TS, VEC, LPR, MASKED, OFF32, MAXB>(c, v, n, g, addr, lane_active, acc);
     }
 }
 
@@ -391,7 +455,7 @@ __device__ __forceinline__ void accumulate_segment(const int32_t* __restrict__ c
 // still gathering, and every further chunk is fetched before the current one is processed -- the index fetch
 // latency leaves the per-segment dependency chain (index -> gather -> fold -> store), which is what bounds
 // short rows.  Loads retire in order, so waiting for the gathers implies the prefetch has landed.
-template <int VEC, int LPR, bool OFF32, int MAXB = H2GCN_MAIN_MAXB, int NP>
+template <typename TS, int VEC, int LPR, bool OFF32, int MAXB = H2GCN_MAIN_MAXB, int NP>
 __device__ __forceinline__ void accumulate_segment_prefetched(const int32_t* __restrict__ colidx,
                                                               const float* __restrict__ vals, int64_t seg_begin,
                                                               int64_t seg_end, int c, float v,
@@ -404,7 +468,7 @@ __device__ __forceinline__ void accumulate_segment_prefetched(const int32_t* __r
         int c_next = 0;
         float v_next = 0.f;
         if (left > kWave) load_chunk(colidx, vals, base + kWave, seg_end, lane, c_next, v_next);
-        process_chunk<VEC, LPR, false, OFF32, MAXB>(c, v, n, g, addr, true, acc);
+        process_chunk<TS, VEC, LPR, false, OFF32, MAXB>(c, v, n, g, addr, true, acc);
         c = c_next;
         v = v_next;
     }
@@ -416,28 +480,28 @@ __device__ __forceinline__ void accumulate_segment_prefetched(const int32_t* __r
 // keeps the four partials P[j mod 4] in registers and combines them as (P0 + P1) + (P2 + P3).
 // Handles segments of at most LPR nonzeros (one index fetch per group): `c`, `v` hold the group's indices/values
 // lane-wise (lane li of the group = neighbour li), `n_mine` its length, `n_max` the longest of the round (uniform).
-template <int VEC, int LPR, bool OFF32>
+template <typename TS, int VEC, int LPR, bool OFF32>
 __device__ __forceinline__ void accumulate_grouped(int c, float v, int n_mine, int n_max, int lane,
                                                    const GatherAddr<OFF32>& addr, float (&part)[kTreeParts][VEC]) {
     constexpr int U = kTreeParts;  // neighbours per batch: neighbour t+u (t % 4 == 0) -> canonical partial u
     const int group_base = lane & ~(LPR - 1);
     for (int t = 0; t < n_max; t += U) {
-        typename VecT<VEC>::type x[U];
+        typename LoadT<TS, VEC>::type x[U];
         float w[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
             const int cj = lane_gather(c, group_base + t + u);
             w[u] = lane_gather(v, group_base + t + u);
             if (t + u < n_mine) {
-                x[u] = load_vec<VEC>(addr.row(cj));
+                x[u] = load_vec<TS, VEC>(addr.row(cj));
             } else {
                 w[u] = 0.f;
-                if constexpr (VEC == 1) x[u] = 0.f; else x[u] = (typename VecT<VEC>::type)(0.f);
+                x[u] = zero_load<TS, VEC>();
             }
         }
 #pragma unroll
         for (int u = 0; u < U; ++u)
-            if (t + u < n_mine) fma_vec<VEC>(part[u], w[u], x[u]);
+            if (t + u < n_mine) fma_vec<TS, VEC>(part[u], w[u], x[u]);
     }
 }
 
@@ -462,9 +526,30 @@ __device__ __forceinline__ void epilogue(float (&acc)[VEC], const float* __restr
     }
 }
 
-template <int VEC>
-__device__ __forceinline__ void store_vec(float* p, const float (&acc)[VEC]) {
-    if constexpr (VEC == 1) {
+// one finished output element: fp32 as it is, bf16 rounded to nearest even
+template <typename TD>
+__device__ __forceinline__ void store_one(TD* p, float t) {
+    if constexpr (std::is_same<TD, bf16>::value)
+        __builtin_nontemporal_store(__builtin_bit_cast(uint16_t, (__bf16)t), reinterpret_cast<uint16_t*>(p));
+    else
+        __builtin_nontemporal_store(t, p);
+}
+
+template <typename TD, int VEC>
+__device__ __forceinline__ void store_vec(TD* p, const float (&acc)[VEC]) {
+    if constexpr (std::is_same<TD, bf16>::value) {
+        // VEC bf16 = VEC / 2 dwords (VEC = 4: one 8-byte store; the output base, strides and width are even, so dword-aligned)
+        if constexpr (VEC == 1) {
+            store_one<TD>(p, acc[0]);
+        } else if constexpr (VEC == 2) {
+            __builtin_nontemporal_store(pack_bf16x2(acc[0], acc[1]), reinterpret_cast<uint32_t*>(p));
+        } else {
+            typename LoadT<bf16, VEC>::type o;
+#pragma unroll
+            for (int i = 0; i < VEC / 2; ++i) o[i] = pack_bf16x2(acc[2 * i], acc[2 * i + 1]);
+            __builtin_nontemporal_store(o, reinterpret_cast<typename LoadT<bf16, VEC>::type*>(p));
+        }
+    } else if constexpr (VEC == 1) {
         __builtin_nontemporal_store(acc[0], p);
     } else {
         typename VecT<VEC>::type o;
@@ -487,22 +572,23 @@ __device__ __forceinline__ void store_vec(float* p, const float (&acc)[VEC]) {
 // the output row.  Plain kernels: one 16-byte store when the whole vector lies inside d.  General-store kernels (GEN)
 // add the bias / ReLU epilogue and let the tail lane store the columns it owns element-wise -- which is how odd feature
 // widths (reference: any b.shape[1], _layers.py:62-76) run on the float4 gather kernels.
-template <int VEC, bool GEN, typename P>
-__device__ __forceinline__ void store_out(const P& p, float* row, int col0, int ecol, float (&tot)[VEC]) {
+template <typename TD, int VEC, bool GEN, typename P>
+__device__ __forceinline__ void store_out(const P& p, TD* row, int col0, int ecol, float (&tot)[VEC]) {
+    constexpr bool kF32 = std::is_same<TD, float>::value;   // (accumulate exists for fp32 outputs only)
     if (col0 + VEC <= p.d) {
         if constexpr (GEN) {
-            if (p.accumulate) {
+            if (kF32 && p.accumulate) {
                 if constexpr (VEC == 1) {
-                    tot[0] += row[col0];
+                    tot[0] += reinterpret_cast<const float*>(row)[col0];
                 } else {
-                    const typename VecT<VEC>::type old = *reinterpret_cast<const typename VecT<VEC>::type*>(row + col0);
+                    const typename VecT<VEC>::type old = *reinterpret_cast<const typename VecT<VEC>::type*>(reinterpret_cast<const float*>(row) + col0);
 #pragma unroll
                     for (int i = 0; i < VEC; ++i) tot[i] += old[i];
                 }
             }
             epilogue<VEC>(tot, p.bias, p.relu, col0);
         }
-        store_vec<VEC>(row + col0, tot);
+        store_vec<TD, VEC>(row + col0, tot);
         return;
     }
     if constexpr (GEN) {
@@ -512,10 +598,10 @@ __device__ __forceinline__ void store_out(const P& p, float* row, int col0, int 
                 const int c = ecol + i;
                 if (c >= col0 && c < p.d) {
                     float t = tot[i];
-                    if (p.accumulate) t += row[c];
+                    if (kF32 && p.accumulate) t += reinterpret_cast<const float*>(row)[c];
                     if (p.bias) t += p.bias[c];
                     if (p.relu) t = fmaxf(t, 0.f);
-                    __builtin_nontemporal_store(t, row + c);
+                    store_one<TD>(row + c, t);
                 }
             }
         }
@@ -540,7 +626,7 @@ __device__ __forceinline__ void store_out(const P& p, float* row, int col0, int 
 // hops are short; the partials run on across the hops exactly as the wave walk's accumulators do.
 // The arithmetic is the canonical tree of the header comment (a group keeps P[j mod 4] in registers, combined as
 // (P0 + P1) + (P2 + P3)), so which class served a segment can never be seen in the result.
-template <int VEC, int LPR, bool SUM, bool OFF32, bool EPI, int PD>
+template <typename TS, typename TD, int VEC, int LPR, bool SUM, bool OFF32, bool EPI, int PD>
 __device__ __forceinline__ void short_list_blocks(const LaunchParams& p, int64_t sblock, int lane, int wave, int64_t lane_off0,
                                                   int64_t src_col_begin, int lcol, int ecol,
                                                   uint64_t (&s_seg)[kWavesPerBlock][kShortSumHops][kWave],
@@ -631,15 +717,15 @@ __device__ __forceinline__ void short_list_blocks(const LaunchParams& p, int64_t
 #pragma unroll
         for (int gg = 0; gg < G; ++gg) n_max = max(n_max, __builtin_amdgcn_readlane(len, gg * LPR));
         const int hs = SUM ? s : hop;
-        const GatherAddr<OFF32> addr{reinterpret_cast<const char*>(p.src + p.src_hop_off[hs] + src_col_begin - VEC), (off_t)lane_off0,
-                                     (off_t)(p.ld_src * 4)};
-        accumulate_grouped<VEC, LPR, OFF32>(c, v, len, n_max, lane, addr, part);
+        const GatherAddr<OFF32> addr{reinterpret_cast<const char*>(src_ptr<TS>(p.src) + p.src_hop_off[hs] + src_col_begin - VEC), (off_t)lane_off0,
+                                     (off_t)(p.ld_src * sizeof(TS))};
+        accumulate_grouped<TS, VEC, LPR, OFF32>(c, v, len, n_max, lane, addr, part);
         if (s == NS - 1) {
             if (len >= 0) {
                 float tot[VEC];
                 combine_partials<VEC>(part, tot);
                 const int64_t row = s_row[wave][t * G + g];
-                store_out<VEC, EPI>(p, p.dst + row * p.ld_dst + (SUM ? 0 : p.dst_hop_off[hop]), lcol, ecol, tot);
+                store_out<TD, VEC, EPI>(p, dst_ptr<TD>(p.dst) + row * p.ld_dst + (SUM ? 0 : p.dst_hop_off[hop]), lcol, ecol, tot);
             }
             s = 0;
             ++t;
@@ -653,7 +739,7 @@ __device__ __forceinline__ void short_list_blocks(const LaunchParams& p, int64_t
 // Forward: an entry is a (row, hop) segment of the hop the workgroup's list belongs to; SUM: a row that is neither listed
 // as short nor owned by the long path, all selected hops' segments accumulated into one output row.  Lane j*NS + s fetches
 // the row pointers of entry j, hop s; the walk itself is accumulate_segment, i.e. the tile walk's arithmetic.
-template <int VEC, int LPR, bool SUM, bool OFF32, bool EPI, int MAXB>
+template <typename TS, typename TD, int VEC, int LPR, bool SUM, bool OFF32, bool EPI, int MAXB>
 __device__ __forceinline__ void medium_list_blocks(const LaunchParams& p, int64_t mblock, int lane, int wave, int64_t lane_off0,
                                                    int64_t src_col_begin, int lcol, int ecol) {
     using off_t = typename std::conditional<OFF32, uint32_t, int64_t>::type;
@@ -699,13 +785,13 @@ __device__ __forceinline__ void medium_list_blocks(const LaunchParams& p, int64_
             bounds(j * NS + s, sb, se);
             const int hs = SUM ? s : hop;
             const HopCsr& h = p.hop[hs];
-            const GatherAddr<OFF32> addr{reinterpret_cast<const char*>(p.src + p.src_hop_off[hs] + src_col_begin - VEC), (off_t)lane_off0,
-                                         (off_t)(p.ld_src * 4)};
-            accumulate_segment<VEC, LPR, false, OFF32, MAXB>(h.colidx, h.vals, sb, se, 0, 1, addr, lane, true, acc);
+            const GatherAddr<OFF32> addr{reinterpret_cast<const char*>(src_ptr<TS>(p.src) + p.src_hop_off[hs] + src_col_begin - VEC), (off_t)lane_off0,
+                                         (off_t)(p.ld_src * sizeof(TS))};
+            accumulate_segment<TS, VEC, LPR, false, OFF32, MAXB>(h.colidx, h.vals, sb, se, 0, 1, addr, lane, true, acc);
         }
         float tot[VEC];
         fold_tree<VEC, LPR, NP>(acc, tot);
-        if (g == 0) store_out<VEC, EPI>(p, p.dst + orow * p.ld_dst + (SUM ? 0 : p.dst_hop_off[hop]), lcol, ecol, tot);
+        if (g == 0) store_out<TD, VEC, EPI>(p, dst_ptr<TD>(p.dst) + orow * p.ld_dst + (SUM ? 0 : p.dst_hop_off[hop]), lcol, ecol, tot);
     }
 }
 
@@ -713,7 +799,7 @@ __device__ __forceinline__ void medium_list_blocks(const LaunchParams& p, int64_
 // Rounds of G consecutive rows (one hop) whose segments are all <= LPR nonzeros are served one lane group per segment
 // (accumulate_grouped), with the next round's index fetch issued before the current round gathers; other rounds fall back to
 // the wave-per-segment walk with load batches of FB.  (Instantiated in spmm_short.hip only -- see there.)
-template <int VEC, int LPR, bool SUM, bool OFF32, bool EPI, int FB>
+template <typename TS, typename TD, int VEC, int LPR, bool SUM, bool OFF32, bool EPI, int FB>
 __device__ __forceinline__ void in_tile_short_rows(const LaunchParams& p, int lane, int rpw, int64_t row0, int rows_here, int rp_lo, int rp_hi,
                                                    int64_t lane_off0_, int64_t src_col_begin, int lcol, int ecol) {
     using off_t = typename std::conditional<OFF32, uint32_t, int64_t>::type;
@@ -729,7 +815,7 @@ __device__ __forceinline__ void in_tile_short_rows(const LaunchParams& p, int la
         constexpr int G = kWave / LPR;
         const int short_max = min(LPR, p.long_threshold - 1);
         const int n_blocks = (rows_here + G - 1) / G;       // row blocks of G consecutive rows
-        const GatherAddr<OFF32> addr0{nullptr, lane_off0, (off_t)(p.ld_src * 4)};
+        const GatherAddr<OFF32> addr0{nullptr, lane_off0, (off_t)(p.ld_src * sizeof(TS))};
         // wave-per-segment walk of one row (all hops in SUM mode, hop `s_only` otherwise) -- the general path
         auto row_wave_wide = [&](int r, int s_first, int s_last) {
             float acc[NP][VEC];
@@ -746,19 +832,19 @@ __device__ __forceinline__ void in_tile_short_rows(const LaunchParams& p, int la
                 if (!SUM && se - sb >= p.long_threshold) continue;
                 const HopCsr& h = p.hop[s];
                 GatherAddr<OFF32> addr = addr0;
-                addr.base = reinterpret_cast<const char*>(p.src + p.src_hop_off[s] + src_col_begin - kBias);
-                accumulate_segment<VEC, LPR, false, OFF32, FB>(h.colidx, h.vals, sb, se, 0, 1, addr, lane, true, acc);
+                addr.base = reinterpret_cast<const char*>(src_ptr<TS>(p.src) + p.src_hop_off[s] + src_col_begin - kBias);
+                accumulate_segment<TS, VEC, LPR, false, OFF32, FB>(h.colidx, h.vals, sb, se, 0, 1, addr, lane, true, acc);
                 if constexpr (!SUM) {
                     float tot[VEC];
                     fold_tree<VEC, LPR, NP>(acc, tot);
-                    if (g == 0) store_out<VEC, EPI>(p, p.dst + (row0 + r) * p.ld_dst + p.dst_hop_off[s], lcol, ecol, tot);
+                    if (g == 0) store_out<TD, VEC, EPI>(p, dst_ptr<TD>(p.dst) + (row0 + r) * p.ld_dst + p.dst_hop_off[s], lcol, ecol, tot);
                     zero_acc<VEC, NP>(acc);
                 }
             }
             if constexpr (SUM) {
                 float tot[VEC];
                 fold_tree<VEC, LPR, NP>(acc, tot);
-                if (g == 0) store_out<VEC, EPI>(p, p.dst + (row0 + r) * p.ld_dst, lcol, ecol, tot);
+                if (g == 0) store_out<TD, VEC, EPI>(p, dst_ptr<TD>(p.dst) + (row0 + r) * p.ld_dst, lcol, ecol, tot);
             }
         };
         // (begin, length) of the segment (hop s, row b*G + g) for this lane's group; length -1 for rows beyond the tile
@@ -805,11 +891,11 @@ __device__ __forceinline__ void in_tile_short_rows(const LaunchParams& p, int la
                     float part[kTreeParts][VEC];
                     zero_acc<VEC, kTreeParts>(part);
                     GatherAddr<OFF32> addr = addr0;
-                    addr.base = reinterpret_cast<const char*>(p.src + p.src_hop_off[s] + src_col_begin - kBias);
-                    accumulate_grouped<VEC, LPR, OFF32>(c, v, len, n_max, lane, addr, part);
+                    addr.base = reinterpret_cast<const char*>(src_ptr<TS>(p.src) + p.src_hop_off[s] + src_col_begin - kBias);
+                    accumulate_grouped<TS, VEC, LPR, OFF32>(c, v, len, n_max, lane, addr, part);
                     float tot[VEC];
                     combine_partials<VEC>(part, tot);
-                    if (len >= 0) store_out<VEC, EPI>(p, p.dst + (row0 + blk * G + g) * p.ld_dst + p.dst_hop_off[s], lcol, ecol, tot);
+                    if (len >= 0) store_out<TD, VEC, EPI>(p, dst_ptr<TD>(p.dst) + (row0 + blk * G + g) * p.ld_dst + p.dst_hop_off[s], lcol, ecol, tot);
                 } else {
                     for (int gg = 0; gg < G && blk * G + gg < rows_here; ++gg) row_wave_wide(blk * G + gg, s, s + 1);
                 }
@@ -858,12 +944,12 @@ __device__ __forceinline__ void in_tile_short_rows(const LaunchParams& p, int la
 #pragma unroll
                         for (int gg = 0; gg < G; ++gg) n_max = max(n_max, __builtin_amdgcn_readlane(len, gg * LPR));
                         GatherAddr<OFF32> addr = addr0;
-                        addr.base = reinterpret_cast<const char*>(p.src + p.src_hop_off[s] + src_col_begin - kBias);
-                        accumulate_grouped<VEC, LPR, OFF32>(c, v, len, n_max, lane, addr, part);
+                        addr.base = reinterpret_cast<const char*>(src_ptr<TS>(p.src) + p.src_hop_off[s] + src_col_begin - kBias);
+                        accumulate_grouped<TS, VEC, LPR, OFF32>(c, v, len, n_max, lane, addr, part);
                     }
                     float tot[VEC];
                     combine_partials<VEC>(part, tot);
-                    if (valid) store_out<VEC, EPI>(p, p.dst + (row0 + blk * G + g) * p.ld_dst, lcol, ecol, tot);
+                    if (valid) store_out<TD, VEC, EPI>(p, dst_ptr<TD>(p.dst) + (row0 + blk * G + g) * p.ld_dst, lcol, ecol, tot);
                 } else {
                     if (blk + 1 < n_blocks) fetch(blk + 1, 0, nxt_short);
                     for (int gg = 0; gg < G && blk * G + gg < rows_here; ++gg) row_wave_wide(blk * G + gg, 0, n_sel);
@@ -884,6 +970,18 @@ constexpr bool heavy_registers() {
     if (SHORT) return (SUM && (!OFF32 || LPR >= 32)) || (!OFF32 && LPR >= 32);   // (the list-driven kernels at FB = 8)
     if (!OFF32) return EPI || LPR >= 32 || PIPE;
     return PIPE && LPR == 32;
+}
+
+// bf16 gather sources: the instantiations whose fp32 bound leaves them short of registers (scratch; tools/kernel_resources.py)
+// run one wave per SIMD lower -- the list-driven adjoint at FB = 4 with 64-bit offsets, the general store of 128-column slices
+// with 32-bit offsets, the prefetching adjoint walk of 64-column slices and the plain forward walk of 64-column slices with
+// 64-bit offsets.  (Unpacking a bf16 pair costs a register per element in flight: the bf16 kernels are not lighter than the
+// fp32 ones.)
+template <typename TS, int VEC, int LPR, bool SUM, bool OFF32, bool PIPE, bool SHORT, bool EPI, int FB, bool LISTS>
+constexpr bool bf16_one_wave_less() {
+    if (!std::is_same<TS, bf16>::value || VEC != 4 || SHORT) return false;
+    if (LISTS) return FB == 4 && SUM && !OFF32;
+    return (OFF32 && EPI && LPR == 32) || (SUM && OFF32 && PIPE && LPR == 16) || (!SUM && !OFF32 && !PIPE && !EPI && LPR == 16);
 }
 
 // VEC    floats per lane per gathered row (4 on the fast paths)
@@ -907,14 +1005,18 @@ constexpr bool heavy_registers() {
 // EPI    general store (see store_out): optional bias / ReLU epilogue, element-wise bounded stores for odd widths and
 //        unaligned outputs (separate instantiations: the extra registers would otherwise push the 6-waves-per-SIMD
 //        variants of the plain aggregation into spilling)
+// TS, TD element types of the gather source and of the output: float, float everywhere but in spmm_bf16.hip (bf16 source,
+//        float or bf16 output: the same lanes load VEC bf16 in VEC/2 dwords, widen them exactly, and the same tree sums them)
 // FB     deepest load batch of the wave-per-segment walk inside the SHORT kernels (their fallback) and the LISTS kernels
 //        (medium / long walks): 4 keeps them at 7-8 waves per SIMD (memory-resident operands dominated by short segments:
 //        occupancy buys bandwidth), 8 otherwise (cache-resident operands / launches dominated by longer segments)
-template <int VEC, int LPR, bool EXACT, bool SUM, bool OFF32, bool PIPE = false, bool SHORT = false, bool EPI = false, int FB = 8, bool LISTS = false>
-__global__ __launch_bounds__(kBlock, EXACT ? (LISTS ? (FB == 4 ? H2GCN_SHORT_FB4_MIN_WAVES : heavy_registers<VEC, LPR, SUM, OFF32, PIPE, true, EPI>() ? H2GCN_OFF64_HEAVY_MIN_WAVES : (LPR >= 32 ? H2GCN_WIDE_MIN_WAVES : kMinWavesPerSimd))
+template <int VEC, int LPR, bool EXACT, bool SUM, bool OFF32, bool PIPE = false, bool SHORT = false, bool EPI = false, int FB = 8, bool LISTS = false,
+          typename TS = float, typename TD = float>
+__global__ __launch_bounds__(kBlock, (EXACT ? (LISTS ? (FB == 4 ? H2GCN_SHORT_FB4_MIN_WAVES : heavy_registers<VEC, LPR, SUM, OFF32, PIPE, true, EPI>() ? H2GCN_OFF64_HEAVY_MIN_WAVES : (LPR >= 32 ? H2GCN_WIDE_MIN_WAVES : kMinWavesPerSimd))
                                                 : SHORT ? (FB == 4 && !SUM ? H2GCN_SHORT_FB4_MIN_WAVES : H2GCN_SHORT_MIN_WAVES)
                                                 : heavy_registers<VEC, LPR, SUM, OFF32, PIPE, false, EPI>() ? H2GCN_OFF64_HEAVY_MIN_WAVES
-                                                : (LPR >= 32 ? H2GCN_WIDE_MIN_WAVES : kMinWavesPerSimd)) : 2) void spmm_hops_kernel(const LaunchParams p) {
+                                                : (LPR >= 32 ? H2GCN_WIDE_MIN_WAVES : kMinWavesPerSimd)) : 2)
+                                     - (bf16_one_wave_less<TS, VEC, LPR, SUM, OFF32, PIPE, SHORT, EPI, FB, LISTS>() ? 1 : 0)) void spmm_hops_kernel(const LaunchParams p) {
     static_assert(!LISTS || (EXACT && !SHORT && !PIPE && (LPR == 16 || LPR == 32)), "list-driven launches exist for 64- and 128-column slices");
     static_assert(EXACT || LPR == kWave, "column-tiled path uses the whole wave per row");
     __shared__ float partial[kWavesPerBlock][kMaxTileCols];
@@ -943,7 +1045,7 @@ __global__ __launch_bounds__(kBlock, EXACT ? (LISTS ? (FB == 4 ? H2GCN_SHORT_FB4
     const int ecol = EXACT ? ((lcol + VEC <= p.d_src) ? lcol : p.d_src - VEC) : lcol;
     // byte offset of ecol inside the slice, biased by VEC elements so that it is never negative (the tail of a slice that
     // holds fewer than VEC columns reaches back into the previous slice); the wave-uniform base is lowered accordingly
-    const off_t lane_off0 = (off_t)((ecol - col_begin + VEC) * 4);
+    const off_t lane_off0 = (off_t)((ecol - col_begin + VEC) * (int)sizeof(TS));
     constexpr int kBias = EXACT ? VEC : 0;
 
     if (b < p.n_long) {
@@ -959,9 +1061,9 @@ __global__ __launch_bounds__(kBlock, EXACT ? (LISTS ? (FB == 4 ? H2GCN_SHORT_FB4
             for (int s = s_first; s < s_last; ++s) {
                 const HopCsr& h = p.hop[s];
                 const int64_t sb = h.rowptr[row], se = h.rowptr[row + 1];
-                const GatherAddr<OFF32> addr{reinterpret_cast<const char*>(p.src + p.src_hop_off[s] + src_col_begin + (col0 - col_begin) - kBias),
-                                             EXACT ? lane_off0 : (off_t)(li * VEC * 4), (off_t)(p.ld_src * 4)};
-                accumulate_segment<VEC, LPR, !EXACT, OFF32, kMainB>(h.colidx, h.vals, sb, se, wave, kWavesPerBlock, addr, lane,
+                const GatherAddr<OFF32> addr{reinterpret_cast<const char*>(src_ptr<TS>(p.src) + p.src_hop_off[s] + src_col_begin + (col0 - col_begin) - kBias),
+                                             EXACT ? lane_off0 : (off_t)(li * VEC * (int)sizeof(TS)), (off_t)(p.ld_src * sizeof(TS))};
+                accumulate_segment<TS, VEC, LPR, !EXACT, OFF32, kMainB>(h.colidx, h.vals, sb, se, wave, kWavesPerBlock, addr, lane,
                                                             lane_active, acc);
             }
             float tot[VEC];
@@ -985,11 +1087,12 @@ __global__ __launch_bounds__(kBlock, EXACT ? (LISTS ? (FB == 4 ? H2GCN_SHORT_FB4
                 for (int w = 1; w < kWavesPerBlock; ++w) t += partial[w][c];
                 const int64_t off = row * p.ld_dst + (SUM ? 0 : p.dst_hop_off[s_first]) + col0 + c;
                 if constexpr (EPI) {
-                    if (p.accumulate) t += p.dst[off];
+                    if constexpr (std::is_same<TD, float>::value)
+                        if (p.accumulate) t += dst_ptr<float>(p.dst)[off];
                     if (p.bias) t += p.bias[col0 + c];
                     if (p.relu) t = fmaxf(t, 0.f);
                 }
-                __builtin_nontemporal_store(t, p.dst + off);
+                store_one<TD>(dst_ptr<TD>(p.dst) + off, t);
             }
             if (!EXACT) __syncthreads();
         }
@@ -1010,10 +1113,10 @@ __global__ __launch_bounds__(kBlock, EXACT ? (LISTS ? (FB == 4 ? H2GCN_SHORT_FB4
         const int64_t n_groups = p.short_groups + p.med_groups;
         const int64_t s_before = (q * p.short_groups) / n_groups;
         if (((q + 1) * p.short_groups) / n_groups > s_before)
-            short_list_blocks<VEC, LPR, SUM, OFF32, EPI, H2GCN_SHORT_PREFETCH>(p, s_before * kNumXcd + i8, lane, wave, (int64_t)lane_off0,
+            short_list_blocks<TS, TD, VEC, LPR, SUM, OFF32, EPI, H2GCN_SHORT_PREFETCH>(p, s_before * kNumXcd + i8, lane, wave, (int64_t)lane_off0,
                                                                                src_col_begin, lcol, ecol, s_seg, s_row);
         else
-            medium_list_blocks<VEC, LPR, SUM, OFF32, EPI, FB>(p, (q - s_before) * kNumXcd + i8, lane, wave, (int64_t)lane_off0,
+            medium_list_blocks<TS, TD, VEC, LPR, SUM, OFF32, EPI, FB>(p, (q - s_before) * kNumXcd + i8, lane, wave, (int64_t)lane_off0,
                                                               src_col_begin, lcol, ecol);
         return;
     } else {
@@ -1038,7 +1141,7 @@ __global__ __launch_bounds__(kBlock, EXACT ? (LISTS ? (FB == 4 ? H2GCN_SHORT_FB4
     };
 
     if constexpr (SHORT && EXACT && (kWave / LPR == 2 || kWave / LPR == 4)) {
-        in_tile_short_rows<VEC, LPR, SUM, OFF32, EPI, FB>(p, lane, rpw, row0, rows_here, rp_lo, rp_hi, (int64_t)lane_off0, src_col_begin, lcol, ecol);
+        in_tile_short_rows<TS, TD, VEC, LPR, SUM, OFF32, EPI, FB>(p, lane, rpw, row0, rows_here, rp_lo, rp_hi, (int64_t)lane_off0, src_col_begin, lcol, ecol);
         return;
     }
     if constexpr (PIPE && EXACT) {
@@ -1075,15 +1178,15 @@ __global__ __launch_bounds__(kBlock, EXACT ? (LISTS ? (FB == 4 ? H2GCN_SHORT_FB4
             const int r = q / n_sel;
             const int64_t row = row0 + r;
             const HopCsr& h = p.hop[s_cur];
-            const GatherAddr<OFF32> addr{reinterpret_cast<const char*>(p.src + p.src_hop_off[s_cur] + src_col_begin - kBias),
-                                         lane_off0, (off_t)(p.ld_src * 4)};
-            accumulate_segment_prefetched<VEC, LPR, OFF32>(h.colidx, h.vals, b_cur, e_cur, c_cur, v_cur, addr, lane, acc);
+            const GatherAddr<OFF32> addr{reinterpret_cast<const char*>(src_ptr<TS>(p.src) + p.src_hop_off[s_cur] + src_col_begin - kBias),
+                                         lane_off0, (off_t)(p.ld_src * sizeof(TS))};
+            accumulate_segment_prefetched<TS, VEC, LPR, OFF32>(h.colidx, h.vals, b_cur, e_cur, c_cur, v_cur, addr, lane, acc);
             const bool skipped = (skip >> q) & 1u;
             if (!SUM || s_cur == n_sel - 1) {
                 if (!skipped) {
                     float tot[VEC];
                     fold_tree<VEC, LPR, NP>(acc, tot);
-                    if (g == 0) store_out<VEC, EPI>(p, p.dst + row * p.ld_dst + (SUM ? 0 : p.dst_hop_off[s_cur]), lcol, ecol, tot);
+                    if (g == 0) store_out<TD, VEC, EPI>(p, dst_ptr<TD>(p.dst) + row * p.ld_dst + (SUM ? 0 : p.dst_hop_off[s_cur]), lcol, ecol, tot);
                 }
                 zero_acc<VEC, NP>(acc);
             }
@@ -1111,19 +1214,19 @@ __global__ __launch_bounds__(kBlock, EXACT ? (LISTS ? (FB == 4 ? H2GCN_SHORT_FB4
                 float v;
                 load_chunk(h.colidx, h.vals, sb, se, lane, c, v);
                 if (held_valid) {
-                    if (g == 0) store_out<VEC, EPI>(p, p.dst + held_off, lcol, ecol, held);
+                    if (g == 0) store_out<TD, VEC, EPI>(p, dst_ptr<TD>(p.dst) + held_off, lcol, ecol, held);
                     held_valid = false;
                 }
                 float acc[NP][VEC];
                 zero_acc<VEC, NP>(acc);
-                const GatherAddr<OFF32> addr{reinterpret_cast<const char*>(p.src + p.src_hop_off[s] + src_col_begin - kBias), lane_off0, (off_t)(p.ld_src * 4)};
-                accumulate_segment_prefetched<VEC, LPR, OFF32, kMainB>(h.colidx, h.vals, sb, se, c, v, addr, lane, acc);
+                const GatherAddr<OFF32> addr{reinterpret_cast<const char*>(src_ptr<TS>(p.src) + p.src_hop_off[s] + src_col_begin - kBias), lane_off0, (off_t)(p.ld_src * sizeof(TS))};
+                accumulate_segment_prefetched<TS, VEC, LPR, OFF32, kMainB>(h.colidx, h.vals, sb, se, c, v, addr, lane, acc);
                 fold_tree<VEC, LPR, NP>(acc, held);
                 held_off = row * p.ld_dst + p.dst_hop_off[s];
                 held_valid = true;
             }
         }
-        if (held_valid && g == 0) store_out<VEC, EPI>(p, p.dst + held_off, lcol, ecol, held);
+        if (held_valid && g == 0) store_out<TD, VEC, EPI>(p, dst_ptr<TD>(p.dst) + held_off, lcol, ecol, held);
         return;
     }
 #endif
@@ -1152,9 +1255,9 @@ __global__ __launch_bounds__(kBlock, EXACT ? (LISTS ? (FB == 4 ? H2GCN_SHORT_FB4
                 const int64_t sb = seg_bound(l0), se = seg_bound(l0 + 1);
                 if (!SUM && se - sb >= p.long_threshold) continue;  // a workgroup of the long path owns it
                 const HopCsr& h = p.hop[s];
-                const GatherAddr<OFF32> addr{reinterpret_cast<const char*>(p.src + p.src_hop_off[s] + src_col_begin + (col0 - col_begin) - kBias),
-                                             EXACT ? lane_off0 : (off_t)(li * VEC * 4), (off_t)(p.ld_src * 4)};
-                accumulate_segment<VEC, LPR, !EXACT, OFF32, kMainB>(h.colidx, h.vals, sb, se, 0, 1, addr, lane, lane_active, acc);
+                const GatherAddr<OFF32> addr{reinterpret_cast<const char*>(src_ptr<TS>(p.src) + p.src_hop_off[s] + src_col_begin + (col0 - col_begin) - kBias),
+                                             EXACT ? lane_off0 : (off_t)(li * VEC * (int)sizeof(TS)), (off_t)(p.ld_src * sizeof(TS))};
+                accumulate_segment<TS, VEC, LPR, !EXACT, OFF32, kMainB>(h.colidx, h.vals, sb, se, 0, 1, addr, lane, lane_active, acc);
                 if constexpr (!SUM) {
                     float tot[VEC];
                     fold_tree<VEC, LPR, NP>(acc, tot);
@@ -1165,14 +1268,14 @@ __global__ __launch_bounds__(kBlock, EXACT ? (LISTS ? (FB == 4 ? H2GCN_SHORT_FB4
                         held_s = 0;
                     } else {
                         if (held_s >= 0 && g == 0 && lane_active)
-                            store_out<VEC, EPI>(p, p.dst + row * p.ld_dst + p.dst_hop_off[held_s], lcol, ecol, held);
+                            store_out<TD, VEC, EPI>(p, dst_ptr<TD>(p.dst) + row * p.ld_dst + p.dst_hop_off[held_s], lcol, ecol, held);
                         held_s = -1;
                         if (g == 0 && lane_active)
-                            store_out<VEC, EPI>(p, p.dst + row * p.ld_dst + p.dst_hop_off[s], EXACT ? lcol : col0 + li * VEC, EXACT ? ecol : col0 + li * VEC, tot);
+                            store_out<TD, VEC, EPI>(p, dst_ptr<TD>(p.dst) + row * p.ld_dst + p.dst_hop_off[s], EXACT ? lcol : col0 + li * VEC, EXACT ? ecol : col0 + li * VEC, tot);
                     }
 #else
                     if (g == 0 && lane_active)
-                        store_out<VEC, EPI>(p, p.dst + row * p.ld_dst + p.dst_hop_off[s], EXACT ? lcol : col0 + li * VEC, EXACT ? ecol : col0 + li * VEC, tot);
+                        store_out<TD, VEC, EPI>(p, dst_ptr<TD>(p.dst) + row * p.ld_dst + p.dst_hop_off[s], EXACT ? lcol : col0 + li * VEC, EXACT ? ecol : col0 + li * VEC, tot);
 #endif
                     zero_acc<VEC, NP>(acc);
                 }
@@ -1180,13 +1283,13 @@ __global__ __launch_bounds__(kBlock, EXACT ? (LISTS ? (FB == 4 ? H2GCN_SHORT_FB4
 #ifdef H2GCN_DEFER_HOP_STORES
             if constexpr (!SUM)
                 if (held_s >= 0 && g == 0 && lane_active)
-                    store_out<VEC, EPI>(p, p.dst + row * p.ld_dst + p.dst_hop_off[held_s], lcol, ecol, held);
+                    store_out<TD, VEC, EPI>(p, dst_ptr<TD>(p.dst) + row * p.ld_dst + p.dst_hop_off[held_s], lcol, ecol, held);
 #endif
             if constexpr (SUM) {
                 float tot[VEC];
                 fold_tree<VEC, LPR, NP>(acc, tot);
                 if (g == 0 && lane_active)
-                    store_out<VEC, EPI>(p, p.dst + row * p.ld_dst, EXACT ? lcol : col0 + li * VEC, EXACT ? ecol : col0 + li * VEC, tot);
+                    store_out<TD, VEC, EPI>(p, dst_ptr<TD>(p.dst) + row * p.ld_dst, EXACT ? lcol : col0 + li * VEC, EXACT ? ecol : col0 + li * VEC, tot);
             }
         }
     }
@@ -1232,6 +1335,78 @@ __global__ void repack_slice_major_kernel(const float* __restrict__ x, int64_t l
             __builtin_nontemporal_store(col < d ? *src : 0.f, w + i);
         }
     }
+}
+
+// Which instantiation a launch runs (decided on the host: h2gcn_capi.hip, decide()).
+struct KernelChoice {
+    bool scalar128, lists, shortrow, pipe, gen, off32, fb4;
+    int slice;  // 256 / 128 / 64 columns; 0: generic column-tiled kernel (d < 4)
+};
+
+// The in-tile short-row kernels of one (SUM, slice, source / output type).  Instantiated in translation units of their own
+// (spmm_short.hip for fp32, spmm_bf16.hip for bf16): see spmm_short.hip.
+template <bool SUM, int LPR, typename TS, typename TD>
+void launch_in_tile_short_kernels(const LaunchParams& p, bool off32, bool fb4, dim3 grid, hipStream_t stream) {
+    const dim3 block(kBlock);
+    if (off32 && fb4)
+        hipLaunchKernelGGL((spmm_hops_kernel<4, LPR, true, SUM, true, false, true, false, 4, false, TS, TD>), grid, block, 0, stream, p);
+    else if (off32)
+        hipLaunchKernelGGL((spmm_hops_kernel<4, LPR, true, SUM, true, false, true, false, 8, false, TS, TD>), grid, block, 0, stream, p);
+    else if (fb4)
+        hipLaunchKernelGGL((spmm_hops_kernel<4, LPR, true, SUM, false, false, true, false, 4, false, TS, TD>), grid, block, 0, stream, p);
+    else
+        hipLaunchKernelGGL((spmm_hops_kernel<4, LPR, true, SUM, false, false, true, false, 8, false, TS, TD>), grid, block, 0, stream, p);
+}
+
+// Every other launch (tile walk, list-driven walks, long segments, column-tiled kernel) of one (SUM, source / output type); the
+// caller routes in-tile short-row launches (k.shortrow) to launch_in_tile_short_kernels and checks hipGetLastError.
+template <bool SUM, typename TS, typename TD>
+void launch_spmm_kernels(const LaunchParams& p, const KernelChoice& k, dim3 grid, hipStream_t stream) {
+    const dim3 block(kBlock);
+    const bool gen = k.gen, off32 = k.off32, pipe = k.pipe, short_fb4 = k.fb4;
+#define H2GCN_LAUNCH_LISTS(VEC, LPR)                                                                                              \
+    do {                                                                                                                          \
+        if (off32 && short_fb4)                                                                                                   \
+            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, true, SUM, true, false, false, false, 4, true, TS, TD>), grid, block, 0, stream, p);   \
+        else if (off32)                                                                                                           \
+            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, true, SUM, true, false, false, false, 8, true, TS, TD>), grid, block, 0, stream, p);   \
+        else if (short_fb4)                                                                                                       \
+            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, true, SUM, false, false, false, false, 4, true, TS, TD>), grid, block, 0, stream, p);  \
+        else                                                                                                                      \
+            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, true, SUM, false, false, false, false, 8, true, TS, TD>), grid, block, 0, stream, p);  \
+    } while (0)
+#define H2GCN_LAUNCH(VEC, LPR, EXACT)                                                                             \
+    do {                                                                                                          \
+        if (gen && off32)                                                                                         \
+            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, EXACT, SUM, true, false, false, true, 8, false, TS, TD>), grid, block, 0, stream, p);  \
+        else if (gen)                                                                                             \
+            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, EXACT, SUM, false, false, false, true, 8, false, TS, TD>), grid, block, 0, stream, p); \
+        else if (off32 && pipe && EXACT)                                                                               \
+            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, EXACT, SUM, true, true, false, false, 8, false, TS, TD>), grid, block, 0, stream, p);   \
+        else if (off32)                                                                                           \
+            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, EXACT, SUM, true, false, false, false, 8, false, TS, TD>), grid, block, 0, stream, p);  \
+        else if (pipe && EXACT)                                                                                   \
+            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, EXACT, SUM, false, true, false, false, 8, false, TS, TD>), grid, block, 0, stream, p);  \
+        else                                                                                                      \
+            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, EXACT, SUM, false, false, false, false, 8, false, TS, TD>), grid, block, 0, stream, p); \
+    } while (0)
+    if (k.scalar128) {
+        H2GCN_LAUNCH(2, 64, true);  // one neighbour per load instruction, scalar base addressing
+    } else if (k.slice == 256) {
+        H2GCN_LAUNCH(4, 64, true);
+    } else if (k.slice == 128 && k.lists) {
+        H2GCN_LAUNCH_LISTS(4, 32);
+    } else if (k.slice == 64 && k.lists) {
+        H2GCN_LAUNCH_LISTS(4, 16);
+    } else if (k.slice == 128) {
+        H2GCN_LAUNCH(4, 32, true);
+    } else if (k.slice == 64) {
+        H2GCN_LAUNCH(4, 16, true);
+    } else {
+        H2GCN_LAUNCH(1, 64, false);  // d < 4: generic column-tiled path
+    }
+#undef H2GCN_LAUNCH
+#undef H2GCN_LAUNCH_LISTS
 }
 
 }  // namespace h2gcn

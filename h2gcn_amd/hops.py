@@ -23,11 +23,27 @@ def _require(cond: bool, msg: str) -> None:
         raise ValueError(msg)
 
 
+def _bf16_layout(name: str, t: torch.Tensor, d: int, strides) -> None:
+    """The C ABI's rule for bf16 arrays: 4-byte aligned base, even strides (elements), even width."""
+    _require(d % 2 == 0, f"bf16 {name}: the feature width d must be even (got {d})")
+    _require(t.data_ptr() % 4 == 0, f"bf16 {name}: the base address must be 4-byte aligned")
+    for st in strides:
+        _require(st % 2 == 0, f"bf16 {name}: row / hop strides must be even (got {tuple(strides)} elements)")
+
+
+def _bf16_symbols() -> None:
+    _require(_capi.has("h2gcn_spmm_hops_bf16"), f"{_capi.library_path()} predates the bf16 launches (ABI 5)")
+
+
 class HopPlan:
     """H hop matrices sharing one row space, resident on one GPU.
 
     Results are bit-reproducible functions of the operands: every launch builds the library's canonical per-row
     summation tree (``include/h2gcn_hip.h``), whatever slice width, scratch copy or segment walk the schedule picks.
+
+    Embeddings / gradients may be float32 or bfloat16 (the gathered operand; adjacency values stay float32).  A bfloat16
+    operand is widened exactly and summed in fp32 in the same tree: an fp32 result equals the launch on ``x.float()`` bit for
+    bit, a bfloat16 result is that value ``.to(torch.bfloat16)``.  bfloat16 needs an even width and even strides.
 
     Parameters
     ----------
@@ -190,31 +206,61 @@ class HopPlan:
 
     # ------------------------------------------------------------------ launches
     def spmm(self, x: torch.Tensor, hops=None, out: Optional[torch.Tensor] = None, bias: Optional[torch.Tensor] = None,
-             relu: bool = False) -> torch.Tensor:
+             relu: bool = False, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
         """``out[i, s, :] = act(sum_j A_s[i, j] * x[j, :] + bias)`` for the selected hops -> ``[n_rows, H_sel, d]``
         (``bias`` [d] and ``relu`` are the optional fused epilogue of the store; default: the plain sum).
 
-        ``out`` may be any fp32 tensor view of shape ``[n_rows, H_sel, d]`` whose last dim is contiguous
+        ``x``: float32 or bfloat16.  The result's dtype is ``out.dtype``, else ``out_dtype``, else ``x.dtype``: float32 ->
+        float32, bfloat16 -> float32 or bfloat16 (see the class docstring; float32 -> bfloat16 does not exist).  ``bias`` is
+        float32 and the epilogue runs before the rounding to bfloat16.
+        ``out`` may be any tensor view of shape ``[n_rows, H_sel, d]`` whose last dim is contiguous
         (e.g. a column slice of a wider concat buffer)."""
         _require(x.dim() == 2, f"inputs must be [n_cols, d], got shape {tuple(x.shape)}")
-        _require(x.dtype == torch.float32, f"inputs must be float32, got {x.dtype}")
+        _require(x.dtype in (torch.float32, torch.bfloat16), f"inputs must be float32 or bfloat16, got {x.dtype}")
         _require(x.device == self.device, f"inputs on {x.device}, plan on {self.device}")
         _require(x.shape[0] == self.n_cols, f"inputs have {x.shape[0]} rows, hop matrices have {self.n_cols} columns")
         d = int(x.shape[1])
         _require(d >= 1, "inputs need at least one column")
+        bf16 = x.dtype == torch.bfloat16
+        if out_dtype is None:
+            out_dtype = out.dtype if out is not None else x.dtype
+        _require(out_dtype in (torch.float32, torch.bfloat16), f"outputs must be float32 or bfloat16, got {out_dtype}")
+        _require(bf16 or out_dtype == torch.float32, "float32 inputs give float32 outputs (float32 -> bfloat16 is not supported)")
         if x.stride(1) != 1:
             x = x.contiguous()
         h_sel = self.n_selected(hops)
         if out is None:
-            out = torch.empty((self.n_rows, h_sel, d), dtype=torch.float32, device=self.device)
+            out = torch.empty((self.n_rows, h_sel, d), dtype=out_dtype, device=self.device)
         else:
-            _require(out.dtype == torch.float32 and out.device == self.device, "out must be float32 on the plan's device")
+            _require(out.dtype == out_dtype and out.device == self.device, f"out must be {out_dtype} on the plan's device")
             _require(tuple(out.shape) == (self.n_rows, h_sel, d), f"out has shape {tuple(out.shape)}, expected {(self.n_rows, h_sel, d)}")
             _require(d == 1 or out.stride(2) == 1, "out's last dimension must be contiguous")
+        if bf16:
+            _bf16_symbols()
+            _bf16_layout("inputs", x, d, (x.stride(0),))
+            if out_dtype == torch.bfloat16:
+                _bf16_layout("out", out, d, (out.stride(0), out.stride(1) if h_sel > 1 else d))
         if self.n_rows == 0:
             return out
         L = _capi.lib()
         mask = self._mask(hops)
+        if bf16:
+            # bf16 launches gather in place (no slice-major scratch copy)
+            with torch.cuda.device(self.device):
+                stream = torch.cuda.current_stream(self.device).cuda_stream
+                opts = None
+                if bias is not None or relu:
+                    if bias is not None:
+                        _require(bias.dtype == torch.float32 and bias.device == self.device and bias.numel() == d and bias.is_contiguous(),
+                                 f"bias must be a contiguous float32 [{d}] tensor on the plan's device")
+                    opts = _capi.LaunchOpts(struct_size=C.sizeof(_capi.LaunchOpts), flags=_capi.LAUNCH_RELU if relu else 0,
+                                            workspace=None, workspace_bytes=0, bias=bias.data_ptr() if bias is not None else None)
+                y_dtype = _capi.DTYPE_BF16 if out_dtype == torch.bfloat16 else _capi.DTYPE_F32
+                st = L.h2gcn_spmm_hops_bf16(self._handle, mask, C.c_void_p(x.data_ptr()), x.stride(0), d, y_dtype,
+                                            C.c_void_p(out.data_ptr()), out.stride(0), out.stride(1) if h_sel > 1 else d,
+                                            C.byref(opts) if opts is not None else None, C.c_void_p(stream))
+            _capi.check(st)
+            return out
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
             # scratch for the slice-major copy of X the library wants when X's row stride is a multiple of 1 KiB, when
@@ -236,29 +282,57 @@ class HopPlan:
         _capi.check(st)
         return out
 
-    def spmm_t(self, grad: torch.Tensor, hops=None, out: torch.Tensor = None, accumulate: bool = False) -> torch.Tensor:
+    def spmm_t(self, grad: torch.Tensor, hops=None, out: torch.Tensor = None, accumulate: bool = False,
+               out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
         """Adjoint: ``dx[j, :] = sum_s sum_i A_s[i, j] * grad[i, s, :]`` -> ``[n_cols, d]``.  ``out``: write into this
         ``[n_cols, d]`` tensor (unit column stride, any row stride) instead of a new one; ``accumulate=True`` ADDS the
-        result to what ``out`` holds (``H2GCN_LAUNCH_ACCUMULATE``: the `+=` of a gradient slot fused into the store)."""
+        result to what ``out`` holds (``H2GCN_LAUNCH_ACCUMULATE``: the `+=` of a gradient slot fused into the store).
+        ``grad``: float32 or bfloat16; the dtype of ``dx`` is ``out.dtype``, else ``out_dtype``, else ``grad.dtype`` (as in
+        :meth:`spmm`).  ``accumulate=True`` needs a float32 ``out``."""
         _require(self.has_transpose, "plan was built without build_transpose=True; backward is unavailable")
         h_sel = self.n_selected(hops)
         _require(grad.dim() == 3 and grad.shape[0] == self.n_rows and grad.shape[1] == h_sel,
                  f"grad must be [{self.n_rows}, {h_sel}, d], got {tuple(grad.shape)}")
-        _require(grad.dtype == torch.float32 and grad.device == self.device, "grad must be float32 on the plan's device")
+        _require(grad.dtype in (torch.float32, torch.bfloat16) and grad.device == self.device,
+                 "grad must be float32 or bfloat16 on the plan's device")
         d = int(grad.shape[2])
+        bf16 = grad.dtype == torch.bfloat16
+        if out_dtype is None:
+            out_dtype = out.dtype if out is not None else grad.dtype
+        _require(out_dtype in (torch.float32, torch.bfloat16), f"dx must be float32 or bfloat16, got {out_dtype}")
+        _require(bf16 or out_dtype == torch.float32, "a float32 grad gives a float32 dx (float32 -> bfloat16 is not supported)")
+        _require(not (accumulate and out_dtype == torch.bfloat16), "accumulate=True needs a float32 out (a bfloat16 dx cannot be accumulated into)")
         if grad.stride(2) != 1 or grad.stride(0) < d or (h_sel > 1 and grad.stride(1) < d):
             grad = grad.contiguous()  # e.g. an expanded (stride-0) gradient coming out of a reduction
         if out is None:
             _require(not accumulate, "accumulate=True needs the tensor to accumulate into (out=)")
-            dx = torch.empty((self.n_cols, d), dtype=torch.float32, device=self.device)
+            dx = torch.empty((self.n_cols, d), dtype=out_dtype, device=self.device)
         else:
-            _require(out.shape == (self.n_cols, d) and out.dtype == torch.float32 and out.device == self.device
+            _require(out.shape == (self.n_cols, d) and out.dtype == out_dtype and out.device == self.device
                      and (out.stride(1) == 1 or d == 1) and (out.stride(0) >= d or self.n_cols <= 1),
-                     f"out must be float32 [{self.n_cols}, {d}] on the plan's device with unit column stride")
+                     f"out must be {out_dtype} [{self.n_cols}, {d}] on the plan's device with unit column stride")
             dx = out
+        if bf16:
+            _bf16_symbols()
+            _bf16_layout("grad", grad, d, (grad.stride(0) if self.n_rows > 0 else h_sel * d, grad.stride(1) if h_sel > 1 else d))
+            if out_dtype == torch.bfloat16:
+                _bf16_layout("dx", dx, d, (dx.stride(0) if self.n_cols > 1 else d,))
         if self.n_cols == 0:
             return dx
         L = _capi.lib()
+        if bf16:
+            # bf16 launches gather in place (no slice-major scratch copy)
+            with torch.cuda.device(self.device):
+                stream = torch.cuda.current_stream(self.device).cuda_stream
+                ld_row, ld_hop = (grad.stride(0) if self.n_rows > 0 else h_sel * d), (grad.stride(1) if h_sel > 1 else d)
+                opts = (_capi.LaunchOpts(struct_size=C.sizeof(_capi.LaunchOpts), flags=_capi.LAUNCH_ACCUMULATE, workspace=None,
+                                         workspace_bytes=0, bias=None) if accumulate else None)
+                dx_dtype = _capi.DTYPE_BF16 if out_dtype == torch.bfloat16 else _capi.DTYPE_F32
+                st = L.h2gcn_spmm_hops_T_bf16(self._handle, self._mask(hops), C.c_void_p(grad.data_ptr()), ld_row, ld_hop, d,
+                                              dx_dtype, C.c_void_p(dx.data_ptr()), dx.stride(0) if self.n_cols > 1 else d,
+                                              C.byref(opts) if opts is not None else None, C.c_void_p(stream))
+            _capi.check(st)
+            return dx
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
             mask = self._mask(hops)

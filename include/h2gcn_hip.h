@@ -38,7 +38,7 @@
 extern "C" {
 #endif
 
-#define H2GCN_ABI_VERSION 4
+#define H2GCN_ABI_VERSION 5
 #define H2GCN_MAX_HOPS 8
 
 typedef enum h2gcn_status {
@@ -268,6 +268,46 @@ int h2gcn_spmm_hops_T_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const flo
 int h2gcn_spmm_hops_T_opts_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* dY_dev, int64_t ldg_row,
                                int64_t ldg_hop, int32_t d, float* dX_dev, int64_t ldx,
                                const h2gcn_launch_opts* opts, void* stream);
+
+/*
+ * bf16 embeddings (ABI 5).  The same two launches with the GATHER SOURCE in bf16 -- X for the forward, dY for the adjoint --
+ * and an fp32 or a bf16 output.  Adjacency values stay fp32 and the plan is the same: one plan serves fp32 and bf16 launches.
+ * At d = 128 the gathered feature row is 256 B instead of 512 B per aggregated edge, so the dominant stream of a launch
+ * roughly halves.  The suffix names the source dtype, as _f32 does.  Strides are in ELEMENTS.
+ *
+ *   y_dtype / dx_dtype   H2GCN_DTYPE_F32 or H2GCN_DTYPE_BF16 (any other value: H2GCN_ERR_INVALID_ARGUMENT)
+ *
+ * Arithmetic: every gathered bf16 element is widened exactly to fp32 (bf16 -> fp32 is exact), then multiplied and added in
+ * fp32 in the canonical summation tree above.  An fp32 output is therefore BIT-IDENTICAL to the fp32 launch on the upcast
+ * source (X.float()), for every segment walk, slice width, hop selection, feature chunking, row block, rows_per_wave and
+ * long_row_threshold.  A bf16 output is the round-to-nearest-even of exactly that fp32 value (torch's .to(torch.bfloat16),
+ * ties and overflow to inf included).  The forward's bias / H2GCN_LAUNCH_RELU epilogue runs on the fp32 value, before the
+ * rounding; bias stays fp32.
+ * Accuracy against the fp32 launch on an fp32 source x: with fp32 output, |Y(bf16(x)) - Y(x)| <= 2^-7 * sum_j |a_j| |x_j|
+ * element-wise -- rounding x to bf16 contributes at most 2^-8 (the unit roundoff of an 8-bit significand) relative to each
+ * term, and the two fp32 trees add a few fp32 ulps.
+ *
+ * Supported: bf16 -> fp32 and bf16 -> bf16, forward and adjoint (fp32 -> fp32 is the _f32 entry points; fp32 -> bf16 does not
+ * exist).  H2GCN_LAUNCH_ACCUMULATE is accepted with an fp32 dX only (old + sum, as for the fp32 adjoint); with a bf16 dX it is
+ * H2GCN_ERR_INVALID_ARGUMENT.
+ * Alignment: every bf16 array needs a 4-byte aligned base, even row and hop strides and an even d (d = 2 included), so that
+ * every lane's 8- / 4-byte load and store is dword-aligned; anything else is H2GCN_ERR_INVALID_ARGUMENT, with a message that
+ * names the rule.  (The bf16 widths of H2GCN -- 64, 128, 256 and their concat slices -- are all even.)
+ * Scratch: a bf16 launch never uses the slice-major scratch copy; opts->workspace_dev / workspace_bytes are ignored, and
+ * h2gcn_spmm_workspace_bytes keeps describing fp32 launches.
+ * Schedule: a bf16 launch takes the fp32 schedule for the same d and element strides -- h2gcn_plan_schedule and
+ * h2gcn_plan_segment_classes describe it, except that it gathers in place where they report a scratch copy.
+ * Offsets: whether the 32-bit gather offsets apply is decided in bytes of the real element size, so a bf16 source beyond 4 GiB
+ * takes the 64-bit kernels.
+ * hipGraph capture: the same condition as the fp32 launches (one eager launch per hop selection and width first).  Arguments
+ * are validated before the device is touched.
+ */
+#define H2GCN_DTYPE_F32 0
+#define H2GCN_DTYPE_BF16 1
+int h2gcn_spmm_hops_bf16(const h2gcn_plan_t* plan, uint32_t hop_mask, const uint16_t* X_dev, int64_t ldx, int32_t d,
+                         int y_dtype, void* Y_dev, int64_t ldy_row, int64_t ldy_hop, const h2gcn_launch_opts* opts, void* stream);
+int h2gcn_spmm_hops_T_bf16(const h2gcn_plan_t* plan, uint32_t hop_mask, const uint16_t* dY_dev, int64_t ldg_row, int64_t ldg_hop,
+                           int32_t d, int dx_dtype, void* dX_dev, int64_t ldx, const h2gcn_launch_opts* opts, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Operand construction on the device: exact-k-hop neighbourhood rings and their normalisation -- the step that

@@ -9,6 +9,15 @@ Every library is dlopen'ed into THIS process (its own ctypes handle, its own pla
 operands at the SAME addresses: one synthetic graph per shape (h2gcn_amd/synth.py, generated once), one X, one dY, one Y /
 dX.  Per round the libraries take turns (A B C, A B C, ...), forward then adjoint, 2 warm-up + `launches` timed launches
 each, HIP events on the launch stream; the figure per (library, round) is the MEDIAN launch.  Micro-benchmark, not product.
+
+--dtypes f32 bf16_f32 bf16_bf16 adds the element-type axis (ABI 5): the same operands with X / dY in bf16 and an fp32 or bf16
+output, every (library, dtype) taking turns.  X and dY are then rounded to bf16 once and the fp32 launches run on the upcast
+copies, so every bf16 -> fp32 output must carry the fp32 checksum and every bf16 -> bf16 output that of the fp32 output rounded
+to bf16 (printed per configuration).  Rates are quoted on each configuration's own algorithmic bytes (alg_bytes: 2-byte
+elements where the operand is bf16) and as aggregated edges / s.  Libraries without the bf16 entry points run f32 only.
+
+    tools/ab_dram_regimes.py --libs new=h2gcn_amd/csrc/libh2gcn_hip.so --shapes products arxiv products_x6 lowdeg \
+        --dtypes f32 bf16_f32 bf16_bf16 --rounds 5 --launches 10
 """
 import argparse
 import ctypes as C
@@ -26,6 +35,16 @@ from h2gcn_amd import synth  # noqa: E402
 from h2gcn_amd._capi import LaunchOpts, PlanOpts  # noqa: E402  (struct layouts only; no library is loaded through _capi)
 
 PLAN_BUILD_TRANSPOSE = 0x1
+DTYPE_F32, DTYPE_BF16 = 0, 1
+#: --dtypes: (bytes per gathered element, bytes per output element, output dtype code of the bf16 entry points)
+DTYPES = {"f32": (4, 4, None), "bf16_f32": (2, 4, DTYPE_F32), "bf16_bf16": (2, 2, DTYPE_BF16)}
+
+
+def alg_bytes(nnz, n, d, h_out, src_bytes=4, out_bytes=4):
+    """Algorithmic bytes of one launch: per nonzero its 8 B of column id + value and one gathered feature row of d elements
+    (src_bytes each: 4 for fp32, 2 for bf16), the row pointers of every hop, one write of the n x h_out x d output (out_bytes
+    per element)."""
+    return sum(z * (8 + src_bytes * d) + (n + 1) * 8 for z in nnz) + n * h_out * d * out_bytes
 
 
 class Lib:
@@ -46,6 +65,14 @@ class Lib:
                                                C.POINTER(LaunchOpts), C.c_void_p]
         L.h2gcn_spmm_hops_T_opts_f32.restype = C.c_int
         L.h2gcn_spmm_hops_T_opts_f32.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int64,
+                                                 C.POINTER(LaunchOpts), C.c_void_p]
+        self.has_bf16 = hasattr(L, "h2gcn_spmm_hops_bf16")
+        if self.has_bf16:
+            L.h2gcn_spmm_hops_bf16.restype = C.c_int
+            L.h2gcn_spmm_hops_bf16.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_int64, C.c_int64,
+                                               C.POINTER(LaunchOpts), C.c_void_p]
+            L.h2gcn_spmm_hops_T_bf16.restype = C.c_int
+            L.h2gcn_spmm_hops_T_bf16.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_int, C.c_void_p, C.c_int64,
                                                  C.POINTER(LaunchOpts), C.c_void_p]
         self.abi = L.h2gcn_abi_version()
         self.plan = C.c_void_p()
@@ -94,6 +121,16 @@ class Lib:
         self.check(self.L.h2gcn_spmm_hops_T_opts_f32(self.plan, mask, C.c_void_p(dy.data_ptr()), dy.stride(0), dy.stride(1), d, C.c_void_p(dx.data_ptr()),
                                                      dx.stride(0), C.byref(o) if o is not None else None,
                                                      C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+
+
+    def forward_bf16(self, xb, y, y_dtype, mask=0):
+        """bf16 X (no scratch copy: bf16 launches gather in place), y fp32 or bf16 per y_dtype"""
+        self.check(self.L.h2gcn_spmm_hops_bf16(self.plan, mask, C.c_void_p(xb.data_ptr()), xb.stride(0), xb.shape[1], y_dtype, C.c_void_p(y.data_ptr()),
+                                               y.stride(0), y.stride(1), None, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+
+    def adjoint_bf16(self, dyb, dx, dx_dtype, mask=0):
+        self.check(self.L.h2gcn_spmm_hops_T_bf16(self.plan, mask, C.c_void_p(dyb.data_ptr()), dyb.stride(0), dyb.stride(1), dyb.shape[2], dx_dtype,
+                                                 C.c_void_p(dx.data_ptr()), dx.stride(0), None, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
 
 
 def timed(fn, warm, launches):
@@ -233,6 +270,8 @@ def main():
     ap.add_argument("--transposed", action="store_true", help="--matrix: also run forward / adjoint on the transposed hop matrices")
     ap.add_argument("--lite", action="store_true", help="--matrix without the plan-option configurations (builds only)")
     ap.add_argument("--matrix", action="store_true", help="forward-vs-adjoint matrix on the first of --shapes (see forward_vs_adjoint)")
+    ap.add_argument("--dtypes", nargs="+", default=["f32"], choices=list(DTYPES),
+                    help="element types of the gather source -> output, taking turns with the libraries (see the module docstring)")
     a = ap.parse_args()
     if a.matrix:
         return forward_vs_adjoint(a)
@@ -251,46 +290,81 @@ def main():
         csr = [synth.synth_hop_rows(degs[k], n, seeds[k], 0, n, dev) for k in range(2)]
         x = synth.synth_features(d, synth.SEED_X, 0, n, dev)
         dy = synth.synth_features(2 * d, 77, 0, n, dev).view(n, 2, d)
-        y = torch.empty((n, 2, d), dtype=torch.float32, device=dev)
-        dx = torch.empty((n, d), dtype=torch.float32, device=dev)
+        bf16 = any(dt != "f32" for dt in a.dtypes)
+        xb = dyb = None
+        if bf16:
+            # round once; the fp32 launches run on the upcast copies, so the bf16 -> fp32 outputs must carry their checksums
+            xb, dyb = x.to(torch.bfloat16), dy.to(torch.bfloat16)
+            x, dy = xb.float(), dyb.float()
+        out = {"f32": (torch.empty((n, 2, d), dtype=torch.float32, device=dev), torch.empty((n, d), dtype=torch.float32, device=dev))}
+        if "bf16_bf16" in a.dtypes:
+            out["bf16"] = (torch.empty((n, 2, d), dtype=torch.bfloat16, device=dev), torch.empty((n, d), dtype=torch.bfloat16, device=dev))
         nnz = [int(c[0][-1]) for c in csr]
-        b_fwd = sum(z * (8 + 4 * d) + (n + 1) * 8 for z in nnz) + n * 2 * d * 4
-        b_adj = sum(z * (8 + 4 * d) + (n + 1) * 8 for z in nnz) + n * d * 4
+        edges = sum(nnz)   # aggregated edges per launch (forward and adjoint)
+        nbytes = {dt: (alg_bytes(nnz, n, d, 2, *DTYPES[dt][:2]), alg_bytes(nnz, n, d, 1, *DTYPES[dt][:2])) for dt in a.dtypes}
         torch.cuda.synchronize()
         torch.cuda.empty_cache()     # the libraries allocate with hipMalloc: give back what the generator's temporaries left cached
         for lb in libs:
             lb.create(csr, n)
         torch.cuda.synchronize()
-        print(f"\n## {shape}: |V| = {n}, nnz = {nnz}, d = {d}; X = {n * d * 4 / 1e9:.2f} GB")
-        # the bits must agree before the times are compared
+        print(f"\n## {shape}: |V| = {n}, nnz = {nnz}, d = {d}; X = {n * d * 4 / 1e9:.2f} GB fp32" + (f" / {n * d * 2 / 1e9:.2f} GB bf16" if bf16 else ""))
+
+        def launches(lb, dt):
+            """(forward, adjoint) callables of one (library, dtype) and their output tensors"""
+            if dt == "f32":
+                y, dx = out["f32"]
+                return (lambda: lb.forward(x, y)), (lambda: lb.adjoint(dy, dx)), y, dx
+            code = DTYPES[dt][2]
+            y, dx = out["bf16" if code == DTYPE_BF16 else "f32"]
+            return (lambda: lb.forward_bf16(xb, y, code)), (lambda: lb.adjoint_bf16(dyb, dx, code)), y, dx
+
+        def checksum(t):
+            return int(t.float().view(torch.int32).to(torch.int64).sum())
+
+        cfgs = [(lb, dt) for lb in libs for dt in a.dtypes if dt == "f32" or lb.has_bf16]
+        # the bits must agree before the times are compared (the fp32 launches run once as the reference even when not timed)
         sums = {}
-        for lb in libs:
-            lb.forward(x, y)
-            lb.adjoint(dy, dx)
+        for lb, dt in [(lb, "f32") for lb in libs if "f32" not in a.dtypes] + cfgs:
+            fwd, adj, y, dx = launches(lb, dt)
+            fwd()
+            adj()
             torch.cuda.synchronize()
-            sums[lb.name] = (int(y.view(torch.int32).to(torch.int64).sum()), int(dx.view(torch.int32).to(torch.int64).sum()))
-        print("checksums (Y, dX) identical across libraries:", len(set(sums.values())) == 1, sums[libs[0].name])
-        per = {lb.name: {"fwd": [], "adj": []} for lb in libs}
+            sums[(lb.name, dt)] = (checksum(y), checksum(dx))
+            if dt == "f32" and bf16:   # what the bf16 -> bf16 launches must reproduce
+                sums[(lb.name, "f32_rounded")] = (checksum(y.to(torch.bfloat16)), checksum(dx.to(torch.bfloat16)))
+        f32_sums = {v for (name, dt), v in sums.items() if dt == "f32"}
+        print("checksums (Y, dX) of the fp32 launches identical across libraries:", len(f32_sums) == 1, sorted(f32_sums)[0])
+        ref = sums[(libs[0].name, "f32")]
+        for lb, dt in cfgs:
+            if dt != "f32":
+                want = ref if dt == "bf16_f32" else sums[(libs[0].name, "f32_rounded")]
+                print(f"checksums (Y, dX) {lb.name} {dt} == fp32 launch on the upcast operand{' rounded to bf16' if dt == 'bf16_bf16' else ''}:",
+                      sums[(lb.name, dt)] == want, sums[(lb.name, dt)])
+        per = {(lb.name, dt): {"fwd": [], "adj": []} for lb, dt in cfgs}
         for r in range(a.rounds):
-            for lb in libs:
-                f = statistics.median(timed(lambda: lb.forward(x, y), 2, a.launches))
-                t = statistics.median(timed(lambda: lb.adjoint(dy, dx), 2, a.launches))
-                per[lb.name]["fwd"].append(f)
-                per[lb.name]["adj"].append(t)
-                print(f"round {r + 1} {lb.name:>5}  fwd {f:9.3f} ms ({b_fwd / f / 1e6 / 8000:.3f} of 8 TB/s)   adj {t:9.3f} ms ({b_adj / t / 1e6 / 8000:.3f})")
+            for lb, dt in cfgs:
+                fwd, adj, _, _ = launches(lb, dt)
+                f = statistics.median(timed(fwd, 2, a.launches))
+                t = statistics.median(timed(adj, 2, a.launches))
+                per[(lb.name, dt)]["fwd"].append(f)
+                per[(lb.name, dt)]["adj"].append(t)
+                b_fwd, b_adj = nbytes[dt]
+                print(f"round {r + 1} {lb.name:>5} {dt:>9}  fwd {f:9.3f} ms ({b_fwd / f / 1e6 / 8000:.3f} of 8 TB/s)   adj {t:9.3f} ms ({b_adj / t / 1e6 / 8000:.3f})")
         summary[shape] = {}
-        for direction, b in (("fwd", b_fwd), ("adj", b_adj)):
-            ref = statistics.median(per[base][direction])
-            for lb in libs:
-                v = per[lb.name][direction]
+        for i, direction in enumerate(("fwd", "adj")):
+            ref_ms = statistics.median(per[(base, "f32")][direction]) if (base, "f32") in per else float("nan")
+            for lb, dt in cfgs:
+                b = nbytes[dt][i]
+                v = per[(lb.name, dt)][direction]
                 med = statistics.median(v)
-                summary[shape][f"{lb.name}/{direction}"] = {"median_ms": med, "min_ms": min(v), "max_ms": max(v), "frac": b / med / 1e6 / 8000,
-                                                           "vs_" + base: med / ref - 1.0}
-                print(f"{shape:>12} {direction} {lb.name:>5}: median of rounds {med:9.3f} ms  [{min(v):.3f} .. {max(v):.3f}]  frac {b / med / 1e6 / 8000:.3f}  "
-                      f"{(med / ref - 1.0) * 100:+.2f} % vs {base}")
+                key = f"{lb.name}/{direction}" if dt == "f32" else f"{lb.name}/{dt}/{direction}"
+                summary[shape][key] = {"median_ms": med, "min_ms": min(v), "max_ms": max(v), "algorithmic_GB": b / 1e9, "frac": b / med / 1e6 / 8000,
+                                       "edges_per_s": edges / med * 1e3, "vs_" + base: med / ref_ms - 1.0, "checksums": sums[(lb.name, dt)]}
+                print(f"{shape:>12} {direction} {lb.name:>5} {dt:>9}: median of rounds {med:9.3f} ms  [{min(v):.3f} .. {max(v):.3f}]  {b / 1e9:7.2f} GB  "
+                      f"frac {b / med / 1e6 / 8000:.3f}  {edges / med * 1e3 / 1e9:7.2f} G edges/s  {(med / ref_ms - 1.0) * 100:+.2f} % time vs {base} f32")
         for lb in libs:
             lb.destroy()
-        del csr, x, dy, y, dx
+        del csr, x, dy, xb, dyb, out
         torch.cuda.empty_cache()
     print("\n" + json.dumps({"summary": summary}))
 
