@@ -120,8 +120,16 @@ __global__ void check_colidx_kernel(const int32_t* __restrict__ colidx, int64_t 
     if (bad) atomicOr(flag, 1);
 }
 
-void launch_in_tile_short(bool sum, const LaunchParams& p, int slice, bool off32, bool fb4, dim3 grid, hipStream_t stream);
-void launch_bf16(bool sum, bool out_bf16, const LaunchParams& p, const KernelChoice& k, dim3 grid, hipStream_t stream);
+// compiled in translation units of their own (see spmm_short.hip and spmm_bf16.hip)
+extern template void launch_in_tile_short_rows<32, false, float, float>(const LaunchParams&, const Schedule&, dim3, hipStream_t);
+extern template void launch_in_tile_short_rows<16, false, float, float>(const LaunchParams&, const Schedule&, dim3, hipStream_t);
+extern template void launch_in_tile_short_rows<32, true, float, float>(const LaunchParams&, const Schedule&, dim3, hipStream_t);
+extern template void launch_in_tile_short_rows<16, true, float, float>(const LaunchParams&, const Schedule&, dim3, hipStream_t);
+extern template void launch_spmm<false, bf16, float>(const LaunchParams&, const Schedule&, dim3, hipStream_t);
+extern template void launch_spmm<false, bf16, bf16>(const LaunchParams&, const Schedule&, dim3, hipStream_t);
+extern template void launch_spmm<true, bf16, float>(const LaunchParams&, const Schedule&, dim3, hipStream_t);
+extern template void launch_spmm<true, bf16, bf16>(const LaunchParams&, const Schedule&, dim3, hipStream_t);
+
 int transpose_csr_device(int64_t n_rows, int64_t n_cols, int64_t nnz, const int64_t* rowptr, const int32_t* colidx,
                          const float* vals, int64_t** t_rowptr_out, int32_t** t_colidx_out, float** t_vals_out,
                          uint32_t** perm_out_keep, hipStream_t stream, std::string* err);
@@ -132,6 +140,7 @@ namespace {
 
 using h2gcn::HopCsr;
 using h2gcn::LaunchParams;
+using h2gcn::Schedule;
 
 // Host transposition of one CSR (counting sort by column; keeps ascending row order inside each output row,
 // i.e. the canonical order `tf.sparse.reorder` would give the adjoint operand).
@@ -404,7 +413,28 @@ struct LaunchShape {
     double short_nnz_frac;  // share of its nonzeros
 };
 
-LaunchShape shape_of(const h2gcn_plan* plan, uint32_t mask, bool adjoint);
+// The LaunchShape of a launch over the hop selection `mask` that gathers from `src` (row / hop stride in elements, width d):
+// the one definition behind the launch, h2gcn_spmm_workspace_bytes and the two report functions (plan creation passes the
+// selection alone).  Without a pointer the base counts as line-aligned.  The short-class fields are filled in by decide().
+LaunchShape shape_of(const h2gcn_plan* plan, uint32_t mask, bool adjoint, const void* src = nullptr, int64_t ld_src = 0,
+                     int64_t ld_src_hop = 0, int d = 0) {
+    LaunchShape sh;
+    memset(&sh, 0, sizeof(sh));
+    sh.adjoint = adjoint;
+    const std::vector<HopOperand>& ops = adjoint ? plan->adj : plan->fwd;
+    for (int k = 0; k < plan->n_hops; ++k)
+        if (mask & (1u << k)) { sh.nnz_sel += ops[k].nnz; ++sh.n_sel; }
+    sh.n_out = adjoint ? plan->n_cols : plan->n_rows;
+    sh.n_src = adjoint ? plan->n_rows : plan->n_cols;
+    sh.avg = (sh.n_out > 0 && sh.n_sel > 0) ? (double)sh.nnz_sel / ((double)sh.n_out * sh.n_sel) : 0.0;
+    sh.ld_src = ld_src;
+    sh.d = d;
+    // (bf16 sources: the fp32 rule on the element strides)
+    sh.src_line_aligned = (reinterpret_cast<uintptr_t>(src) & 127u) == 0 && (ld_src * 4) % 128 == 0 &&
+                          (!adjoint || sh.n_sel <= 1 || (ld_src_hop * 4) % 128 == 0);
+    return sh;
+}
+
 int fill_short(const h2gcn_plan* plan, uint32_t mask, bool adjoint, LaunchShape& sh, bool build_lists = false);
 
 // Slice width of the slice-major scratch copy this launch should gather from (see repack_slice_major_kernel);
@@ -440,13 +470,9 @@ size_t scratch_bytes(const LaunchShape& sh, int rs) {
     return (size_t)sh.n_src * n_slices * (size_t)rs * 4 * (size_t)(sh.adjoint ? sh.n_sel : 1);
 }
 
-struct Schedule {
-    bool pipe, scalar128, exact, shortrow, lists, fb4;
-    int slice;
-};
-
-// The launch-time decisions (also reported by h2gcn_plan_schedule).  `exact_ok`: the float4 kernels can serve the
-// launch (d >= 4; narrower rows take the generic column-tiled kernel).
+// The launch-time decisions (also reported by h2gcn_plan_schedule and h2gcn_plan_segment_classes), after filling in the
+// short-class fields of `sh`.  `scratch`: slice width of the scratch copy the launch gathers from (0: none); `gen`: general
+// store.  Sets every field of `sc` but off32, which the launch decides.
 //
 // CSR-adaptive dispatch.  Long segments (>= long_row_threshold) always have their own workgroups.  For the rest:
 //   * segments short throughout (mean < 16 nonzeros over the selected hops): the IN-TILE short-row mode -- tile walk, G
@@ -459,61 +485,52 @@ struct Schedule {
 //     28.9-29.2 in-tile; neutral where the longer segments carry the bytes: h2gcn_like, products_tail);
 //   * otherwise the wave-per-segment tile walk.
 // (Rounds 2-3 chose ONE walk per launch from the pooled mean alone.)
-Schedule decide(int variant, bool exact_ok, int d, int rows_per_wave, int n_sel, int forced_slice, int64_t n_src_rows,
-                double avg_segment_nnz, bool rows_line_aligned, bool gen, double short_frac, double short_nnz_frac, double short_min_frac,
-                int64_t n_out_rows) {
-    Schedule sc;
+int decide(const h2gcn_plan* plan, uint32_t mask, LaunchShape& sh, int scratch, bool gen, Schedule& sc) {
+    const int st = fill_short(plan, mask, sh.adjoint, sh);
+    if (st != H2GCN_OK) return st;
+    const int d = sh.d;
+    const bool exact_ok = d >= 4;   // the float4 kernels can serve the launch; narrower rows take the generic column-tiled kernel
+    const int forced_slice = scratch > 0 ? scratch : plan->slice_cols;
     // index prefetch across segments: pays on short segments (+4 % at mean degree 4), costs ~0.4 % on long ones;
     // variant 2 forces it, variant 3 forbids it (bitwise-identical results either way)
-    if (variant == 4) variant = 0;
-    sc.pipe = (variant == 2 || (variant == 0 && avg_segment_nnz < 16.0)) && rows_per_wave * n_sel <= 32;
+    const int variant = plan->variant == 4 ? 0 : plan->variant;
+    sc.pipe = (variant == 2 || (variant == 0 && sh.avg < 16.0)) && plan->rows_per_wave * sh.n_sel <= 32;
     sc.scalar128 = exact_ok && variant == 1 && d == 128 && forced_slice == 0;  // variant 1 only exists for d = 128
-    sc.slice = (exact_ok && !sc.scalar128) ? pick_slice_cols(d, n_src_rows, forced_slice, avg_segment_nnz, rows_line_aligned) : 0;
+    // (the rows of a scratch copy are line-aligned; its slice width is forced anyway)
+    sc.slice = (exact_ok && !sc.scalar128) ? pick_slice_cols(d, sh.n_src, forced_slice, sh.avg, scratch > 0 || sh.src_line_aligned) : 0;
     sc.exact = sc.slice > 0 || sc.scalar128;
+    sc.gen = gen;
     const bool grouped_ok = sc.exact && !sc.scalar128 && !gen && (sc.slice == 64 || sc.slice == 128);   // 4 / 2 lane groups, plain stores
     // variant 5 forces the in-tile short-row mode, variant 6 the list-driven launch (when a short segment exists at all);
     // variants 2 / 3 keep the wave-per-segment walk with / without the index prefetch
     // (the in-tile mode is a THROUGHPUT device: below ~50 k output rows a launch is a few waves' dependent chains, a wave takes
     // one row -- see kWavesToFill -- and a round of the in-tile mode would use one of its G lane groups; such launches are
     // list-driven instead: citeseer epoch 0.277-0.328 ms in-tile vs 0.256 ms, profiles/r04_ab_work_per_wave.txt)
-    sc.shortrow = grouped_ok && (variant == 5 || (variant == 0 && avg_segment_nnz < 16.0 && n_out_rows >= 4 * kWavesToFill));
-    sc.lists = grouped_ok && !sc.shortrow && short_frac > 0.0 && (variant == 6 || (variant == 0 && short_frac >= short_min_frac));
+    sc.shortrow = grouped_ok && (variant == 5 || (variant == 0 && sh.avg < 16.0 && sh.n_out >= 4 * kWavesToFill));
+    sc.lists = grouped_ok && !sc.shortrow && sh.short_frac > 0.0 && (variant == 6 || (variant == 0 && sh.short_frac >= plan->short_min_frac));
     sc.pipe = sc.pipe && sc.exact && !sc.shortrow && !sc.lists && !gen;
     // shallow load batches (more waves per SIMD) once the gather source is far beyond the caches: in-tile mode always
     // (profiles/r02_ab_short_row_occupancy_auto.txt), list-driven launches when most nonzeros sit in short segments
-    const bool beyond = (double)n_src_rows * d * 4.0 >= 512.0 * 1024 * 1024;
-    sc.fb4 = beyond && (sc.shortrow || (sc.lists && short_nnz_frac > 0.5));
-    return sc;
+    const bool beyond = (double)sh.n_src * d * 4.0 >= 512.0 * 1024 * 1024;
+    sc.fb4 = beyond && (sc.shortrow || (sc.lists && sh.short_nnz_frac > 0.5));
+    sc.off32 = false;
+    return H2GCN_OK;
 }
 
-// src_bf16 / out_bf16: element types of the gather source and of the output (the schedule is the same as for fp32 operands of
-// the same width and element strides)
-template <bool SUM>
-int launch(LaunchParams& p, const h2gcn_plan* plan, uint32_t mask, LaunchShape& sh, bool off32, int forced_slice, hipStream_t stream,
-           bool src_bf16 = false, bool out_bf16 = false) {
+// Slices, list-driven work split and grid of a decided launch, then its kernel (the router: direction x source type x output
+// type; launch_spmm picks the walk family and the lane geometry).
+int launch(LaunchParams& p, const h2gcn_plan* plan, uint32_t mask, LaunchShape& sh, const Schedule& sc, bool adjoint,
+           bool src_bf16, bool out_bf16, hipStream_t stream) {
     using namespace h2gcn;
-    // A/B measurements only (profiles/r04_ab_off64_*.txt): run the 64-bit-offset instantiations on an operand that would
-    // qualify for 32-bit gather offsets
-    static const bool force_off64 = getenv("H2GCN_FORCE_OFF64") != nullptr;
-    if (force_off64) off32 = false;
-    const int variant = plan->variant;
-    const bool exact_ok = p.d >= 4;
-    // general store (bias / ReLU epilogue, element-wise tail of a width that is not a multiple of 4): dedicated instantiations
-    const bool gen = p.d % 4 != 0 || p.bias != nullptr || p.relu != 0 || p.accumulate != 0;
-    const Schedule sc = decide(variant, exact_ok, p.d, p.rows_per_wave, p.n_sel, forced_slice, sh.n_src, sh.avg,
-                               sh.src_line_aligned, gen, sh.short_frac, sh.short_nnz_frac, plan->short_min_frac, sh.n_out);
-    const bool short_fb4 = sc.fb4;
-    const bool pipe = sc.pipe, scalar128 = sc.scalar128, exact = sc.exact, shortrow = sc.shortrow, lists = sc.lists;
-    const int slice = sc.slice;
-    p.slice_cols = exact ? (slice > 0 ? slice : 128) : p.d;
-    p.n_slices = exact ? (p.d + p.slice_cols - 1) / p.slice_cols : 1;
+    p.slice_cols = sc.exact ? (sc.slice > 0 ? sc.slice : 128) : p.d;
+    p.n_slices = sc.exact ? (p.d + p.slice_cols - 1) / p.slice_cols : 1;
     if (p.src_slice_stride == 0) p.src_slice_stride = p.slice_cols;  // row-major source
     p.short_max = -1;
     p.short_groups = p.med_groups = 0;
-    if (lists) {
+    if (sc.lists) {
         // the device lists exist from the first list-driven launch of this selection on (all-hops selections of mixed operands:
         // from plan creation, so that such launches can be captured into a hipGraph without a warm-up)
-        int st = fill_short(plan, mask, SUM, sh, true);
+        int st = fill_short(plan, mask, adjoint, sh, true);
         if (st != H2GCN_OK) return st;
         // list-driven launch: short-list workgroups serve 4 waves x 64 entries, medium-list workgroups 4 waves x
         // med_per_wave entries; forward -- one run of workgroups per selected hop and class
@@ -524,12 +541,12 @@ int launch(LaunchParams& p, const h2gcn_plan* plan, uint32_t mask, LaunchShape& 
             longest = std::max(longest, sh.short_count[s]);
         }
         // entries per wave follow the size of the launch (see kWavesToFill): a medium-list wave walks up to 8 segments
-        // (SUM: 4 rows), a lane-group wave serves up to 64 entries (one coalesced list read, 16-32 rounds) -- fewer on small
+        // (adjoint: 4 rows), a lane-group wave serves up to 64 entries (one coalesced list read, 16-32 rounds) -- fewer on small
         // operands, so that the launch still has a couple of waves per wave slot of the chip
         static const int env_mpw = getenv("H2GCN_MED_PER_WAVE") ? atoi(getenv("H2GCN_MED_PER_WAVE")) : 0;
         static const int env_spw = getenv("H2GCN_SHORT_PER_WAVE") ? atoi(getenv("H2GCN_SHORT_PER_WAVE")) : 0;
         static const int env_major = getenv("H2GCN_SHORT_HOP_MAJOR") ? atoi(getenv("H2GCN_SHORT_HOP_MAJOR")) : -1;
-        const int mpw_max = SUM ? std::max(1, std::min(4, kWave / p.n_sel)) : 8;
+        const int mpw_max = adjoint ? std::max(1, std::min(4, kWave / p.n_sel)) : 8;
         p.med_per_wave = (int)std::max<int64_t>(1, std::min<int64_t>(n_med / kWavesToFill, mpw_max));
         if (env_mpw >= 1 && env_mpw * p.n_sel <= kWave) p.med_per_wave = env_mpw;
         p.short_per_wave = 4;
@@ -549,7 +566,7 @@ int launch(LaunchParams& p, const h2gcn_plan* plan, uint32_t mask, LaunchShape& 
             mblocks += (sh.med_count[s] + per_block - 1) / per_block;
             p.med_end[s] = mblocks;
         }
-        if (!SUM && !p.short_hop_major) sblocks = (longest + s_per_block - 1) / s_per_block * sh.n_short_lists;   // chunk-major: every hop padded to the longest list
+        if (!adjoint && !p.short_hop_major) sblocks = (longest + s_per_block - 1) / s_per_block * sh.n_short_lists;   // chunk-major: every hop padded to the longest list
         p.short_groups = (sblocks + kNumXcd - 1) / kNumXcd;
         p.med_groups = (mblocks + kNumXcd - 1) / kNumXcd;
         p.short_max = plan->short_max;
@@ -561,17 +578,12 @@ int launch(LaunchParams& p, const h2gcn_plan* plan, uint32_t mask, LaunchShape& 
     if (n_blocks <= 0) return H2GCN_OK;
     if (n_blocks > 0x7fffffffLL) return fail(H2GCN_ERR_INVALID_ARGUMENT, "grid too large (%lld blocks)", (long long)n_blocks);
     const dim3 grid((unsigned)n_blocks);
-    const KernelChoice kc{scalar128, lists, shortrow, pipe, gen, off32, short_fb4, slice};
-    if (src_bf16) {
-        // bf16 gather sources: every instantiation lives in spmm_bf16.hip
-        launch_bf16(SUM, out_bf16, p, kc, grid, stream);
-    } else if ((slice == 128 || slice == 64) && shortrow) {
-        // the in-tile short-row kernels live in a translation unit of their own (spmm_short.hip): compiled next to them,
-        // the tile-walk kernels of THIS file come out 2-6 VGPRs heavier and several of them spill (tools/kernel_resources.py)
-        launch_in_tile_short(SUM, p, slice, off32, short_fb4, grid, stream);
-    } else {
-        launch_spmm_kernels<SUM, float, float>(p, kc, grid, stream);
-    }
+    if (!src_bf16 && adjoint) launch_spmm<true, float, float>(p, sc, grid, stream);
+    else if (!src_bf16) launch_spmm<false, float, float>(p, sc, grid, stream);
+    else if (out_bf16 && adjoint) launch_spmm<true, bf16, bf16>(p, sc, grid, stream);
+    else if (out_bf16) launch_spmm<false, bf16, bf16>(p, sc, grid, stream);
+    else if (adjoint) launch_spmm<true, bf16, float>(p, sc, grid, stream);
+    else launch_spmm<false, bf16, float>(p, sc, grid, stream);
     H2GCN_HIP_TRY(hipGetLastError());
     return H2GCN_OK;
 }
@@ -850,25 +862,6 @@ int h2gcn_plan_info(const h2gcn_plan_t* plan, int hop, int64_t* n_rows, int64_t*
 }
 
 namespace {
-// hop selection -> LaunchShape (src_vec_ok / ld_src / d are filled in by the caller)
-// every gathered row starts on a 128-byte cache line
-bool line_aligned(const float* src, int64_t ld_src, int64_t ld_src_hop, int n_sel, bool adjoint) {
-    return (reinterpret_cast<uintptr_t>(src) & 127u) == 0 && (ld_src * 4) % 128 == 0 && (!adjoint || n_sel <= 1 || (ld_src_hop * 4) % 128 == 0);
-}
-
-LaunchShape shape_of(const h2gcn_plan* plan, uint32_t mask, bool adjoint) {
-    LaunchShape sh;
-    memset(&sh, 0, sizeof(sh));
-    sh.adjoint = adjoint;
-    const std::vector<HopOperand>& ops = adjoint ? plan->adj : plan->fwd;
-    for (int k = 0; k < plan->n_hops; ++k)
-        if (mask & (1u << k)) { sh.nnz_sel += ops[k].nnz; ++sh.n_sel; }
-    sh.n_out = adjoint ? plan->n_cols : plan->n_rows;
-    sh.n_src = adjoint ? plan->n_rows : plan->n_cols;
-    sh.avg = (sh.n_out > 0 && sh.n_sel > 0) ? (double)sh.nnz_sel / ((double)sh.n_out * sh.n_sel) : 0.0;
-    return sh;
-}
-
 // The binned short segments this hop selection can use (lists are built on first use and cached in the plan).
 // Shares of the launch's segments / nonzeros in the short class (always), and -- build_lists -- the device lists themselves.
 int fill_short(const h2gcn_plan* plan, uint32_t mask, bool adjoint, LaunchShape& sh, bool build_lists) {
@@ -913,42 +906,48 @@ int fill_short(const h2gcn_plan* plan, uint32_t mask, bool adjoint, LaunchShape&
     return H2GCN_OK;
 }
 
+// The launch that h2gcn_plan_schedule and h2gcn_plan_segment_classes describe.  Their assumptions, stated once: no pointer, so
+// the base is line-aligned; the adjoint hop stride is d, as for a contiguous [n, H, d] gradient; the general store follows from
+// d % 4 alone (no epilogue); the scratch copy (`scratch`) is taken whenever the heuristic wants one.
+int report_schedule(const h2gcn_plan* plan, uint32_t hop_mask, int adjoint, int64_t ld_src, int32_t d, uint32_t* mask,
+                    LaunchShape& sh, int& scratch, Schedule& sc) {
+    if (!plan) return fail(H2GCN_ERR_INVALID_ARGUMENT, "plan is NULL");
+    int st = resolve_mask(plan, hop_mask, mask);
+    if (st != H2GCN_OK) return st;
+    if (d < 1 || ld_src < d) return fail(H2GCN_ERR_INVALID_ARGUMENT, "bad width %d / stride %lld", d, (long long)ld_src);
+    if (adjoint && !plan->has_transpose) return fail(H2GCN_ERR_NO_TRANSPOSE, "plan was created without H2GCN_PLAN_BUILD_TRANSPOSE");
+    sh = shape_of(plan, *mask, adjoint != 0, nullptr, ld_src, d, d);
+    scratch = scratch_slice_cols(plan, sh);
+    return decide(plan, *mask, sh, scratch, d % 4 != 0, sc);
+}
+
 }  // namespace
 
 int h2gcn_plan_schedule(const h2gcn_plan_t* plan, uint32_t hop_mask, int adjoint, int64_t ld_src, int32_t d,
                         int32_t* slice_cols, int32_t* n_slices, int32_t* segment_walk, int32_t* scratch_copy) {
-    if (!plan) return fail(H2GCN_ERR_INVALID_ARGUMENT, "plan is NULL");
     uint32_t mask;
-    int st = resolve_mask(plan, hop_mask, &mask);
+    LaunchShape sh;
+    int scratch;
+    Schedule sc;
+    const int st = report_schedule(plan, hop_mask, adjoint, ld_src, d, &mask, sh, scratch, sc);
     if (st != H2GCN_OK) return st;
-    if (d < 1 || ld_src < d) return fail(H2GCN_ERR_INVALID_ARGUMENT, "bad width %d / stride %lld", d, (long long)ld_src);
-    if (adjoint && !plan->has_transpose) return fail(H2GCN_ERR_NO_TRANSPOSE, "plan was created without H2GCN_PLAN_BUILD_TRANSPOSE");
-    LaunchShape sh = shape_of(plan, mask, adjoint != 0);
-    if ((st = fill_short(plan, mask, adjoint != 0, sh)) != H2GCN_OK) return st;
-    sh.ld_src = ld_src;
-    sh.d = d;
-    sh.src_line_aligned = (ld_src * 4) % 128 == 0 && (!adjoint || sh.n_sel <= 1 || (d * 4) % 128 == 0);  // aligned base assumed
-    const int rs = scratch_slice_cols(plan, sh);
-    const Schedule sc = decide(plan->variant, d >= 4, d, plan->rows_per_wave, sh.n_sel, rs > 0 ? rs : plan->slice_cols, sh.n_src, sh.avg,
-                               rs > 0 || sh.src_line_aligned, d % 4 != 0, sh.short_frac, sh.short_nnz_frac, plan->short_min_frac, sh.n_out);
     const int w = sc.exact ? (sc.slice > 0 ? sc.slice : 128) : d;
     if (slice_cols) *slice_cols = w;
     if (n_slices) *n_slices = sc.exact ? (d + w - 1) / w : 1;
     if (segment_walk) *segment_walk = sc.pipe ? 1 : (sc.shortrow ? 2 : (sc.lists ? 3 : 0));
-    if (scratch_copy) *scratch_copy = rs > 0 ? 1 : 0;
+    if (scratch_copy) *scratch_copy = scratch > 0 ? 1 : 0;
     return H2GCN_OK;
 }
 
 int h2gcn_plan_segment_classes(const h2gcn_plan_t* plan, uint32_t hop_mask, int adjoint, int64_t ld_src, int32_t d,
                                int64_t* segments, int64_t* nonzeros, int64_t* listed) {
-    if (!plan) return fail(H2GCN_ERR_INVALID_ARGUMENT, "plan is NULL");
     uint32_t mask;
-    int st = resolve_mask(plan, hop_mask, &mask);
+    LaunchShape sh;
+    int scratch;
+    Schedule sc;
+    const int st = report_schedule(plan, hop_mask, adjoint, ld_src, d, &mask, sh, scratch, sc);
     if (st != H2GCN_OK) return st;
-    if (d < 1 || ld_src < d) return fail(H2GCN_ERR_INVALID_ARGUMENT, "bad width %d / stride %lld", d, (long long)ld_src);
-    if (adjoint && !plan->has_transpose) return fail(H2GCN_ERR_NO_TRANSPOSE, "plan was created without H2GCN_PLAN_BUILD_TRANSPOSE");
     const std::vector<HopOperand>& ops = adjoint ? plan->adj : plan->fwd;
-    const int64_t n_out = adjoint ? plan->n_cols : plan->n_rows;
     int s = 0;
     for (int k = 0; k < plan->n_hops; ++k) {
         if (!(mask & (1u << k))) continue;
@@ -956,7 +955,7 @@ int h2gcn_plan_segment_classes(const h2gcn_plan_t* plan, uint32_t hop_mask, int 
         const int64_t n_long = (int64_t)op.long_rows.size();
         if (segments) {
             segments[3 * s + 0] = op.n_short;
-            segments[3 * s + 1] = n_out - op.n_short - n_long;
+            segments[3 * s + 1] = sh.n_out - op.n_short - n_long;
             segments[3 * s + 2] = n_long;
         }
         if (nonzeros) {
@@ -967,14 +966,6 @@ int h2gcn_plan_segment_classes(const h2gcn_plan_t* plan, uint32_t hop_mask, int 
         ++s;
     }
     if (listed) {
-        LaunchShape sh = shape_of(plan, mask, adjoint != 0);
-        if ((st = fill_short(plan, mask, adjoint != 0, sh)) != H2GCN_OK) return st;
-        sh.ld_src = ld_src;
-        sh.d = d;
-        sh.src_line_aligned = (ld_src * 4) % 128 == 0 && (!adjoint || sh.n_sel <= 1 || (d * 4) % 128 == 0);
-        const int rs = scratch_slice_cols(plan, sh);
-        const Schedule sc = decide(plan->variant, d >= 4, d, plan->rows_per_wave, sh.n_sel, rs > 0 ? rs : plan->slice_cols, sh.n_src, sh.avg,
-                                   rs > 0 || sh.src_line_aligned, d % 4 != 0, sh.short_frac, sh.short_nnz_frac, plan->short_min_frac, sh.n_out);
         *listed = 0;
         if (sc.lists)
             for (int q = 0; q < sh.n_short_lists; ++q) *listed += sh.short_count[q];
@@ -989,16 +980,8 @@ size_t h2gcn_spmm_workspace_bytes(const h2gcn_plan_t* plan, uint32_t hop_mask, i
     if (adjoint && !plan->has_transpose) return 0;
     uint32_t mask;
     if (resolve_mask(plan, hop_mask, &mask) != H2GCN_OK) return 0;
-    LaunchShape sh = shape_of(plan, mask, adjoint != 0);
-    sh.src_line_aligned = line_aligned(src_dev, ld_src, ld_src_hop, sh.n_sel, adjoint != 0);
-    sh.ld_src = ld_src;
-    sh.d = d;
+    const LaunchShape sh = shape_of(plan, mask, adjoint != 0, src_dev, ld_src, ld_src_hop, d);
     return scratch_bytes(sh, scratch_slice_cols(plan, sh));
-}
-
-int h2gcn_spmm_hops_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* X, int64_t ldx, int32_t d,
-                        float* Y, int64_t ldy_row, int64_t ldy_hop, void* stream_v) {
-    return h2gcn_spmm_hops_opts_f32(plan, hop_mask, X, ldx, d, Y, ldy_row, ldy_hop, nullptr, stream_v);
 }
 
 namespace {
@@ -1012,9 +995,7 @@ int read_launch_opts(const h2gcn_launch_opts* lopts, h2gcn_launch_opts* lo) {
     if (lo->flags & ~(uint32_t)(H2GCN_LAUNCH_RELU | H2GCN_LAUNCH_ACCUMULATE)) return fail(H2GCN_ERR_INVALID_ARGUMENT, "unknown launch flags 0x%x", lo->flags);
     return H2GCN_OK;
 }
-}  // namespace
 
-namespace {
 // bf16 arrays: 4-byte aligned base, even strides (elements) and an even width, so that every lane's load / store is dword-aligned
 int check_bf16_layout(const char* what, const void* p, int64_t ld_row, int64_t ld_hop, int32_t d) {
     if (reinterpret_cast<uintptr_t>(p) & 3u)
@@ -1033,92 +1014,130 @@ int check_dtype(const char* what, int dtype) {
     return H2GCN_OK;
 }
 
-// The forward launch for an fp32 (src_bf16 = false, fp32 output) or a bf16 gather source (fp32 or bf16 output).
-int spmm_forward(const h2gcn_plan_t* plan, uint32_t hop_mask, const void* X, bool src_bf16, int64_t ldx, int32_t d, void* Y,
-                 bool out_bf16, int64_t ldy_row, int64_t ldy_hop, const h2gcn_launch_opts* lopts, void* stream_v) {
-    const int64_t esz = src_bf16 ? 2 : 4;   // bytes per gathered element
+// A dense operand of a launch, as the entry points name it in their messages: element type, base, row / hop stride (elements;
+// the forward source and the adjoint output have no hop dimension: 0).
+struct Dense {
+    const char* name;
+    bool bf16;
+    const void* ptr;
+    int64_t ld_row, ld_hop;
+};
+
+// The hop-SpMM launch behind the six entry points: forward (src = X, dst = Y[:, s, :] = A_s X) or adjoint (src = dY,
+// dst = dX = sum_s A_s^T dY[:, s, :]), fp32 or bf16 gather source and output.  The checks keep the entry points' order,
+// status codes and messages; all of them come before anything is allocated or launched.
+int spmm_hops(bool adjoint, const h2gcn_plan_t* plan, uint32_t hop_mask, Dense src, int32_t d, Dense dst,
+              const h2gcn_launch_opts* lopts, void* stream_v) {
+    using namespace h2gcn;
     try {
         h2gcn_launch_opts lo;
         int st = read_launch_opts(lopts, &lo);
         if (st != H2GCN_OK) return st;
-        if (lo.flags & ~H2GCN_LAUNCH_RELU) return fail(H2GCN_ERR_INVALID_ARGUMENT, "forward launch flags 0x%x: only H2GCN_LAUNCH_RELU applies", lo.flags);
+        if (!adjoint && (lo.flags & ~H2GCN_LAUNCH_RELU))
+            return fail(H2GCN_ERR_INVALID_ARGUMENT, "forward launch flags 0x%x: only H2GCN_LAUNCH_RELU applies", lo.flags);
+        if (adjoint && (lo.bias_dev || (lo.flags & ~H2GCN_LAUNCH_ACCUMULATE)))
+            return fail(H2GCN_ERR_INVALID_ARGUMENT, "the adjoint launch has no bias / activation epilogue (only H2GCN_LAUNCH_ACCUMULATE is accepted)");
+        if (adjoint && dst.bf16 && (lo.flags & H2GCN_LAUNCH_ACCUMULATE))
+            return fail(H2GCN_ERR_INVALID_ARGUMENT, "H2GCN_LAUNCH_ACCUMULATE needs an fp32 dX (a bf16 dX cannot be accumulated into)");
         if (!plan) return fail(H2GCN_ERR_INVALID_ARGUMENT, "plan is NULL");
+        if (adjoint && !plan->has_transpose)
+            return fail(H2GCN_ERR_NO_TRANSPOSE, "plan was created without H2GCN_PLAN_BUILD_TRANSPOSE");
         uint32_t mask;
         st = resolve_mask(plan, hop_mask, &mask);
         if (st != H2GCN_OK) return st;
-        if (src_bf16) {
-            if ((st = check_bf16_layout("X", X, ldx, 0, d)) != H2GCN_OK) return st;
-            if (out_bf16 && (st = check_bf16_layout("Y", Y, ldy_row, ldy_hop, d)) != H2GCN_OK) return st;
+        if (src.bf16) {
+            if ((st = check_bf16_layout(src.name, src.ptr, src.ld_row, src.ld_hop, d)) != H2GCN_OK) return st;
+            if (dst.bf16 && (st = check_bf16_layout(dst.name, dst.ptr, dst.ld_row, dst.ld_hop, d)) != H2GCN_OK) return st;
         }
         if ((st = check_device(plan)) != H2GCN_OK) return st;
         if (d < 1) return fail(H2GCN_ERR_INVALID_ARGUMENT, "d = %d", d);
-        if (plan->n_rows == 0) return H2GCN_OK;
-        if (!Y) return fail(H2GCN_ERR_INVALID_ARGUMENT, "Y is NULL");
-        if (!X && plan->n_cols > 0) return fail(H2GCN_ERR_INVALID_ARGUMENT, "X is NULL");
+        LaunchShape sh = shape_of(plan, mask, adjoint, src.ptr, src.ld_row, src.ld_hop, d);
+        if (sh.n_out == 0) return H2GCN_OK;
+        if (!dst.ptr) return fail(H2GCN_ERR_INVALID_ARGUMENT, "%s is NULL", dst.name);
+        if (!src.ptr && sh.n_src > 0) return fail(H2GCN_ERR_INVALID_ARGUMENT, "%s is NULL", src.name);
+        const int64_t ldx = adjoint ? dst.ld_row : src.ld_row;
         if (ldx < d) return fail(H2GCN_ERR_INVALID_ARGUMENT, "ldx = %lld < d = %d", (long long)ldx, d);
-        if (ldy_hop < 0 || ldy_row < 0) return fail(H2GCN_ERR_INVALID_ARGUMENT, "negative output stride");
+        if (!adjoint && (dst.ld_hop < 0 || dst.ld_row < 0)) return fail(H2GCN_ERR_INVALID_ARGUMENT, "negative output stride");
+        if (adjoint && (src.ld_row < d || src.ld_hop < 0)) return fail(H2GCN_ERR_INVALID_ARGUMENT, "bad gradient strides");
+        if (!adjoint && sh.n_sel > 1 && dst.ld_hop < d)
+            return fail(H2GCN_ERR_INVALID_ARGUMENT, "ldy_hop = %lld < d = %d: hop outputs would overlap", (long long)dst.ld_hop, d);
         CaptureScope capture_scope((hipStream_t)stream_v);
         LaunchParams p;
         memset(&p, 0, sizeof(p));
-        LaunchShape sh = shape_of(plan, mask, false);
+        const std::vector<HopOperand>& ops = adjoint ? plan->adj : plan->fwd;
         int s = 0;
         for (int k = 0; k < plan->n_hops; ++k) {
             if (!(mask & (1u << k))) continue;
-            const HopOperand& op = plan->fwd[k];
+            const HopOperand& op = ops[k];
             p.hop[s] = HopCsr{op.rowptr, op.colidx, op.vals};
-            p.src_hop_off[s] = 0;
-            p.dst_hop_off[s] = (int64_t)s * ldy_hop;
+            p.src_hop_off[s] = (int64_t)s * src.ld_hop;
+            p.dst_hop_off[s] = (int64_t)s * dst.ld_hop;
             ++s;
         }
         p.n_sel = s;
-        if (s > 1 && ldy_hop < d) return fail(H2GCN_ERR_INVALID_ARGUMENT, "ldy_hop = %lld < d = %d: hop outputs would overlap", (long long)ldy_hop, d);
         p.d = d;
         p.d_src = d;
-        p.n_rows = plan->n_rows;
-        p.src = X;
-        p.ld_src = ldx;
-        p.dst = Y;
-        p.ld_dst = ldy_row;
+        p.n_rows = sh.n_out;
+        p.src = src.ptr;
+        p.ld_src = src.ld_row;
+        p.dst = const_cast<void*>(dst.ptr);
+        p.ld_dst = dst.ld_row;
         p.bias = lo.bias_dev;
         p.relu = (lo.flags & H2GCN_LAUNCH_RELU) ? 1 : 0;
-        st = get_long_list(plan, false, mask, &p.long_list, &p.n_long);
+        p.accumulate = (lo.flags & H2GCN_LAUNCH_ACCUMULATE) ? 1 : 0;
+        st = get_long_list(plan, adjoint, mask, &p.long_list, &p.n_long);
         if (st != H2GCN_OK) return st;
         p.long_threshold = plan->long_threshold;
         p.rows_per_wave = plan->rows_per_wave;
-        const int64_t rows_per_tile = (int64_t)p.rows_per_wave * h2gcn::kWavesPerBlock;
+        const int64_t rows_per_tile = (int64_t)p.rows_per_wave * kWavesPerBlock;
         p.n_tiles = (p.n_rows + rows_per_tile - 1) / rows_per_tile;
-        p.tiles_per_xcd = (p.n_tiles + h2gcn::kNumXcd - 1) / h2gcn::kNumXcd;
-        // 32-bit gather offsets when the farthest byte of X is below 4 GiB
-        bool off32 = ((double)(plan->n_cols > 0 ? plan->n_cols - 1 : 0) * (double)ldx + d) * (double)esz < 4294967296.0;
-        int forced_slice = plan->slice_cols;
-        sh.ld_src = ldx;
-        sh.d = d;
-        sh.src_line_aligned = line_aligned((const float*)X, ldx, 0, s, false);   // (bf16: the fp32 rule on the element stride)
-        const int rs = (!src_bf16 && lo.workspace_dev && aligned16(lo.workspace_dev)) ? scratch_slice_cols(plan, sh) : 0;
-        if (rs > 0 && lo.workspace_bytes >= scratch_bytes(sh, rs)) {
-            use_scratch(p, sh, rs, 0, lo.workspace_dev, (hipStream_t)stream_v, &off32);
+        p.tiles_per_xcd = (p.n_tiles + kNumXcd - 1) / kNumXcd;
+        // 32-bit gather offsets when the farthest byte of the source is below 4 GiB (in bytes of its real element type)
+        const int64_t esz = src.bf16 ? 2 : 4;
+        bool off32 = ((double)(sh.n_src > 0 ? sh.n_src - 1 : 0) * (double)src.ld_row + (double)(s - 1) * (double)src.ld_hop + d) *
+                     (double)esz < 4294967296.0;
+        // the slice-major scratch copy: fp32 sources only (bf16 launches gather in place)
+        int scratch = (!src.bf16 && lo.workspace_dev && aligned16(lo.workspace_dev)) ? scratch_slice_cols(plan, sh) : 0;
+        if (scratch > 0 && lo.workspace_bytes >= scratch_bytes(sh, scratch)) {
+            use_scratch(p, sh, scratch, src.ld_hop, lo.workspace_dev, (hipStream_t)stream_v, &off32);
             H2GCN_HIP_TRY(hipGetLastError());
-            forced_slice = rs;
+        } else {
+            scratch = 0;
         }
-        if ((st = fill_short(plan, mask, false, sh)) != H2GCN_OK) return st;
-        return launch<false>(p, plan, mask, sh, off32, forced_slice, (hipStream_t)stream_v, src_bf16, out_bf16);
+        // general store (bias / ReLU epilogue, accumulation, element-wise tail of a width that is not a multiple of 4):
+        // dedicated instantiations
+        const bool gen = d % 4 != 0 || p.bias != nullptr || p.relu != 0 || p.accumulate != 0;
+        Schedule sc;
+        if ((st = decide(plan, mask, sh, scratch, gen, sc)) != H2GCN_OK) return st;
+        // A/B measurements only (profiles/r04_ab_off64_*.txt): run the 64-bit-offset instantiations on an operand that would
+        // qualify for 32-bit gather offsets
+        static const bool force_off64 = getenv("H2GCN_FORCE_OFF64") != nullptr;
+        sc.off32 = off32 && !force_off64;
+        return launch(p, plan, mask, sh, sc, adjoint, src.bf16, dst.bf16, (hipStream_t)stream_v);
     } catch (...) {
-        return fail(H2GCN_ERR_INTERNAL, "unexpected exception in spmm_hops_%s", src_bf16 ? "bf16" : "opts_f32");
+        return fail(H2GCN_ERR_INTERNAL, "unexpected exception in spmm_hops_%s",
+                    adjoint ? (src.bf16 ? "T_bf16" : "T_f32") : (src.bf16 ? "bf16" : "opts_f32"));
     }
 }
 }  // namespace
 
+int h2gcn_spmm_hops_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* X, int64_t ldx, int32_t d,
+                        float* Y, int64_t ldy_row, int64_t ldy_hop, void* stream_v) {
+    return h2gcn_spmm_hops_opts_f32(plan, hop_mask, X, ldx, d, Y, ldy_row, ldy_hop, nullptr, stream_v);
+}
+
 int h2gcn_spmm_hops_opts_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* X, int64_t ldx, int32_t d,
                              float* Y, int64_t ldy_row, int64_t ldy_hop, const h2gcn_launch_opts* lopts,
                              void* stream_v) {
-    return spmm_forward(plan, hop_mask, X, false, ldx, d, Y, false, ldy_row, ldy_hop, lopts, stream_v);
+    return spmm_hops(false, plan, hop_mask, {"X", false, X, ldx, 0}, d, {"Y", false, Y, ldy_row, ldy_hop}, lopts, stream_v);
 }
 
 int h2gcn_spmm_hops_bf16(const h2gcn_plan_t* plan, uint32_t hop_mask, const uint16_t* X, int64_t ldx, int32_t d, int y_dtype,
                          void* Y, int64_t ldy_row, int64_t ldy_hop, const h2gcn_launch_opts* lopts, void* stream_v) {
     const int st = check_dtype("y_dtype", y_dtype);
     if (st != H2GCN_OK) return st;
-    return spmm_forward(plan, hop_mask, X, true, ldx, d, Y, y_dtype == H2GCN_DTYPE_BF16, ldy_row, ldy_hop, lopts, stream_v);
+    return spmm_hops(false, plan, hop_mask, {"X", true, X, ldx, 0}, d, {"Y", y_dtype == H2GCN_DTYPE_BF16, Y, ldy_row, ldy_hop},
+                     lopts, stream_v);
 }
 
 int h2gcn_spmm_hops_T_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* dY, int64_t ldg_row,
@@ -1126,95 +1145,18 @@ int h2gcn_spmm_hops_T_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const flo
     return h2gcn_spmm_hops_T_opts_f32(plan, hop_mask, dY, ldg_row, ldg_hop, d, dX, ldx, nullptr, stream_v);
 }
 
-namespace {
-// The adjoint launch for an fp32 (src_bf16 = false, fp32 dX) or a bf16 gradient (fp32 or bf16 dX).
-int spmm_adjoint(const h2gcn_plan_t* plan, uint32_t hop_mask, const void* dY, bool src_bf16, int64_t ldg_row, int64_t ldg_hop,
-                 int32_t d, void* dX, bool out_bf16, int64_t ldx, const h2gcn_launch_opts* lopts, void* stream_v) {
-    const int64_t esz = src_bf16 ? 2 : 4;   // bytes per gathered element
-    try {
-        h2gcn_launch_opts lo;
-        int st = read_launch_opts(lopts, &lo);
-        if (st != H2GCN_OK) return st;
-        if (lo.bias_dev || (lo.flags & ~H2GCN_LAUNCH_ACCUMULATE))
-            return fail(H2GCN_ERR_INVALID_ARGUMENT, "the adjoint launch has no bias / activation epilogue (only H2GCN_LAUNCH_ACCUMULATE is accepted)");
-        if (out_bf16 && (lo.flags & H2GCN_LAUNCH_ACCUMULATE))
-            return fail(H2GCN_ERR_INVALID_ARGUMENT, "H2GCN_LAUNCH_ACCUMULATE needs an fp32 dX (a bf16 dX cannot be accumulated into)");
-        if (!plan) return fail(H2GCN_ERR_INVALID_ARGUMENT, "plan is NULL");
-        if (!plan->has_transpose)
-            return fail(H2GCN_ERR_NO_TRANSPOSE, "plan was created without H2GCN_PLAN_BUILD_TRANSPOSE");
-        uint32_t mask;
-        st = resolve_mask(plan, hop_mask, &mask);
-        if (st != H2GCN_OK) return st;
-        if (src_bf16) {
-            if ((st = check_bf16_layout("dY", dY, ldg_row, ldg_hop, d)) != H2GCN_OK) return st;
-            if (out_bf16 && (st = check_bf16_layout("dX", dX, ldx, 0, d)) != H2GCN_OK) return st;
-        }
-        if ((st = check_device(plan)) != H2GCN_OK) return st;
-        if (d < 1) return fail(H2GCN_ERR_INVALID_ARGUMENT, "d = %d", d);
-        if (plan->n_cols == 0) return H2GCN_OK;
-        if (!dX) return fail(H2GCN_ERR_INVALID_ARGUMENT, "dX is NULL");
-        if (!dY && plan->n_rows > 0) return fail(H2GCN_ERR_INVALID_ARGUMENT, "dY is NULL");
-        if (ldx < d) return fail(H2GCN_ERR_INVALID_ARGUMENT, "ldx = %lld < d = %d", (long long)ldx, d);
-        if (ldg_row < d || ldg_hop < 0) return fail(H2GCN_ERR_INVALID_ARGUMENT, "bad gradient strides");
-        CaptureScope capture_scope((hipStream_t)stream_v);
-        LaunchParams p;
-        memset(&p, 0, sizeof(p));
-        LaunchShape sh = shape_of(plan, mask, true);
-        int s = 0;
-        for (int k = 0; k < plan->n_hops; ++k) {
-            if (!(mask & (1u << k))) continue;
-            const HopOperand& op = plan->adj[k];
-            p.hop[s] = HopCsr{op.rowptr, op.colidx, op.vals};
-            p.src_hop_off[s] = (int64_t)s * ldg_hop;
-            p.dst_hop_off[s] = 0;
-            ++s;
-        }
-        p.n_sel = s;
-        p.d = d;
-        p.d_src = d;
-        p.n_rows = plan->n_cols;
-        p.src = dY;
-        p.ld_src = ldg_row;
-        p.dst = dX;
-        p.ld_dst = ldx;
-        p.accumulate = (lo.flags & H2GCN_LAUNCH_ACCUMULATE) ? 1 : 0;
-        st = get_long_list(plan, true, mask, &p.long_list, &p.n_long);
-        if (st != H2GCN_OK) return st;
-        p.long_threshold = plan->long_threshold;
-        p.rows_per_wave = plan->rows_per_wave;
-        const int64_t rows_per_tile = (int64_t)p.rows_per_wave * h2gcn::kWavesPerBlock;
-        p.n_tiles = (p.n_rows + rows_per_tile - 1) / rows_per_tile;
-        p.tiles_per_xcd = (p.n_tiles + h2gcn::kNumXcd - 1) / h2gcn::kNumXcd;
-        bool off32 = ((double)(plan->n_rows > 0 ? plan->n_rows - 1 : 0) * (double)ldg_row + (double)(s - 1) * (double)ldg_hop + d) * (double)esz < 4294967296.0;
-        int forced_slice = plan->slice_cols;
-        sh.ld_src = ldg_row;
-        sh.d = d;
-        sh.src_line_aligned = line_aligned((const float*)dY, ldg_row, ldg_hop, s, true);   // (bf16: the fp32 rule on the element strides)
-        const int rs = (!src_bf16 && lo.workspace_dev && aligned16(lo.workspace_dev) && plan->n_rows > 0) ? scratch_slice_cols(plan, sh) : 0;
-        if (rs > 0 && lo.workspace_bytes >= scratch_bytes(sh, rs)) {
-            use_scratch(p, sh, rs, ldg_hop, lo.workspace_dev, (hipStream_t)stream_v, &off32);
-            H2GCN_HIP_TRY(hipGetLastError());
-            forced_slice = rs;
-        }
-        if ((st = fill_short(plan, mask, true, sh)) != H2GCN_OK) return st;
-        return launch<true>(p, plan, mask, sh, off32, forced_slice, (hipStream_t)stream_v, src_bf16, out_bf16);
-    } catch (...) {
-        return fail(H2GCN_ERR_INTERNAL, "unexpected exception in spmm_hops_T_%s", src_bf16 ? "bf16" : "f32");
-    }
-}
-}  // namespace
-
 int h2gcn_spmm_hops_T_opts_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* dY, int64_t ldg_row,
                                int64_t ldg_hop, int32_t d, float* dX, int64_t ldx, const h2gcn_launch_opts* lopts,
                                void* stream_v) {
-    return spmm_adjoint(plan, hop_mask, dY, false, ldg_row, ldg_hop, d, dX, false, ldx, lopts, stream_v);
+    return spmm_hops(true, plan, hop_mask, {"dY", false, dY, ldg_row, ldg_hop}, d, {"dX", false, dX, ldx, 0}, lopts, stream_v);
 }
 
 int h2gcn_spmm_hops_T_bf16(const h2gcn_plan_t* plan, uint32_t hop_mask, const uint16_t* dY, int64_t ldg_row, int64_t ldg_hop,
                            int32_t d, int dx_dtype, void* dX, int64_t ldx, const h2gcn_launch_opts* lopts, void* stream_v) {
     const int st = check_dtype("dx_dtype", dx_dtype);
     if (st != H2GCN_OK) return st;
-    return spmm_adjoint(plan, hop_mask, dY, true, ldg_row, ldg_hop, d, dX, dx_dtype == H2GCN_DTYPE_BF16, ldx, lopts, stream_v);
+    return spmm_hops(true, plan, hop_mask, {"dY", true, dY, ldg_row, ldg_hop}, d, {"dX", dx_dtype == H2GCN_DTYPE_BF16, dX, ldx, 0},
+                     lopts, stream_v);
 }
 
 }  // extern "C"

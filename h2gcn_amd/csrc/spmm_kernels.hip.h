@@ -961,27 +961,34 @@ __device__ __forceinline__ void in_tile_short_rows(const LaunchParams& p, int la
     }
 }
 
-// Instantiations that need more than 80 VGPRs to stay out of scratch (tools/kernel_resources.py): 64-bit gather offsets
-// (two address registers per load in flight) together with a general store, a 128 / 256-column slice or the index prefetch;
-// the prefetching walk on 128-column slices.  They run at H2GCN_OFF64_HEAVY_MIN_WAVES (5) waves per SIMD.
-template <int VEC, int LPR, bool SUM, bool OFF32, bool PIPE, bool SHORT, bool EPI>
-constexpr bool heavy_registers() {
-    if (VEC != 4) return false;
-    if (SHORT) return (SUM && (!OFF32 || LPR >= 32)) || (!OFF32 && LPR >= 32);   // (the list-driven kernels at FB = 8)
-    if (!OFF32) return EPI || LPR >= 32 || PIPE;
-    return PIPE && LPR == 32;
-}
-
-// bf16 gather sources: the instantiations whose fp32 bound leaves them short of registers (scratch; tools/kernel_resources.py)
-// run one wave per SIMD lower -- the list-driven adjoint at FB = 4 with 64-bit offsets, the general store of 128-column slices
-// with 32-bit offsets, the prefetching adjoint walk of 64-column slices and the plain forward walk of 64-column slices with
-// 64-bit offsets.  (Unpacking a bf16 pair costs a register per element in flight: the bf16 kernels are not lighter than the
-// fp32 ones.)
-template <typename TS, int VEC, int LPR, bool SUM, bool OFF32, bool PIPE, bool SHORT, bool EPI, int FB, bool LISTS>
-constexpr bool bf16_one_wave_less() {
-    if (!std::is_same<TS, bf16>::value || VEC != 4 || SHORT) return false;
-    if (LISTS) return FB == 4 && SUM && !OFF32;
-    return (OFF32 && EPI && LPR == 32) || (SUM && OFF32 && PIPE && LPR == 16) || (!SUM && !OFF32 && !PIPE && !EPI && LPR == 16);
+// Waves per SIMD the register budget of an instantiation must allow: the second argument of the __launch_bounds__ of
+// spmm_hops_kernel (template parameters as there).  The H2GCN_*_MIN_WAVES macros are A/B knobs (tools/build_ab_lib.sh).
+template <int VEC, int LPR, bool EXACT, bool SUM, bool OFF32, bool PIPE, bool SHORT, bool EPI, int FB, bool LISTS, typename TS>
+constexpr int min_waves_per_simd() {
+    // the generic column-tiled kernel (d < 4)
+    if (!EXACT) return 2;
+    // in-tile short-row kernels: the forward ones with shallow fallback batches at 7, the others at 4
+    if (SHORT) return FB == 4 && !SUM ? H2GCN_SHORT_FB4_MIN_WAVES : H2GCN_SHORT_MIN_WAVES;
+    // bf16 gather sources: the instantiations whose fp32 bound leaves them short of registers (scratch; tools/kernel_resources.py)
+    // run one wave per SIMD lower -- the list-driven adjoint at FB = 4 with 64-bit offsets, the general store of 128-column
+    // slices with 32-bit offsets, the prefetching adjoint walk of 64-column slices and the plain forward walk of 64-column
+    // slices with 64-bit offsets.  (Unpacking a bf16 pair costs a register per element in flight: the bf16 kernels are not
+    // lighter than the fp32 ones.)
+    const bool bf16_less = std::is_same<TS, bf16>::value && VEC == 4 &&
+                           (LISTS ? FB == 4 && SUM && !OFF32
+                                  : (OFF32 && EPI && LPR == 32) || (SUM && OFF32 && PIPE && LPR == 16) ||
+                                        (!SUM && !OFF32 && !PIPE && !EPI && LPR == 16));
+    // list-driven kernels with shallow load batches (FB = 4)
+    if (LISTS && FB == 4) return H2GCN_SHORT_FB4_MIN_WAVES - bf16_less;
+    // instantiations that need more than 80 VGPRs to stay out of scratch (tools/kernel_resources.py): 64-bit gather offsets
+    // (two address registers per load in flight) together with a general store, a 128 / 256-column slice or the index
+    // prefetch; the prefetching walk on 128-column slices; list-driven walks (FB = 8) with 64-bit offsets on 128-column slices,
+    // and adjoint ones with 64-bit offsets or on 128-column slices
+    const bool heavy = VEC == 4 && (LISTS ? (SUM && (!OFF32 || LPR >= 32)) || (!OFF32 && LPR >= 32)
+                                          : !OFF32 ? EPI || LPR >= 32 || PIPE : PIPE && LPR == 32);
+    if (heavy) return H2GCN_OFF64_HEAVY_MIN_WAVES - bf16_less;
+    // everything else: 6 (the 128 / 256-column slices have a knob of their own)
+    return (LPR >= 32 ? H2GCN_WIDE_MIN_WAVES : kMinWavesPerSimd) - bf16_less;
 }
 
 // VEC    floats per lane per gathered row (4 on the fast paths)
@@ -1012,11 +1019,7 @@ constexpr bool bf16_one_wave_less() {
 //        occupancy buys bandwidth), 8 otherwise (cache-resident operands / launches dominated by longer segments)
 template <int VEC, int LPR, bool EXACT, bool SUM, bool OFF32, bool PIPE = false, bool SHORT = false, bool EPI = false, int FB = 8, bool LISTS = false,
           typename TS = float, typename TD = float>
-__global__ __launch_bounds__(kBlock, (EXACT ? (LISTS ? (FB == 4 ? H2GCN_SHORT_FB4_MIN_WAVES : heavy_registers<VEC, LPR, SUM, OFF32, PIPE, true, EPI>() ? H2GCN_OFF64_HEAVY_MIN_WAVES : (LPR >= 32 ? H2GCN_WIDE_MIN_WAVES : kMinWavesPerSimd))
-                                                : SHORT ? (FB == 4 && !SUM ? H2GCN_SHORT_FB4_MIN_WAVES : H2GCN_SHORT_MIN_WAVES)
-                                                : heavy_registers<VEC, LPR, SUM, OFF32, PIPE, false, EPI>() ? H2GCN_OFF64_HEAVY_MIN_WAVES
-                                                : (LPR >= 32 ? H2GCN_WIDE_MIN_WAVES : kMinWavesPerSimd)) : 2)
-                                     - (bf16_one_wave_less<TS, VEC, LPR, SUM, OFF32, PIPE, SHORT, EPI, FB, LISTS>() ? 1 : 0)) void spmm_hops_kernel(const LaunchParams p) {
+__global__ __launch_bounds__(kBlock, (min_waves_per_simd<VEC, LPR, EXACT, SUM, OFF32, PIPE, SHORT, EPI, FB, LISTS, TS>())) void spmm_hops_kernel(const LaunchParams p) {
     static_assert(!LISTS || (EXACT && !SHORT && !PIPE && (LPR == 16 || LPR == 32)), "list-driven launches exist for 64- and 128-column slices");
     static_assert(EXACT || LPR == kWave, "column-tiled path uses the whole wave per row");
     __shared__ float partial[kWavesPerBlock][kMaxTileCols];
@@ -1337,76 +1340,86 @@ __global__ void repack_slice_major_kernel(const float* __restrict__ x, int64_t l
     }
 }
 
-// Which instantiation a launch runs (decided on the host: h2gcn_capi.hip, decide()).
-struct KernelChoice {
-    bool scalar128, lists, shortrow, pipe, gen, off32, fb4;
-    int slice;  // 256 / 128 / 64 columns; 0: generic column-tiled kernel (d < 4)
+// What a launch runs: decided on the host (h2gcn_capi.hip, decide(); reported by h2gcn_plan_schedule) and turned into an
+// instantiation by launch_spmm.
+struct Schedule {
+    bool exact;      // float4 slices (d >= 4); otherwise the generic column-tiled kernel
+    bool scalar128;  // variant 1 (d = 128): one neighbour per load instruction, scalar base addressing
+    bool pipe;       // tile walk with the index prefetch across segments
+    bool shortrow;   // in-tile short-row mode
+    bool lists;      // list-driven launch
+    bool fb4;        // shallow load batches of the in-tile short-row / list-driven walks
+    bool gen;        // general store (bias / ReLU / accumulate epilogue, width not a multiple of 4)
+    bool off32;      // 32-bit gather offsets
+    int slice;       // 256 / 128 / 64 columns; 0: generic column-tiled kernel (d < 4)
 };
 
-// The in-tile short-row kernels of one (SUM, slice, source / output type).  Instantiated in translation units of their own
-// (spmm_short.hip for fp32, spmm_bf16.hip for bf16): see spmm_short.hip.
-template <bool SUM, int LPR, typename TS, typename TD>
-void launch_in_tile_short_kernels(const LaunchParams& p, bool off32, bool fb4, dim3 grid, hipStream_t stream) {
+// One function template per walk family, each fanning out its runtime flags once; launch_spmm picks the family and the lane
+// geometry.  Where the kernels are compiled: the fp32 in-tile short-row ones in spmm_short.hip, every bf16 one in spmm_bf16.hip
+// (explicit instantiations there, `extern template` in h2gcn_capi.hip), the rest in h2gcn_capi.hip.  The caller checks
+// hipGetLastError.
+
+// Tile walk (and the long segments' workgroups): general store / 32-bit offsets / index prefetch.
+template <int VEC, int LPR, bool EXACT, bool SUM, typename TS, typename TD>
+void launch_tile_walk(const LaunchParams& p, const Schedule& k, dim3 grid, hipStream_t stream) {
     const dim3 block(kBlock);
-    if (off32 && fb4)
+    const bool pipe = EXACT && k.pipe;   // the column-tiled kernel has no index prefetch
+    if (k.gen && k.off32)
+        hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, EXACT, SUM, true, false, false, true, 8, false, TS, TD>), grid, block, 0, stream, p);
+    else if (k.gen)
+        hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, EXACT, SUM, false, false, false, true, 8, false, TS, TD>), grid, block, 0, stream, p);
+    else if (k.off32 && !pipe)
+        hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, EXACT, SUM, true, false, false, false, 8, false, TS, TD>), grid, block, 0, stream, p);
+    else if (!pipe)
+        hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, EXACT, SUM, false, false, false, false, 8, false, TS, TD>), grid, block, 0, stream, p);
+    else if constexpr (EXACT) {
+        if (k.off32)
+            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, EXACT, SUM, true, true, false, false, 8, false, TS, TD>), grid, block, 0, stream, p);
+        else
+            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, EXACT, SUM, false, true, false, false, 8, false, TS, TD>), grid, block, 0, stream, p);
+    }
+}
+
+// List-driven launch (64- / 128-column slices): 32-bit offsets / shallow load batches.
+template <int LPR, bool SUM, typename TS, typename TD>
+void launch_list_driven(const LaunchParams& p, const Schedule& k, dim3 grid, hipStream_t stream) {
+    const dim3 block(kBlock);
+    if (k.off32 && k.fb4)
+        hipLaunchKernelGGL((spmm_hops_kernel<4, LPR, true, SUM, true, false, false, false, 4, true, TS, TD>), grid, block, 0, stream, p);
+    else if (k.off32)
+        hipLaunchKernelGGL((spmm_hops_kernel<4, LPR, true, SUM, true, false, false, false, 8, true, TS, TD>), grid, block, 0, stream, p);
+    else if (k.fb4)
+        hipLaunchKernelGGL((spmm_hops_kernel<4, LPR, true, SUM, false, false, false, false, 4, true, TS, TD>), grid, block, 0, stream, p);
+    else
+        hipLaunchKernelGGL((spmm_hops_kernel<4, LPR, true, SUM, false, false, false, false, 8, true, TS, TD>), grid, block, 0, stream, p);
+}
+
+// In-tile short rows (64- / 128-column slices): 32-bit offsets / shallow fallback batches.
+template <int LPR, bool SUM, typename TS, typename TD>
+void launch_in_tile_short_rows(const LaunchParams& p, const Schedule& k, dim3 grid, hipStream_t stream) {
+    const dim3 block(kBlock);
+    if (k.off32 && k.fb4)
         hipLaunchKernelGGL((spmm_hops_kernel<4, LPR, true, SUM, true, false, true, false, 4, false, TS, TD>), grid, block, 0, stream, p);
-    else if (off32)
+    else if (k.off32)
         hipLaunchKernelGGL((spmm_hops_kernel<4, LPR, true, SUM, true, false, true, false, 8, false, TS, TD>), grid, block, 0, stream, p);
-    else if (fb4)
+    else if (k.fb4)
         hipLaunchKernelGGL((spmm_hops_kernel<4, LPR, true, SUM, false, false, true, false, 4, false, TS, TD>), grid, block, 0, stream, p);
     else
         hipLaunchKernelGGL((spmm_hops_kernel<4, LPR, true, SUM, false, false, true, false, 8, false, TS, TD>), grid, block, 0, stream, p);
 }
 
-// Every other launch (tile walk, list-driven walks, long segments, column-tiled kernel) of one (SUM, source / output type); the
-// caller routes in-tile short-row launches (k.shortrow) to launch_in_tile_short_kernels and checks hipGetLastError.
+// The kernel of a decision, for one direction (SUM: adjoint) and pair of element types.
 template <bool SUM, typename TS, typename TD>
-void launch_spmm_kernels(const LaunchParams& p, const KernelChoice& k, dim3 grid, hipStream_t stream) {
-    const dim3 block(kBlock);
-    const bool gen = k.gen, off32 = k.off32, pipe = k.pipe, short_fb4 = k.fb4;
-#define H2GCN_LAUNCH_LISTS(VEC, LPR)                                                                                              \
-    do {                                                                                                                          \
-        if (off32 && short_fb4)                                                                                                   \
-            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, true, SUM, true, false, false, false, 4, true, TS, TD>), grid, block, 0, stream, p);   \
-        else if (off32)                                                                                                           \
-            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, true, SUM, true, false, false, false, 8, true, TS, TD>), grid, block, 0, stream, p);   \
-        else if (short_fb4)                                                                                                       \
-            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, true, SUM, false, false, false, false, 4, true, TS, TD>), grid, block, 0, stream, p);  \
-        else                                                                                                                      \
-            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, true, SUM, false, false, false, false, 8, true, TS, TD>), grid, block, 0, stream, p);  \
-    } while (0)
-#define H2GCN_LAUNCH(VEC, LPR, EXACT)                                                                             \
-    do {                                                                                                          \
-        if (gen && off32)                                                                                         \
-            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, EXACT, SUM, true, false, false, true, 8, false, TS, TD>), grid, block, 0, stream, p);  \
-        else if (gen)                                                                                             \
-            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, EXACT, SUM, false, false, false, true, 8, false, TS, TD>), grid, block, 0, stream, p); \
-        else if (off32 && pipe && EXACT)                                                                               \
-            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, EXACT, SUM, true, true, false, false, 8, false, TS, TD>), grid, block, 0, stream, p);   \
-        else if (off32)                                                                                           \
-            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, EXACT, SUM, true, false, false, false, 8, false, TS, TD>), grid, block, 0, stream, p);  \
-        else if (pipe && EXACT)                                                                                   \
-            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, EXACT, SUM, false, true, false, false, 8, false, TS, TD>), grid, block, 0, stream, p);  \
-        else                                                                                                      \
-            hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, EXACT, SUM, false, false, false, false, 8, false, TS, TD>), grid, block, 0, stream, p); \
-    } while (0)
-    if (k.scalar128) {
-        H2GCN_LAUNCH(2, 64, true);  // one neighbour per load instruction, scalar base addressing
-    } else if (k.slice == 256) {
-        H2GCN_LAUNCH(4, 64, true);
-    } else if (k.slice == 128 && k.lists) {
-        H2GCN_LAUNCH_LISTS(4, 32);
-    } else if (k.slice == 64 && k.lists) {
-        H2GCN_LAUNCH_LISTS(4, 16);
-    } else if (k.slice == 128) {
-        H2GCN_LAUNCH(4, 32, true);
-    } else if (k.slice == 64) {
-        H2GCN_LAUNCH(4, 16, true);
-    } else {
-        H2GCN_LAUNCH(1, 64, false);  // d < 4: generic column-tiled path
-    }
-#undef H2GCN_LAUNCH
-#undef H2GCN_LAUNCH_LISTS
+void launch_spmm(const LaunchParams& p, const Schedule& k, dim3 grid, hipStream_t stream) {
+    if (k.shortrow && k.slice == 128) launch_in_tile_short_rows<32, SUM, TS, TD>(p, k, grid, stream);
+    else if (k.shortrow) launch_in_tile_short_rows<16, SUM, TS, TD>(p, k, grid, stream);
+    else if (k.scalar128) launch_tile_walk<2, 64, true, SUM, TS, TD>(p, k, grid, stream);
+    else if (k.slice == 256) launch_tile_walk<4, 64, true, SUM, TS, TD>(p, k, grid, stream);
+    else if (k.lists && k.slice == 128) launch_list_driven<32, SUM, TS, TD>(p, k, grid, stream);
+    else if (k.lists) launch_list_driven<16, SUM, TS, TD>(p, k, grid, stream);
+    else if (k.slice == 128) launch_tile_walk<4, 32, true, SUM, TS, TD>(p, k, grid, stream);
+    else if (k.slice == 64) launch_tile_walk<4, 16, true, SUM, TS, TD>(p, k, grid, stream);
+    else launch_tile_walk<1, 64, false, SUM, TS, TD>(p, k, grid, stream);
 }
 
 }  // namespace h2gcn

@@ -242,43 +242,30 @@ class HopPlan:
                 _bf16_layout("out", out, d, (out.stride(0), out.stride(1) if h_sel > 1 else d))
         if self.n_rows == 0:
             return out
+        if bias is not None:
+            _require(bias.dtype == torch.float32 and bias.device == self.device and bias.numel() == d and bias.is_contiguous(),
+                     f"bias must be a contiguous float32 [{d}] tensor on the plan's device")
         L = _capi.lib()
         mask = self._mask(hops)
-        if bf16:
-            # bf16 launches gather in place (no slice-major scratch copy)
-            with torch.cuda.device(self.device):
-                stream = torch.cuda.current_stream(self.device).cuda_stream
-                opts = None
-                if bias is not None or relu:
-                    if bias is not None:
-                        _require(bias.dtype == torch.float32 and bias.device == self.device and bias.numel() == d and bias.is_contiguous(),
-                                 f"bias must be a contiguous float32 [{d}] tensor on the plan's device")
-                    opts = _capi.LaunchOpts(struct_size=C.sizeof(_capi.LaunchOpts), flags=_capi.LAUNCH_RELU if relu else 0,
-                                            workspace=None, workspace_bytes=0, bias=bias.data_ptr() if bias is not None else None)
-                y_dtype = _capi.DTYPE_BF16 if out_dtype == torch.bfloat16 else _capi.DTYPE_F32
-                st = L.h2gcn_spmm_hops_bf16(self._handle, mask, C.c_void_p(x.data_ptr()), x.stride(0), d, y_dtype,
-                                            C.c_void_p(out.data_ptr()), out.stride(0), out.stride(1) if h_sel > 1 else d,
-                                            C.byref(opts) if opts is not None else None, C.c_void_p(stream))
-            _capi.check(st)
-            return out
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
             # scratch for the slice-major copy of X the library wants when X's row stride is a multiple of 1 KiB, when
             # its rows are wide and not line-aligned, or when d % 4 != 0 / X is not 16-byte addressable (0 bytes
-            # otherwise); a torch allocation, so it is stream-ordered and capturable in a hipGraph
-            ws_bytes = int(L.h2gcn_spmm_workspace_bytes(self._handle, mask, 0, C.c_void_p(x.data_ptr()), x.stride(0), 0, d)) if self.use_workspace else 0
+            # otherwise); a torch allocation, so it is stream-ordered and capturable in a hipGraph.  bf16 launches gather
+            # in place (no scratch copy)
+            ws_bytes = (int(L.h2gcn_spmm_workspace_bytes(self._handle, mask, 0, C.c_void_p(x.data_ptr()), x.stride(0), 0, d))
+                        if self.use_workspace and not bf16 else 0)
             ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device) if ws_bytes else None
             opts = None
             if ws is not None or bias is not None or relu:
-                if bias is not None:
-                    _require(bias.dtype == torch.float32 and bias.device == self.device and bias.numel() == d and bias.is_contiguous(),
-                             f"bias must be a contiguous float32 [{d}] tensor on the plan's device")
                 opts = _capi.LaunchOpts(struct_size=C.sizeof(_capi.LaunchOpts), flags=_capi.LAUNCH_RELU if relu else 0,
                                         workspace=ws.data_ptr() if ws is not None else None, workspace_bytes=ws_bytes,
                                         bias=bias.data_ptr() if bias is not None else None)
-            st = L.h2gcn_spmm_hops_opts_f32(self._handle, mask, C.c_void_p(x.data_ptr()), x.stride(0), d,
-                                            C.c_void_p(out.data_ptr()), out.stride(0), out.stride(1) if h_sel > 1 else d,
-                                            C.byref(opts) if opts is not None else None, C.c_void_p(stream))
+            fn, y_dtype = ((L.h2gcn_spmm_hops_bf16, (_capi.DTYPE_BF16 if out_dtype == torch.bfloat16 else _capi.DTYPE_F32,))
+                           if bf16 else (L.h2gcn_spmm_hops_opts_f32, ()))
+            st = fn(self._handle, mask, C.c_void_p(x.data_ptr()), x.stride(0), d, *y_dtype,
+                    C.c_void_p(out.data_ptr()), out.stride(0), out.stride(1) if h_sel > 1 else d,
+                    C.byref(opts) if opts is not None else None, C.c_void_p(stream))
         _capi.check(st)
         return out
 
@@ -320,33 +307,24 @@ class HopPlan:
         if self.n_cols == 0:
             return dx
         L = _capi.lib()
-        if bf16:
-            # bf16 launches gather in place (no slice-major scratch copy)
-            with torch.cuda.device(self.device):
-                stream = torch.cuda.current_stream(self.device).cuda_stream
-                ld_row, ld_hop = (grad.stride(0) if self.n_rows > 0 else h_sel * d), (grad.stride(1) if h_sel > 1 else d)
-                opts = (_capi.LaunchOpts(struct_size=C.sizeof(_capi.LaunchOpts), flags=_capi.LAUNCH_ACCUMULATE, workspace=None,
-                                         workspace_bytes=0, bias=None) if accumulate else None)
-                dx_dtype = _capi.DTYPE_BF16 if out_dtype == torch.bfloat16 else _capi.DTYPE_F32
-                st = L.h2gcn_spmm_hops_T_bf16(self._handle, self._mask(hops), C.c_void_p(grad.data_ptr()), ld_row, ld_hop, d,
-                                              dx_dtype, C.c_void_p(dx.data_ptr()), dx.stride(0) if self.n_cols > 1 else d,
-                                              C.byref(opts) if opts is not None else None, C.c_void_p(stream))
-            _capi.check(st)
-            return dx
+        mask = self._mask(hops)
+        # (a single hop's stride is only checked for its sign and, bf16, its parity: pass d)
+        ld_row, ld_hop = (grad.stride(0) if self.n_rows > 0 else h_sel * d), (grad.stride(1) if h_sel > 1 else d)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            mask = self._mask(hops)
-            ld_row, ld_hop = (grad.stride(0) if self.n_rows > 0 else h_sel * d), grad.stride(1)
-            # scratch: slice-major copy of the stacked gradient (same rules as the forward launch)
-            ws_bytes = int(L.h2gcn_spmm_workspace_bytes(self._handle, mask, 1, C.c_void_p(grad.data_ptr()), ld_row, ld_hop, d)) if self.use_workspace else 0
+            # scratch: slice-major copy of the stacked gradient (same rules as the forward launch; fp32 only)
+            ws_bytes = (int(L.h2gcn_spmm_workspace_bytes(self._handle, mask, 1, C.c_void_p(grad.data_ptr()), ld_row, ld_hop, d))
+                        if self.use_workspace and not bf16 else 0)
             opts = None
             if ws_bytes or accumulate:
                 ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self.device) if ws_bytes else None
                 opts = _capi.LaunchOpts(struct_size=C.sizeof(_capi.LaunchOpts), flags=_capi.LAUNCH_ACCUMULATE if accumulate else 0,
                                         workspace=ws.data_ptr() if ws is not None else None, workspace_bytes=ws_bytes, bias=None)
-            st = L.h2gcn_spmm_hops_T_opts_f32(self._handle, mask, C.c_void_p(grad.data_ptr()), ld_row, ld_hop, d,
-                                              C.c_void_p(dx.data_ptr()), dx.stride(0) if self.n_cols > 1 else d,
-                                              C.byref(opts) if opts is not None else None, C.c_void_p(stream))
+            fn, dx_dtype = ((L.h2gcn_spmm_hops_T_bf16, (_capi.DTYPE_BF16 if out_dtype == torch.bfloat16 else _capi.DTYPE_F32,))
+                            if bf16 else (L.h2gcn_spmm_hops_T_opts_f32, ()))
+            st = fn(self._handle, mask, C.c_void_p(grad.data_ptr()), ld_row, ld_hop, d, *dx_dtype,
+                    C.c_void_p(dx.data_ptr()), dx.stride(0) if self.n_cols > 1 else d,
+                    C.byref(opts) if opts is not None else None, C.c_void_p(stream))
         _capi.check(st)
         return dx
 
