@@ -216,17 +216,31 @@ class _FusedPropagation(torch.autograd.Function):
     (row stride ``W``) and writes ``r_k`` into its own slot through the kernel's output strides -- no stack, no
     flatten, no concat copy.  Backward walks the rounds in reverse with the adjoint launch, reading the incoming
     gradient slots in place.
+
+    ``dtype=torch.bfloat16``: the buffer is bf16.  ``r0`` (fp32) is rounded into its slot (nearest even) and every round is
+    the bf16 -> bf16 launch (fp32 accumulation, one rounding at the store) from one slot to the next.  The backward receives
+    the buffer's gradient ``g`` in bf16 and walks the rounds ``k = K .. 1`` with this ORDER OF ROUNDINGS (the specification;
+    ``g_K`` is the slot of ``r_K`` in ``g``)::
+
+        t       = spmm_t(g_k)  accumulated and returned in fp32
+        t      += slot_{k-1}(g) widened exactly to fp32
+        g_{k-1} = t rounded to bf16 (nearest even)   for k > 1
+        d r_0   = t, left in fp32                    for k = 1     (the gradient handed to the embedding layer is fp32)
+
+    i.e. one rounding per round on the way down and none on the last.  ``private_grad`` (the in-place accumulate) applies
+    to fp32 only: a bf16 slot cannot be accumulated into.
     """
 
     @staticmethod
     def forward(ctx, r0: torch.Tensor, plan: HopPlan, rounds: int, out: Optional[torch.Tensor] = None, reuse: bool = False,
-                private_grad: bool = False):
+                private_grad: bool = False, dtype: Optional[torch.dtype] = None):
         """``private_grad``: the caller guarantees that the gradient tensor this node's backward receives is a temporary
         nobody else reads (see :func:`fused_propagation`).  ``out``: a caller-owned ``[N, W]`` contiguous buffer to fill instead of a fresh one.  ``reuse``: ``out`` ALREADY
         holds the propagation of this very ``r0`` (see :func:`fused_propagation`) -- nothing is computed, the buffer only
         enters the autograd graph (the backward needs none of the forward's values: the rounds are linear)."""
         n, w0 = r0.shape
         H = plan.n_hops
+        dtype = torch.float32 if dtype is None else dtype
         widths = [w0 * H ** k for k in range(rounds + 1)]
         total = sum(widths)
         # column offsets: r_K first, then r_0 .. r_{K-1}
@@ -237,10 +251,10 @@ class _FusedPropagation(torch.autograd.Function):
             off[k] = pos
             pos += widths[k]
         if out is None:
-            buf = concat_buffer(n, total, r0.device)
+            buf = concat_buffer(n, total, r0.device, dtype)
         else:
-            if out.shape != (n, total) or out.dtype != torch.float32 or out.device != r0.device or not out.is_contiguous():
-                raise ValueError(f"fused_propagation: out must be a contiguous float32 [{n}, {total}] tensor on {r0.device}")
+            if out.shape != (n, total) or out.dtype != dtype or out.device != r0.device or not out.is_contiguous():
+                raise ValueError(f"fused_propagation: out must be a contiguous {str(dtype).replace('torch.', '')} [{n}, {total}] tensor on {r0.device}")
             buf = out.view(n, total)   # a new tensor object on the caller's storage: autograd marks IT as this node's output
         if not reuse:
             buf[:, off[0]:off[0] + w0].copy_(r0)
@@ -249,7 +263,8 @@ class _FusedPropagation(torch.autograd.Function):
                 dst = buf[:, off[k]:off[k] + widths[k]].unflatten(1, (H, widths[k - 1]))
                 plan.spmm(src, out=dst)
         ctx.plan, ctx.rounds, ctx.widths, ctx.off = plan, rounds, widths, off
-        ctx.private_grad = bool(private_grad)
+        ctx.private_grad = bool(private_grad) and dtype == torch.float32
+        ctx.bf16 = dtype == torch.bfloat16
         return buf
 
     @staticmethod
@@ -257,6 +272,15 @@ class _FusedPropagation(torch.autograd.Function):
         plan, K, widths, off = ctx.plan, ctx.rounds, ctx.widths, ctx.off
         H = plan.n_hops
         g_k = grad[:, off[K]:off[K] + widths[K]]  # d r_K: a view, read in place by the adjoint launch
+        if ctx.bf16:   # the rounding order of the class docstring
+            if grad.stride(1) != 1 or grad.stride(0) % 2 or grad.data_ptr() % 4:
+                grad = grad.contiguous()
+                g_k = grad[:, off[K]:off[K] + widths[K]]
+            for k in range(K, 0, -1):
+                t = plan.spmm_t(g_k.unflatten(1, (H, widths[k - 1])), out_dtype=torch.float32)
+                t += grad[:, off[k - 1]:off[k - 1] + widths[k - 1]]
+                g_k = t.to(torch.bfloat16) if k > 1 else t
+            return g_k, None, None, None, None, None, None
         # The adjoint of round k is ADDED to the slot of r_{k-1} inside the incoming gradient itself (the library's
         # accumulate flag: the `+=` rides on the adjoint's store) -- but ONLY when the caller has vouched that this tensor is a
         # temporary of its own (`private_grad`: models.H2GCN sets it when the buffer's sole consumer is a layer whose
@@ -276,20 +300,22 @@ class _FusedPropagation(torch.autograd.Function):
                 g_prev = plan.spmm_t(g_k.unflatten(1, (H, widths[k - 1])))
                 g_prev += slot
                 g_k = g_prev
-        return g_k, None, None, None, None, None
+        return g_k, None, None, None, None, None, None
 
 
-def concat_buffer(n_rows: int, width: int, device) -> torch.Tensor:
-    """The ``[n_rows, width]`` fp32 concat buffer, contiguous.  (Padding its row stride to a cache line was tried in round
+def concat_buffer(n_rows: int, width: int, device, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """The ``[n_rows, width]`` concat buffer (fp32, or bf16 for a bf16 propagation), contiguous.  (Padding its row stride to a cache line was tried in round
     3 and dropped: the hop launches gain < 2 % -- the slots inside a row still start off-line, so they take the
     scratch-copy schedule either way -- while the stock dropout / classifier kernels that consume the buffer fall off
     their vectorised paths on a non-contiguous view: +2.8 ms per products-scale step at ``--hidden 100``,
     ``profiles/r03_train_step_hidden100.txt``.)"""
-    return torch.empty((n_rows, width), dtype=torch.float32, device=device)
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError(f"concat_buffer: dtype must be float32 or bfloat16, got {dtype}")
+    return torch.empty((n_rows, width), dtype=dtype, device=device)
 
 
 def fused_propagation(plan: HopPlan, r0: torch.Tensor, rounds: int, out: Optional[torch.Tensor] = None,
-                      reuse: bool = False, private_grad: bool = False) -> torch.Tensor:
+                      reuse: bool = False, private_grad: bool = False, dtype: Optional[torch.dtype] = None) -> torch.Tensor:
     """``[r_K | r_0 | ... | r_{K-1}]`` for ``rounds = K`` aggregation rounds, without intermediate copies.
 
     ``out`` / ``reuse``: the propagation is a deterministic function of ``(plan, r0)``, and an epoch of the reference evaluates
@@ -301,16 +327,29 @@ def fused_propagation(plan: HopPlan, r0: torch.Tensor, rounds: int, out: Optiona
 
     ``private_grad``: promise that the gradient arriving for the returned buffer is a temporary no one else holds; the
     backward then accumulates the rounds' adjoints into its slots in place (bit-identical, one pass and one tensor less per
-    round).  Leave it off when the buffer's gradient may be observed (hooks, ``retain_grad``, an explicit ``backward(G)``)."""
+    round).  Leave it off when the buffer's gradient may be observed (hooks, ``retain_grad``, an explicit ``backward(G)``).
+
+    ``dtype``: ``None`` / ``torch.float32`` (default) or ``torch.bfloat16`` -- the dtype of the buffer; ``r0`` stays float32.
+    With bfloat16 every hop launch moves half the bytes (fp32 accumulation, one rounding per slot); the gradient of the
+    buffer is bfloat16 and the gradient returned for ``r0`` float32 (rounding order: :class:`_FusedPropagation`).  ``r0``
+    needs an even width (bf16 rows are read in dwords)."""
     if rounds < 1:
         raise ValueError("rounds must be >= 1")
+    if dtype not in (None, torch.float32, torch.bfloat16):
+        raise ValueError(f"fused_propagation: dtype must be float32 or bfloat16, got {dtype}")
+    if dtype == torch.bfloat16:
+        if r0.dtype != torch.float32:
+            raise ValueError(f"fused_propagation: r0 must be float32 (it is rounded into the bfloat16 buffer), got {r0.dtype}")
+        if r0.dim() == 2 and r0.shape[1] % 2:
+            raise ValueError(f"fused_propagation: a bfloat16 buffer needs an even embedding width, got {r0.shape[1]} "
+                             "(bf16 rows are read in dwords: pad the hidden width to an even number or use float32)")
     if r0.dim() != 2 or r0.shape[0] != plan.n_cols or plan.n_rows != plan.n_cols:
         raise ValueError(f"r0 must be [{plan.n_cols}, d] and the hop matrices square")
     if reuse and out is None:
         raise ValueError("fused_propagation: reuse=True needs the buffer that holds the propagation (out=)")
     if r0.requires_grad and torch.is_grad_enabled():
-        return _FusedPropagation.apply(r0, plan, rounds, out, reuse, private_grad)
-    return _FusedPropagation.forward(_NoCtx(), r0, plan, rounds, out, reuse)
+        return _FusedPropagation.apply(r0, plan, rounds, out, reuse, private_grad, dtype)
+    return _FusedPropagation.forward(_NoCtx(), r0, plan, rounds, out, reuse, False, dtype)
 
 
 class _NoCtx:
@@ -328,7 +367,9 @@ def _dd_workspace(n: int, k: int, c: int, device) -> torch.Tensor:
 
 class _DropoutDenseFn(torch.autograd.Function):
     """``Z = (X .* M / keep) @ W + b`` and its gradients on the library's fp32-MFMA kernels; the mask ``M`` is a counter-based
-    function of (seed, step, row, column), recomputed in the backward kernels instead of being stored."""
+    function of (seed, step, row, column), recomputed in the backward kernels instead of being stored.  ``X`` float32 or
+    bfloat16 (the ``_bf16`` entry points: ``Z`` / ``dW`` float32 and bit-identical to the float32 call on ``X.float()``, ``dX``
+    bfloat16)."""
 
     @staticmethod
     def forward(ctx, x, kernel, bias, keep_prob, seed, step_dev):
@@ -342,7 +383,8 @@ class _DropoutDenseFn(torch.autograd.Function):
         ws = _dd_workspace(n, k, c, x.device)
         with torch.cuda.device(x.device):
             stream = torch.cuda.current_stream(x.device).cuda_stream
-            _capi.check(_capi.lib().h2gcn_dropout_dense_f32(
+            fn = _capi.lib().h2gcn_dropout_dense_bf16 if x.dtype == torch.bfloat16 else _capi.lib().h2gcn_dropout_dense_f32
+            _capi.check(fn(
                 C.c_void_p(x.data_ptr()), x.stride(0), n, k, C.c_void_p(w.data_ptr()), c,
                 C.c_void_p(bias.data_ptr()) if bias is not None else None, float(keep_prob), int(seed),
                 C.c_void_p(step_dev.data_ptr()) if step_dev is not None else None, C.c_void_p(z.data_ptr()), z.stride(0),
@@ -361,15 +403,19 @@ class _DropoutDenseFn(torch.autograd.Function):
         c = w.shape[1]
         g = g.contiguous()
         need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        dx = torch.empty((n, k), dtype=torch.float32, device=x.device) if need_dx else None
+        bf16 = x.dtype == torch.bfloat16
+        # (a bf16 dX needs an even row stride: an odd K gets one padding column)
+        dx = torch.empty((n, k + (k % 2 if bf16 else 0)), dtype=x.dtype, device=x.device)[:, :k] if need_dx else None
         dw = torch.empty((k, c), dtype=torch.float32, device=x.device) if need_dw else None
         if need_dx or need_dw:
             ws = _dd_workspace(n, k, c, x.device)
             with torch.cuda.device(x.device):
                 stream = torch.cuda.current_stream(x.device).cuda_stream
-                _capi.check(_capi.lib().h2gcn_dropout_dense_backward_f32(
+                fn, dx_dtype = ((_capi.lib().h2gcn_dropout_dense_backward_bf16, (_capi.DTYPE_BF16,)) if bf16
+                                else (_capi.lib().h2gcn_dropout_dense_backward_f32, ()))
+                _capi.check(fn(
                     C.c_void_p(x.data_ptr()), x.stride(0), n, k, C.c_void_p(w.data_ptr()), c, C.c_void_p(g.data_ptr()), g.stride(0),
-                    ctx.keep_prob, ctx.seed, C.c_void_p(step.data_ptr()) if ctx.has_step else None,
+                    ctx.keep_prob, ctx.seed, C.c_void_p(step.data_ptr()) if ctx.has_step else None, *dx_dtype,
                     C.c_void_p(dx.data_ptr()) if need_dx else None, dx.stride(0) if need_dx else k,
                     C.c_void_p(dw.data_ptr()) if need_dw else None, C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(stream)))
         db = g.sum(0) if ctx.has_bias and ctx.needs_input_grad[2] else None
@@ -382,7 +428,9 @@ class DropoutDense(torch.nn.Module):
     direction: the dropout mask is drawn from a counter-based generator inside the fp32-MFMA product kernels of
     ``csrc/classifier.hip`` (forward, ``dX``, ``dW``) instead of being materialised by a pass of its own.  Same parameters
     as the unfused pair (``kernel [K, units]``, optional ``bias``); in evaluation the mask is off and the layer is the plain
-    product.  Inputs the kernels do not cover (CPU tensors, ``units > 64``, non-fp32) take the stock two-op path.
+    product.  A bfloat16 input (the buffer of a bfloat16 propagation: CUDA, 2-D, even row stride) takes the ``_bf16`` entry
+    points: float32 logits, float32 ``dW``, a bfloat16 ``dX``.  Inputs the kernels do not cover (CPU tensors, ``units > 64``,
+    other dtypes or layouts) take the stock two-op path, upcast to float32 first -- correct, and the slow path.
 
     The mask stream differs from torch's (and from TensorFlow's, which nothing can reproduce): one mask per training
     forward, keyed by ``(seed, step)``; ``step`` lives in a device counter bumped by a stream-ordered op, so a replayed
@@ -411,9 +459,16 @@ class DropoutDense(torch.nn.Module):
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         training = self.training and self.drop_prob > 0.0
-        fused_ok = (x.is_cuda and x.dim() == 2 and x.dtype == torch.float32 and self.kernel.shape[1] <= 64
+        fused_ok = (x.is_cuda and x.dim() == 2 and x.dtype in (torch.float32, torch.bfloat16) and self.kernel.shape[1] <= 64
                     and (x.shape[1] <= 1 or x.stride(1) == 1) and x.stride(0) >= x.shape[1])
+        if fused_ok and x.dtype == torch.bfloat16:
+            from . import _capi
+            if not _capi.has("h2gcn_dropout_dense_bf16"):
+                raise RuntimeError(f"{_capi.library_path()} predates the bf16 classifier (h2gcn_dropout_dense_bf16): rebuild it")
+            fused_ok = x.stride(0) % 2 == 0 and x.data_ptr() % 4 == 0
         if not fused_ok:
+            if x.dtype == torch.bfloat16:
+                x = x.to(self.kernel.dtype)
             if training:
                 x = torch.nn.functional.dropout(x, self.drop_prob, True)
             y = x @ self.kernel

@@ -46,6 +46,10 @@ def add_subparser_args(parser):
     g.add_argument("--no_fused_classifier", action="store_true",
                    help="run `D<rate>` followed by a dense layer as the stock dropout + matmul pair instead of the library's "
                         "one-pass dropout+Dense kernels (csrc/classifier.hip)")
+    g.add_argument("--embedding_dtype", choices=sorted(EMBEDDING_DTYPES), default="float32",
+                   help="dtype of the propagated embeddings (the concat buffer of the fused propagation and the input of the layer "
+                        "that consumes it): bfloat16 halves the bytes of every hop launch and of the classifier's passes; "
+                        "parameters, optimizer state, logits, loss and all accumulation stay float32 (default: %(default)s)")
     g.add_argument("--sparse_dropout_at_eval", action="store_true",
                    help="reproduce the reference's SparseDropout, which Keras never switches off (it drops sparse feature "
                         "values during evaluation as well); default: inactive in evaluation like every other dropout")
@@ -53,6 +57,9 @@ def add_subparser_args(parser):
     g.add_argument("--no_hipgraph", action="store_true", dest="_no_hipgraph",
                    help="run every step eagerly instead of replaying captured hipGraphs")
     parser.function_hooks["argparse"].append(argparse_callback)
+
+
+EMBEDDING_DTYPES = {"float32": torch.float32, "bfloat16": torch.bfloat16}
 
 
 def argparse_callback(args):
@@ -108,7 +115,8 @@ def initialize_model(args, layer_setups, optimizer, lr, l2_regularize_weight, ea
                   sparse_input=not dense_features, l2_regularize_weight=l2_regularize_weight,
                   sparse_dropout_at_eval=getattr(args, "sparse_dropout_at_eval", False),
                   fused_classifier=not getattr(args, "no_fused_classifier", False),
-                  reuse_propagation=not getattr(args, "no_propagation_reuse", False)).to(device)
+                  reuse_propagation=not getattr(args, "no_propagation_reuse", False),
+                  embedding_dtype=EMBEDDING_DTYPES[getattr(args, "embedding_dtype", "float32")]).to(device)
     sharded = _is_sharded()
     if sharded:  # replicas must start identical whatever the seeding on each rank (e.g. --random_seed 0)
         for p_ in model.parameters():
@@ -194,7 +202,7 @@ def initialize_model(args, layer_setups, optimizer, lr, l2_regularize_weight, ea
     @torch.no_grad()
     def predict_step(adj, adj_hops, features, **kwargs):
         model.eval()
-        return model(adj, features, adj_hops)
+        return model(adj, features, adj_hops).float()   # (a no-op on float32 logits)
 
     @torch.no_grad()
     def embed_step(adj, adj_hops, features, **kwargs):
@@ -472,6 +480,8 @@ class Dense(torch.nn.Module):
         self.bias = torch.nn.Parameter(torch.zeros(units)) if use_bias else None
 
     def forward(self, x):
+        if x.dtype == torch.bfloat16:   # the buffer of a bfloat16 propagation on the stock path: upcast (correct, and slow)
+            x = x.to(self.kernel.dtype)
         y = x @ self.kernel
         return y if self.bias is None else y + self.bias
 
@@ -492,12 +502,21 @@ class H2GCN(torch.nn.Module):
 
     Dispatch kinds (``:314-325``): concat/slice layers receive the tag store, ``G`` layers receive
     ``(adjhops, inputs)``, everything else ``(inputs)``; an output tagged ``T<name>`` is stored for later
-    concats (``:339-341``).  Feature widths are tracked statically (keras builds lazily)."""
+    concats (``:339-341``).  Feature widths are tracked statically (keras builds lazily).
+
+    ``embedding_dtype=torch.bfloat16``: the fused propagation block runs on a bfloat16 concat buffer (``layers.fused_propagation``
+    with ``dtype=``) and the layer that consumes the buffer reads it in bfloat16 (``DropoutDense``: the ``_bf16`` classifier
+    kernels; a plain ``Dense`` upcasts -- the slow path).  Parameters, logits, loss and every accumulation stay float32.  What
+    this does not cover is refused with a ``ValueError``, never run in float32 behind the caller's back: a network set-up
+    without a fusable block, an odd width at the block's input, row-partitioned runs."""
 
     def __init__(self, layer_setups, input_dim: int, n_hops: int = 2, sparse_input: bool = True,
                  l2_regularize_weight: float = 0.0, sparse_dropout_at_eval: bool = False, fused_classifier: bool = True,
-                 reuse_propagation: bool = True):
+                 reuse_propagation: bool = True, embedding_dtype: torch.dtype = torch.float32):
         super().__init__()
+        if embedding_dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError(f"embedding_dtype must be torch.float32 or torch.bfloat16, got {embedding_dtype}")
+        self.embedding_dtype = embedding_dtype
         self.l2 = float(l2_regularize_weight)
         self.layer_objs = torch.nn.ModuleList()
         self.kinds = []
@@ -586,6 +605,18 @@ class H2GCN(torch.nn.Module):
                 tag_width[tag] = width
         self.output_width = width
         self.fused = self._find_fusable_block(layer_setups, n_hops)
+        if embedding_dtype == torch.bfloat16:
+            if self.fused is None:
+                raise ValueError("embedding_dtype=bfloat16 needs the fused propagation block (`...-T1-G-V-T2-G-V-C1-C2-...`: unfiltered "
+                                 "G-V rounds with tagged inputs followed by their concats); this network set-up has none -- change "
+                                 "the set-up or use --embedding_dtype float32")
+            w0 = tag_width[self.fused[3][0]]
+            if w0 % 2:
+                raise ValueError(f"embedding_dtype=bfloat16 needs an even width at the propagation's input, got {w0} (bf16 rows are "
+                                 "read in dwords): choose an even --hidden or use --embedding_dtype float32")
+            if _is_sharded():
+                raise ValueError("embedding_dtype=bfloat16 does not cover row-partitioned runs (the exchange is float32): run on "
+                                 "one GPU or use --embedding_dtype float32")
         # Propagation reuse (see layers.fused_propagation): an epoch is train_step then test_step, so the training forward
         # of epoch e+1 recomputes exactly what the evaluation of epoch e has just produced -- provided every layer in front of
         # the propagation behaves the same in both modes (no dropout there; H2GCN's default `M64-R-T1-G-V-...-D0.5-MO` has its
@@ -616,9 +647,9 @@ class H2GCN(torch.nn.Module):
 
     def _propagation_buffer(self, n: int, width: int, device) -> torch.Tensor:
         b = self._prop_buf
-        if b is None or b.shape != (n, width) or b.device != device:
+        if b is None or b.shape != (n, width) or b.device != device or b.dtype != self.embedding_dtype:
             with torch.inference_mode(False):   # an ordinary tensor even if the first evaluation runs under inference_mode
-                self._prop_buf, self._prop_key = L.concat_buffer(n, width, device), None
+                self._prop_buf, self._prop_key = L.concat_buffer(n, width, device, self.embedding_dtype), None
         return self._prop_buf
 
     @staticmethod
@@ -666,13 +697,21 @@ class H2GCN(torch.nn.Module):
             if ind < execute_after:
                 continue
             can_fuse = hasattr(adjhops, "fused_propagation") or (adjhops is not None and adjhops.n_rows == adjhops.n_cols)
+            bf16 = self.embedding_dtype == torch.bfloat16
+            if bf16 and ind == self.fused[0]:   # what bfloat16 mode does not cover is refused, never run in float32 instead
+                if hasattr(adjhops, "fused_propagation"):
+                    raise ValueError("embedding_dtype=bfloat16 does not cover row-partitioned hops (ShardedHops): run on one GPU "
+                                     "or build the model with embedding_dtype=torch.float32")
+                if not (fuse and can_fuse) or ind < return_before < self.fused[1]:
+                    raise ValueError("embedding_dtype=bfloat16 runs the fused propagation block only (square hop matrices, fuse=True, "
+                                     "no stop inside the block): build the model with embedding_dtype=torch.float32 for this call")
             if fuse and can_fuse and self.fused is not None and ind == self.fused[0] and not (ind < return_before < self.fused[1]):
                 # concat-free propagation: layers fused[0] .. fused[1]-1 in one go (row-sharded runs: the shard's
                 # rows of the same buffer, one exchange per round)
                 _, end, K, tags = self.fused
                 sharded_hops = hasattr(adjhops, "fused_propagation")
                 propagate = adjhops.fused_propagation if sharded_hops else functools.partial(
-                    L.fused_propagation, adjhops, private_grad=self._buffer_grad_is_private(end))
+                    L.fused_propagation, adjhops, private_grad=self._buffer_grad_is_private(end), **({"dtype": torch.bfloat16} if bf16 else {}))
                 if self.reuse_propagation and inputs.is_cuda:
                     # (row-partitioned runs: every rank takes the same branch -- the decision depends only on the call
                     # sequence, which is the same on all ranks)
@@ -685,7 +724,7 @@ class H2GCN(torch.nn.Module):
                     # training loop can never adopt a buffer computed from older weights; `note_update()` stays as the
                     # explicit form for anything that writes parameters behind torch's back
                     versions = tuple(p._version for p in self.parameters())
-                    key = (self._weights_tag, versions, id(adjhops), getattr(plan_, "values_version", 0), feat_key, tuple(inputs.shape), K)
+                    key = (self._weights_tag, versions, id(adjhops), getattr(plan_, "values_version", 0), feat_key, tuple(inputs.shape), K, self.embedding_dtype)
                     if not torch.is_grad_enabled():          # evaluation: fill the persistent buffer
                         self._prop_key = None
                         inputs = propagate(inputs, K, out=buf)

@@ -422,6 +422,30 @@ int h2gcn_dropout_dense_backward_f32(const float* X_dev, int64_t ldx, int64_t n_
                                      const float* G_dev, int64_t ldg, float keep_prob, uint64_t seed, const int64_t* step_dev,
                                      float* dX_dev, int64_t lddx, float* dW_dev, void* workspace_dev, size_t workspace_bytes,
                                      void* stream);
+/*
+ * The same two calls on a bf16 X (an additive extension of ABI 5: look the symbols up before calling a build that may predate
+ * them).  X is the bf16 concat buffer a bf16 propagation leaves behind (h2gcn_spmm_hops_bf16 with a bf16 output); W, bias, G,
+ * Z, dW and every accumulation stay fp32; dX is written as dx_dtype = H2GCN_DTYPE_BF16 or H2GCN_DTYPE_F32.  Same argument
+ * order as the _f32 pair (dx_dtype in front of dX_dev), strides in ELEMENTS, the workspace of
+ * h2gcn_dropout_dense_workspace_bytes, the same h2gcn_dropout_dense_small_rows bound.
+ * Arithmetic: a lane loads four bf16 with one 8-byte load and widens them exactly (bf16 -> fp32 is a 16-bit shift); from there
+ * on the kernels ARE the fp32 ones -- v_mfma_f32_16x16x4_f32, the same mask generator, the same placement of the 1 / keep_prob
+ * scale, the same summation orders and fixed-order dW reduction.  Hence:
+ *   Z and dW   bit-identical to the _f32 entry points called on the upcast X (X.float())
+ *   dX fp32    bit-identical to the _f32 call;   dX bf16   that value rounded to nearest even (torch's .to(torch.bfloat16)),
+ *              after mask and scale, two at a time (v_cvt_pk_bf16_f32), one 8-byte store per lane and row tile
+ * Layout: X (and a bf16 dX) needs a 4-byte aligned base and an even row stride, so that every 8-byte access is dword-aligned; K
+ * may be odd (the tail of a row is loaded and stored by element).  Arguments are validated before the device is touched: a NULL
+ * operand, a dx_dtype other than the two above, an odd ldx / lddx or a misaligned base give H2GCN_ERR_INVALID_ARGUMENT with a
+ * message that names the argument.  hipGraph capture: no condition (these launches allocate nothing).
+ */
+int h2gcn_dropout_dense_bf16(const uint16_t* X_dev, int64_t ldx, int64_t n_rows, int32_t k, const float* W_dev, int32_t c,
+                             const float* bias_dev, float keep_prob, uint64_t seed, const int64_t* step_dev,
+                             float* Z_dev, int64_t ldz, void* workspace_dev, size_t workspace_bytes, void* stream);
+int h2gcn_dropout_dense_backward_bf16(const uint16_t* X_dev, int64_t ldx, int64_t n_rows, int32_t k, const float* W_dev, int32_t c,
+                                      const float* G_dev, int64_t ldg, float keep_prob, uint64_t seed, const int64_t* step_dev,
+                                      int dx_dtype, void* dX_dev, int64_t lddx, float* dW_dev, void* workspace_dev,
+                                      size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Masked softmax cross-entropy and masked accuracy (reference h2gcn/models/_metrics.py:8-25; called per mask by train_step /

@@ -1,6 +1,16 @@
-"""Per-entry-point times of the dropout + dense kernels (csrc/classifier.hip) at the products shape, through the C ABI:
-forward, backward-data only, backward-weights only.  usage: python tools/classifier_kernels.py [K] [C] [N] [keep_prob]"""
+"""Per-entry-point times of the dropout + dense kernels (csrc/classifier.hip, classifier_bf16.hip) at the products shape, through
+the C ABI: forward, backward-data only, backward-weights only.
+usage: python tools/classifier_kernels.py [K] [C] [N] [keep_prob] [--dtype f32|bf16|both] [--against OTHER_LIB.so] [--reps R] [--rounds Q]
+  --dtype    element type of X and dX (default f32; `both`: fp32 and bf16 take turns in one process)
+  --against  also time the fp32 entry points of another build of the library (e.g. build/ab/lib_parent.so from
+             tools/build_ab_lib.sh), taking turns with this one in the same process
+Every configuration is timed in Q rounds (default 2; the spread between the rounds of one configuration is the noise) of R
+launches (default 12), each launch between its own pair of device events, after 3 warm-up launches; the median per round is
+printed."""
+import argparse
 import ctypes as C
+import os
+import statistics
 import sys
 from pathlib import Path
 
@@ -9,21 +19,38 @@ import torch
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from h2gcn_amd import _capi
 
-k = int(sys.argv[1]) if len(sys.argv) > 1 else 448
-c = int(sys.argv[2]) if len(sys.argv) > 2 else 47
-n = int(sys.argv[3]) if len(sys.argv) > 3 else 2_400_000
-keep = float(sys.argv[4]) if len(sys.argv) > 4 else 0.5
+ap = argparse.ArgumentParser()
+ap.add_argument("shape", nargs="*", default=[])
+ap.add_argument("--dtype", choices=["f32", "bf16", "both"], default="f32")
+ap.add_argument("--against", default=None)
+ap.add_argument("--reps", type=int, default=12)
+ap.add_argument("--rounds", type=int, default=2)
+a = ap.parse_args()
+k = int(a.shape[0]) if len(a.shape) > 0 else 448
+c = int(a.shape[1]) if len(a.shape) > 1 else 47
+n = int(a.shape[2]) if len(a.shape) > 2 else 2_400_000
+keep = float(a.shape[3]) if len(a.shape) > 3 else 0.5
 dev = torch.device("cuda:0")
 lib = _capi.lib()
-import os
+libs = {"this build": lib}
+if a.against:
+    other = C.CDLL(a.against)
+    for name in ("h2gcn_dropout_dense_f32", "h2gcn_dropout_dense_backward_f32", "h2gcn_dropout_dense_small_rows"):
+        getattr(other, name).restype = getattr(lib, name).restype
+        getattr(other, name).argtypes = getattr(lib, name).argtypes
+    libs[Path(a.against).name] = other
 if os.environ.get("H2GCN_CLS_SMALL_ROWS") is not None:      # rows at or below which the small-operand kernels serve the call (0: never)
-    lib.h2gcn_dropout_dense_small_rows(int(os.environ["H2GCN_CLS_SMALL_ROWS"]))
-x = torch.randn((n, k), device=dev)
+    for L in libs.values():
+        L.h2gcn_dropout_dense_small_rows(int(os.environ["H2GCN_CLS_SMALL_ROWS"]))
+dtypes = {"f32": ["f32"], "bf16": ["bf16"], "both": ["f32", "bf16"]}[a.dtype]
+tdt = {"f32": torch.float32, "bf16": torch.bfloat16}
+x32 = torch.randn((n, k), device=dev)
+x = {d: (x32 if d == "f32" else x32.to(torch.bfloat16)) for d in set(dtypes) | ({"f32"} if a.against else set())}
+dx = {d: torch.empty((n, k), device=dev, dtype=tdt[d]) for d in x}
 w = torch.randn((k, c), device=dev) * 0.05
 b = torch.randn((c,), device=dev)
 g = torch.randn((n, c), device=dev)
 z = torch.empty((n, c), device=dev)
-dx = torch.empty((n, k), device=dev)
 dw = torch.empty((k, c), device=dev)
 ws = torch.empty(int(lib.h2gcn_dropout_dense_workspace_bytes(n, k, c)), dtype=torch.uint8, device=dev)
 step = torch.zeros((), dtype=torch.int64, device=dev)
@@ -31,30 +58,40 @@ stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
 P = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None
 
 
-def fwd():
-    _capi.check(lib.h2gcn_dropout_dense_f32(P(x), k, n, k, P(w), c, P(b), keep, 7, P(step), P(z), c, P(ws), ws.numel(), stream))
+def fwd(L, d):
+    fn = L.h2gcn_dropout_dense_bf16 if d == "bf16" else L.h2gcn_dropout_dense_f32
+    _capi.check(fn(P(x[d]), k, n, k, P(w), c, P(b), keep, 7, P(step), P(z), c, P(ws), ws.numel(), stream))
 
 
-def bwd(want_dx, want_dw):
-    _capi.check(lib.h2gcn_dropout_dense_backward_f32(P(x), k, n, k, P(w), c, P(g), c, keep, 7, P(step), P(dx) if want_dx else None, k,
-                                                     P(dw) if want_dw else None, P(ws), ws.numel(), stream))
+def bwd(L, d, want_dx, want_dw):
+    fn, extra = (L.h2gcn_dropout_dense_backward_bf16, (_capi.DTYPE_BF16,)) if d == "bf16" else (L.h2gcn_dropout_dense_backward_f32, ())
+    _capi.check(fn(P(x[d]), k, n, k, P(w), c, P(g), c, keep, 7, P(step), *extra, P(dx[d]) if want_dx else None, k,
+                   P(dw) if want_dw else None, P(ws), ws.numel(), stream))
 
 
-def timed(fn, reps=10):
+def timed(fn, reps):
     for _ in range(3):
         fn()
     torch.cuda.synchronize()
-    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    s.record()
-    for _ in range(reps):
+    ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(reps)]
+    for s, e in ev:
+        s.record()
         fn()
-    e.record()
+        e.record()
     torch.cuda.synchronize()
-    return s.elapsed_time(e) / reps
+    return statistics.median(s.elapsed_time(e) for s, e in ev)
 
 
-gb = n * k * 4 / 1e9
+configs = [("this build", d) for d in dtypes] + ([(Path(a.against).name, "f32")] if a.against else [])
+if a.against and ("this build", "f32") not in configs:
+    configs.insert(0, ("this build", "f32"))
 flop = 2.0 * n * k * ((c + 15) // 16 * 16)
-for name, fn in (("forward", fwd), ("backward dX", lambda: bwd(True, False)), ("backward dW (+ reduction)", lambda: bwd(False, True))):
-    t = timed(fn, reps=200 if n <= 200_000 else 10)
-    print(f"N={n} K={k} C={c} keep={keep}  {name:26s} {t:7.3f} ms   {gb / t * 1e3:6.0f} GB/s of the [N, K] operand   {flop / t / 1e9:6.1f} TFLOP/s fp32 MFMA")
+reps = a.reps if n > 200_000 else max(a.reps, 200)
+for name, call in (("forward", lambda L, d: fwd(L, d)), ("backward dX", lambda L, d: bwd(L, d, True, False)),
+                   ("backward dW (+ reduction)", lambda L, d: bwd(L, d, False, True))):
+    for rnd in range(a.rounds):            # the configurations take turns
+        for which, d in configs:
+            t = timed(lambda: call(libs[which], d), reps)
+            gb = n * k * (4 if d == "f32" else 2) / 1e9
+            print(f"N={n} K={k} C={c} keep={keep}  {name:26s} {d:4s} {which:18s} round {rnd}  {t:7.3f} ms (median of {reps})   "
+                  f"{gb / t * 1e3:6.0f} GB/s of the [N, K] operand   {flop / t / 1e9:6.1f} TFLOP/s fp32 MFMA", flush=True)
