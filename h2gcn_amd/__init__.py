@@ -14,6 +14,8 @@ C ABI of ``include/h2gcn_hip.h``).  It mirrors the reference's operator interfac
   the library's IPC pulls) for 1..8 GPUs (new; the reference is single-device);
 * :class:`h2gcn_amd.layers.DropoutDense` -- keras ``Dropout`` + output ``Dense`` (``D0.5-MO``) as one pass over the concat
   buffer per direction (reference ``h2gcn/models/H2GCN.py:235-257``);
+* :meth:`h2gcn_amd.hops.HopPlan.select_rows` / :func:`h2gcn_amd.layers.fused_propagation_classify_rows` -- logits of, and the
+  backward from, a subset of the nodes (the labelled rows a semi-supervised loss lives on; new, ``--train_rows_only``);
 * :mod:`h2gcn_amd.metrics` -- masked softmax cross-entropy / accuracy in one pass over the logits
   (reference ``h2gcn/models/_metrics.py:8-25``);
 * :class:`h2gcn_amd.optim.KerasAdam` -- the reference's optimizer step (Keras / TensorFlow Adam arithmetic) as one launch for
@@ -28,5 +30,5 @@ There is no CPU fallback: every compute entry point raises if the HIP library or
 __version__ = "0.6.0"
 
 from . import _capi  # noqa: F401  (does not load the library until first use)
-from .hops import HopPlan  # noqa: F401
+from .hops import HopPlan, RowSelection  # noqa: F401
 from .layers import ConcatLayer, DropoutDense, GCNLayer, SliceLayer, SparseDense, SparseDropout, hop_spmm  # noqa: F401

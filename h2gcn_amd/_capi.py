@@ -67,6 +67,10 @@ EXPORTED_SYMBOLS = (
     "h2gcn_dropout_dense_backward_f32",
     "h2gcn_dropout_dense_bf16",
     "h2gcn_dropout_dense_backward_bf16",
+    "h2gcn_dropout_dense_rows_f32",
+    "h2gcn_dropout_dense_rows_bf16",
+    "h2gcn_dropout_dense_backward_rows_f32",
+    "h2gcn_dropout_dense_backward_rows_bf16",
     "h2gcn_masked_metrics_workspace_bytes",
     "h2gcn_masked_metrics_f32",
     "h2gcn_masked_ce_backward_f32",
@@ -240,6 +244,16 @@ def lib() -> C.CDLL:
         L.h2gcn_dropout_dense_backward_bf16.argtypes = [C.c_void_p, C.c_int64, C.c_int64, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int64,
                                                         C.c_float, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p,
                                                         C.c_size_t, C.c_void_p]
+    if hasattr(L, "h2gcn_dropout_dense_rows_f32"):   # (the row-selected calls, added within ABI 5: the full calls' arguments + rows_dev, n_sel)
+        rows_args = [C.c_void_p, C.c_int64]
+        L.h2gcn_dropout_dense_rows_f32.restype = C.c_int
+        L.h2gcn_dropout_dense_rows_f32.argtypes = list(L.h2gcn_dropout_dense_f32.argtypes) + rows_args
+        L.h2gcn_dropout_dense_rows_bf16.restype = C.c_int
+        L.h2gcn_dropout_dense_rows_bf16.argtypes = list(L.h2gcn_dropout_dense_f32.argtypes) + rows_args
+        L.h2gcn_dropout_dense_backward_rows_f32.restype = C.c_int
+        L.h2gcn_dropout_dense_backward_rows_f32.argtypes = list(L.h2gcn_dropout_dense_backward_f32.argtypes) + rows_args
+        L.h2gcn_dropout_dense_backward_rows_bf16.restype = C.c_int
+        L.h2gcn_dropout_dense_backward_rows_bf16.argtypes = list(L.h2gcn_dropout_dense_backward_bf16.argtypes) + rows_args
     L.h2gcn_masked_metrics_workspace_bytes.restype = C.c_size_t
     L.h2gcn_masked_metrics_workspace_bytes.argtypes = [C.c_int64]
     L.h2gcn_masked_metrics_f32.restype = C.c_int
@@ -294,7 +308,8 @@ def lib() -> C.CDLL:
     # An explicitly named ABI-3 or ABI-4 build (H2GCN_HIP_LIBRARY: the interleaved A/B tools time an older kernel) is accepted.  It
     # lacks what later rounds ADDED -- h2gcn_plan_segment_classes, h2gcn_adam_keras_l2_f32 / h2gcn_l2_penalty_*,
     # h2gcn_xchg_allgather_pull_rows (ABI 4), the bf16 launches h2gcn_spmm_hops_bf16 / _T_bf16 (ABI 5), the bf16 classifier
-    # h2gcn_dropout_dense_bf16 / _backward_bf16 (added within ABI 5) -- and every caller of those
+    # h2gcn_dropout_dense_bf16 / _backward_bf16 and the row-selected h2gcn_dropout_dense_rows_* / _backward_rows_* (added within
+    # ABI 5) -- and every caller of those
     # asks `has()` first: the front end then keeps the l2 penalty in the autograd graph, pulls whole shards, and
     # HopPlan.segment_classes / a bf16 HopPlan launch raise a message instead of an AttributeError.
     if got != ABI_VERSION and not (os.environ.get("H2GCN_HIP_LIBRARY") and got in (3, 4)):

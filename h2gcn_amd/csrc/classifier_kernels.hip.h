@@ -4,7 +4,8 @@
 // EXACTLY to fp32 where it is consumed (a 16-bit shift / mask) and a bf16 dX is the finished fp32 value rounded to nearest even at the
 // store (v_cvt_pk_bf16_f32) -- the MFMA operands, the mask, the placement of the 1 / keep scale and every summation order are
 // those of the fp32 kernels, so Z and dW are bit-identical to the fp32 launch on the upcast X.  Included by classifier.hip
-// (TX = TD = float) and classifier_bf16.hip (TX = bf16, TD = bf16 or float): two translation units, like spmm_bf16.hip --
+// (TX = TD = float), classifier_bf16.hip (TX = bf16, TD = bf16 or float) and classifier_rows.hip (ROWS = true: the row-selected
+// calls, every element type): separate translation units, like spmm_bf16.hip --
 // kernels compiled in one unit change the register allocation of their neighbours, and the fp32 instantiations must compile as
 // they did before the bf16 ones existed (profiles/r08_bf16_model_kernel_resources.txt).
 #pragma once
@@ -157,6 +158,17 @@ __device__ __forceinline__ u2u load_row4(const bf16* __restrict__ X, int64_t ldx
     }
     return w;
 }
+// Row selection (h2gcn_dropout_dense_rows_*): ROWS kernels walk a COMPACT list of n_rows selected rows -- row i of Z / G / dX
+// is row rows[i] of X, and the dropout mask is keyed by rows[i], so that every output row has the bits the full call gives
+// that row.  ROWS = false is the identity (and compiles to the code the kernels had before the selection existed).  A lane reads
+// its entries of rows[] once per row tile; an entry beyond the list yields kNoRow, which no load accepts.
+constexpr int64_t kNoRow = INT64_MAX;
+template <bool ROWS>
+__device__ __forceinline__ int64_t src_row(const int32_t* __restrict__ rows, int64_t n_rows, int64_t row) {
+    if constexpr (ROWS) return row < n_rows ? (int64_t)rows[row] : kNoRow;
+    else return row;
+}
+
 template <typename TX>
 struct Row4 {
     using type = f4u;
@@ -255,11 +267,12 @@ __device__ __forceinline__ void stage_wt(const float* __restrict__ W, int K, int
 // per lane, folded across the wave
 constexpr int kSmallRowsPerWave = 1;   // (2 / 4 rows per wave: 11-13 / 18-19 us per pass on Cora instead of 8-10: the launch is one wave's chain)
 constexpr int kSmallMaxK = 512;      // forward: two column groups per lane in registers (wider operands: matrix-core kernels)
-template <int MASK, typename TX>
+template <int MASK, typename TX, bool ROWS = false>
 __global__ __launch_bounds__(kThreads) void small_fwd_kernel(const TX* __restrict__ X, int64_t ldx, int64_t n_rows, int K,
                                                              const float* __restrict__ W, const float* __restrict__ bias, int C,
                                                              float inv_keep, uint32_t thr, int mask_on, uint64_t seed,
-                                                             const int64_t* step_dev, float* __restrict__ Y, int64_t ldy) {
+                                                             const int64_t* step_dev, float* __restrict__ Y, int64_t ldy,
+                                                             const int32_t* __restrict__ rows) {
     extern __shared__ float wt[];   // [C][Kp]
     const int Kp = (K + 3) & ~3;
     const int lane = threadIdx.x & 63;
@@ -268,10 +281,13 @@ __global__ __launch_bounds__(kThreads) void small_fwd_kernel(const TX* __restric
     // this wave's fragments of X first (K <= 512: the groups 4*lane and 256 + 4*lane of each row): their latency runs under the
     // staging of W
     typename Row4<TX>::type a[kSmallRowsPerWave][2];
+    int64_t src[kSmallRowsPerWave];
 #pragma unroll
-    for (int r = 0; r < kSmallRowsPerWave; ++r)
+    for (int r = 0; r < kSmallRowsPerWave; ++r) {
+        src[r] = src_row<ROWS>(rows, n_rows, row0 + r);
 #pragma unroll
-        for (int h = 0; h < 2; ++h) a[r][h] = load_row4(X, ldx, n_rows, K, row0 + r, 256 * h + 4 * lane);
+        for (int h = 0; h < 2; ++h) a[r][h] = load_row4(X, ldx, ROWS ? kNoRow : n_rows, K, src[r], 256 * h + 4 * lane);
+    }
     stage_wt(W, K, C, Kp, wt);
 #pragma unroll
     for (int r = 0; r < kSmallRowsPerWave; ++r) {
@@ -283,7 +299,7 @@ __global__ __launch_bounds__(kThreads) void small_fwd_kernel(const TX* __restric
         for (int h = 0; h < 2; ++h) {
             const int k = 256 * h + 4 * lane;
             if (k < K) {
-                const f4u x = apply_mask<MASK>(widen4(a[r][h]), mk, row, k);
+                const f4u x = apply_mask<MASK>(widen4(a[r][h]), mk, src[r], k);
 #pragma unroll
                 for (int c = 0; c < kSmallCP; ++c) {
                     if (c < C) {
@@ -311,10 +327,11 @@ __global__ __launch_bounds__(kThreads) void small_fwd_kernel(const TX* __restric
 }
 
 // backward, data: one thread per (row, group of four columns)
-template <int MASK, typename TD>
+template <int MASK, typename TD, bool ROWS = false>
 __global__ __launch_bounds__(kThreads) void small_dx_kernel(const float* __restrict__ G, int64_t ldg, int64_t n_rows, int K, int C,
                                                             const float* __restrict__ W, float inv_keep, uint32_t thr, int mask_on,
-                                                            uint64_t seed, const int64_t* step_dev, TD* __restrict__ dX, int64_t lddx) {
+                                                            uint64_t seed, const int64_t* step_dev, TD* __restrict__ dX, int64_t lddx,
+                                                            const int32_t* __restrict__ rows) {
     extern __shared__ float wt[];   // [C][Kp]
     const int Kp = (K + 3) & ~3;
     const int groups = Kp / 4;
@@ -336,7 +353,7 @@ __global__ __launch_bounds__(kThreads) void small_dx_kernel(const float* __restr
             }
         }
         f4u keep = {inv_keep, inv_keep, inv_keep, inv_keep};
-        keep = apply_mask<MASK>(keep, mk, row, k);        // inv_keep where kept, 0 where dropped
+        keep = apply_mask<MASK>(keep, mk, src_row<ROWS>(rows, n_rows, row), k);        // inv_keep where kept, 0 where dropped
         const f4u o = {out[0] * keep[0], out[1] * keep[1], out[2] * keep[2], out[3] * keep[3]};
         store_row4<false>(dX + row * lddx + k, o, k, K);
     }
@@ -350,11 +367,12 @@ bool small_operand(int64_t n_rows, int K, int C) { return n_rows <= h2gcn_dropou
 // ---- forward -------------------------------------------------------------------------------------------------------------
 // One workgroup = 4 waves x 32 rows; a wave owns 2 row tiles x NT column tiles of 16x16 accumulators.  W chunks of 128 rows
 // are double-buffered in LDS (one barrier per chunk).
-template <int NT, int MASK, typename TX>
+template <int NT, int MASK, typename TX, bool ROWS = false>
 __global__ __launch_bounds__(kThreads) void dropout_dense_fwd_kernel(const TX* __restrict__ X, int64_t ldx, int64_t n_rows, int K,
                                                                      const float* __restrict__ Wp, int Kpad, const float* __restrict__ bias,
                                                                      int C, float inv_keep, uint32_t thr, int mask_on, uint64_t seed,
-                                                                     const int64_t* step_dev, float* __restrict__ Y, int64_t ldy) {
+                                                                     const int64_t* step_dev, float* __restrict__ Y, int64_t ldy,
+                                                                     const int32_t* __restrict__ rows) {
     constexpr int S = lds_stride(NT);
     extern __shared__ float lds[];   // 2 x kKC x S
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -364,6 +382,11 @@ __global__ __launch_bounds__(kThreads) void dropout_dense_fwd_kernel(const TX* _
     const int64_t n_groups = (n_rows + kRowsPerGroup - 1) / kRowsPerGroup;
     for (int64_t grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {
         const int64_t row_base = grp * kRowsPerGroup + (int64_t)wave * kRowsPerWave;
+        int64_t src[2] = {0, 0};   // ROWS: the rows of X behind this lane's two list entries, read once per row tile
+        if constexpr (ROWS) {
+            src[0] = src_row<true>(rows, n_rows, row_base + i);
+            src[1] = src_row<true>(rows, n_rows, row_base + 16 + i);
+        }
         f32x4 acc[2][NT];
 #pragma unroll
         for (int t = 0; t < 2; ++t)
@@ -378,7 +401,10 @@ __global__ __launch_bounds__(kThreads) void dropout_dense_fwd_kernel(const TX* _
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
-                for (int g = 0; g < kKC / 16; ++g) a[t][g] = load_row4(X, ldx, n_rows, K, row_base + 16 * t + i, c * kKC + 16 * g + 4 * kq);
+                for (int g = 0; g < kKC / 16; ++g) {
+                    if constexpr (ROWS) a[t][g] = load_row4(X, ldx, kNoRow, K, src[t], c * kKC + 16 * g + 4 * kq);
+                    else a[t][g] = load_row4(X, ldx, n_rows, K, row_base + 16 * t + i, c * kKC + 16 * g + 4 * kq);
+                }
             // this buffer was last read two chunks ago; every wave has passed the barrier of the previous chunk since
             {
                 const f32x4* src = reinterpret_cast<const f32x4*>(Wp + (int64_t)c * kKC * S);
@@ -388,8 +414,8 @@ __global__ __launch_bounds__(kThreads) void dropout_dense_fwd_kernel(const TX* _
             __syncthreads();
 #pragma unroll
             for (int g = 0; g < kKC / 16; ++g) {
-                const f4u a0 = apply_mask<MASK>(widen4(a[0][g]), mk, row_base + i, c * kKC + 16 * g + 4 * kq);
-                const f4u a1 = apply_mask<MASK>(widen4(a[1][g]), mk, row_base + 16 + i, c * kKC + 16 * g + 4 * kq);
+                const f4u a0 = apply_mask<MASK>(widen4(a[0][g]), mk, ROWS ? src[0] : row_base + i, c * kKC + 16 * g + 4 * kq);
+                const f4u a1 = apply_mask<MASK>(widen4(a[1][g]), mk, ROWS ? src[1] : row_base + 16 + i, c * kKC + 16 * g + 4 * kq);
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
                     const float* brow = buf + ((g * 4 + j) * 4 + kq) * S + i;
@@ -421,11 +447,11 @@ __global__ __launch_bounds__(kThreads) void dropout_dense_fwd_kernel(const TX* _
 }
 
 // ---- backward, data: dX = (G W^T) .* M / keep ---------------------------------------------------------------------------------
-template <int NT, int MASK, typename TD>
+template <int NT, int MASK, typename TD, bool ROWS = false>
 __global__ __launch_bounds__(kThreads) void dropout_dense_dx_kernel(const float* __restrict__ G, int64_t ldg, int64_t n_rows, int K, int C,
                                                                     const float* __restrict__ Wtp, int n_chunks, float inv_keep,
                                                                     uint32_t thr, int mask_on, uint64_t seed, const int64_t* step_dev,
-                                                                    TD* __restrict__ dX, int64_t lddx) {
+                                                                    TD* __restrict__ dX, int64_t lddx, const int32_t* __restrict__ rows) {
     constexpr int CP = NT * 16, NS = NT * 4;
     extern __shared__ float lds[];   // 2 x CP x kDxStride
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -434,6 +460,12 @@ __global__ __launch_bounds__(kThreads) void dropout_dense_dx_kernel(const float*
     const int64_t n_groups = (n_rows + kRowsPerGroup - 1) / kRowsPerGroup;
     for (int64_t grp = blockIdx.x; grp < n_groups; grp += gridDim.x) {
         const int64_t row_base = grp * kRowsPerGroup + (int64_t)wave * kRowsPerWave;
+        // the rows that key the mask of this lane's two output rows (once per row tile)
+        int64_t src[2] = {0, 0};
+        if constexpr (ROWS && MASK != 0) {
+            src[0] = src_row<true>(rows, n_rows, row_base + i);
+            src[1] = src_row<true>(rows, n_rows, row_base + 16 + i);
+        }
         float ga[2][NS];   // A fragments: G[row_base + 16 t + i][4 s + kq]
 #pragma unroll
         for (int t = 0; t < 2; ++t)
@@ -474,7 +506,7 @@ __global__ __launch_bounds__(kThreads) void dropout_dense_dx_kernel(const float*
 #pragma unroll
                     for (int r = 0; r < 4; ++r) o[r] = t == 0 ? acc0[r] : acc1[r];
                     if constexpr (MASK != 0) {
-                        o = apply_mask<MASK>(o, mk, row, col);
+                        o = apply_mask<MASK>(o, mk, ROWS ? src[t] : row, col);
                         o *= inv_keep;
                     }
                     store_row4<kDxStreamingStore<TD>>(dX + row * lddx + col, o, col, K);
@@ -492,11 +524,12 @@ __global__ __launch_bounds__(kThreads) void dropout_dense_dx_kernel(const float*
 // the row range in steps of 4 rows.
 // launch bounds: 3 waves per SIMD (2 with four column tiles) -- without them the epilogue's accumulator read-out (96 AGPRs -> VGPRs
 // at once) sets the allocation and the kernel drops to 2 waves per SIMD (measured 1.45 -> 1.76 ms)
-template <int NT, int MASK, typename TX>
+template <int NT, int MASK, typename TX, bool ROWS = false>
 __global__ __launch_bounds__(kThreads, NT <= 3 ? 3 : 2) void dropout_dense_dw_kernel(const TX* __restrict__ X, int64_t ldx, int64_t n_rows, int K,
                                                                     const float* __restrict__ G, int64_t ldg, int C, float inv_keep,
                                                                     uint32_t thr, int mask_on, uint64_t seed, const int64_t* step_dev,
-                                                                    int64_t rows_per_wg, float* __restrict__ partial, int Kp, int row_split) {
+                                                                    int64_t rows_per_wg, float* __restrict__ partial, int Kp, int row_split,
+                                                                    const int32_t* __restrict__ rows) {
     constexpr int CP = NT * 16;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int i = lane & 15, kq = lane >> 4;
@@ -516,36 +549,59 @@ __global__ __launch_bounds__(kThreads, NT <= 3 ? 3 : 2) void dropout_dense_dw_ke
     // software pipeline: a step covers kDwSub sub-steps of 4 rows; the operands of step s+1 are requested before the
     // kDwSub * 8 * NT MFMAs of step s are issued (bytes in flight per wave: 2 steps x kDwSub x 2 KiB of X)
     using XR = typename Row4<TX>::type;
-    auto fetch = [&](int64_t r0, XR (&xa)[kDwSub][2], float (&gb)[kDwSub][NT]) {
+    // ROWS: the X row (and mask row) of list entry `row` is rows[row].  The entries of a step are read ONE STEP AHEAD of the fetch
+    // that uses them (ri_n), so that the index load is not a second latency in front of every X load; sr carries them to the mask.
+    auto load_idx = [&](int64_t r0, int32_t (&ri)[kDwSub]) {
+#pragma unroll
+        for (int q = 0; q < kDwSub; ++q) {
+            const int64_t row = r0 + 4 * q + kq;
+            ri[q] = row < r_end ? rows[row] : 0;
+        }
+    };
+    auto fetch = [&](int64_t r0, XR (&xa)[kDwSub][2], float (&gb)[kDwSub][NT], int32_t (&sr)[kDwSub], const int32_t (&ri)[kDwSub]) {
 #pragma unroll
         for (int q = 0; q < kDwSub; ++q) {
             const int64_t row = r0 + 4 * q + kq;
             const bool row_ok = row < r_end;
+            if constexpr (ROWS) sr[q] = ri[q];
 #pragma unroll
-            for (int w2 = 0; w2 < 2; ++w2) xa[q][w2] = load_row4(X, ldx, row_ok ? n_rows : 0, K, row, 64 * (seg0 + w2) + 4 * i);
+            for (int w2 = 0; w2 < 2; ++w2) {
+                if constexpr (ROWS) xa[q][w2] = load_row4(X, ldx, row_ok ? kNoRow : 0, K, (int64_t)ri[q], 64 * (seg0 + w2) + 4 * i);
+                else xa[q][w2] = load_row4(X, ldx, row_ok ? n_rows : 0, K, row, 64 * (seg0 + w2) + 4 * i);
+            }
 #pragma unroll
             for (int u = 0; u < NT; ++u) gb[q][u] = (row_ok && 16 * u + i < C) ? G[row * ldg + 16 * u + i] : 0.f;
         }
     };
     XR xa_n[kDwSub][2];
     float gb_n[kDwSub][NT];
-    if (r_begin < r_end) fetch(r_begin, xa_n, gb_n);
+    int32_t sr_n[kDwSub], ri_n[kDwSub];
+    if constexpr (ROWS) load_idx(r_begin, ri_n);
+    if (r_begin < r_end) fetch(r_begin, xa_n, gb_n, sr_n, ri_n);
+    if constexpr (ROWS) load_idx(r_begin + kDwRowsPerStep, ri_n);
     for (int64_t r0 = r_begin; r0 < r_end; r0 += kDwRowsPerStep) {
         XR xa[kDwSub][2];
         float gb[kDwSub][NT];
+        int32_t sr[kDwSub];
 #pragma unroll
         for (int q = 0; q < kDwSub; ++q) {
             xa[q][0] = xa_n[q][0];
             xa[q][1] = xa_n[q][1];
+            if constexpr (ROWS) sr[q] = sr_n[q];
 #pragma unroll
             for (int u = 0; u < NT; ++u) gb[q][u] = gb_n[q][u];
         }
-        if (r0 + kDwRowsPerStep < r_end) fetch(r0 + kDwRowsPerStep, xa_n, gb_n);
+        if (r0 + kDwRowsPerStep < r_end) {
+            fetch(r0 + kDwRowsPerStep, xa_n, gb_n, sr_n, ri_n);
+            if constexpr (ROWS) load_idx(r0 + 2 * kDwRowsPerStep, ri_n);
+        }
 #pragma unroll
         for (int q = 0; q < kDwSub; ++q)
 #pragma unroll
             for (int w2 = 0; w2 < 2; ++w2) {
-                const f4u xm = apply_mask<MASK>(widen4(xa[q][w2]), mk, r0 + 4 * q + kq, 64 * (seg0 + w2) + 4 * i);
+                int64_t mrow = r0 + 4 * q + kq;
+                if constexpr (ROWS) mrow = sr[q];
+                const f4u xm = apply_mask<MASK>(widen4(xa[q][w2]), mk, mrow, 64 * (seg0 + w2) + 4 * i);
 #pragma unroll
                 for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -667,10 +723,11 @@ int with_nt_mask(int nt, int mask, F&& f) {
 }
 
 // ---- launch code of the entry points (arguments already validated for the element types by the callers) -------------------
-template <typename TX>
+// ROWS: n_rows is the length of the row list `rows` (device, ascending, unique, every entry a row of X); Y / G / dX are compact
+template <typename TX, bool ROWS = false>
 int dropout_dense_forward(const TX* X, int64_t ldx, int64_t n_rows, int32_t K, const float* W, int32_t C, const float* bias,
                           float keep_prob, uint64_t seed, const int64_t* step_dev, float* Y, int64_t ldy, void* workspace,
-                          size_t workspace_bytes, void* stream_v) {
+                          size_t workspace_bytes, void* stream_v, const int32_t* rows = nullptr) {
     int st = check_common(X, ldx, n_rows, K, W, C, keep_prob);
     if (st != H2GCN_OK) return st;
     if (n_rows == 0) return H2GCN_OK;
@@ -684,9 +741,9 @@ int dropout_dense_forward(const TX* X, int64_t ldx, int64_t n_rows, int32_t K, c
         const unsigned blocks = (unsigned)((n_rows + rows_per_block - 1) / rows_per_block);
         const size_t lds = small_lds_bytes(K, C);
         switch (mask_mode(keep_prob)) {
-            case 0: hipLaunchKernelGGL((small_fwd_kernel<0, TX>), dim3(blocks), dim3(kThreads), lds, stream, X, ldx, n_rows, (int)K, W, bias, (int)C, 1.f / keep_prob, keep_threshold(keep_prob), 0, seed, step_dev, Y, ldy); break;
-            case 1: hipLaunchKernelGGL((small_fwd_kernel<1, TX>), dim3(blocks), dim3(kThreads), lds, stream, X, ldx, n_rows, (int)K, W, bias, (int)C, 1.f / keep_prob, keep_threshold(keep_prob), 1, seed, step_dev, Y, ldy); break;
-            default: hipLaunchKernelGGL((small_fwd_kernel<2, TX>), dim3(blocks), dim3(kThreads), lds, stream, X, ldx, n_rows, (int)K, W, bias, (int)C, 1.f / keep_prob, keep_threshold(keep_prob), 1, seed, step_dev, Y, ldy); break;
+            case 0: hipLaunchKernelGGL((small_fwd_kernel<0, TX, ROWS>), dim3(blocks), dim3(kThreads), lds, stream, X, ldx, n_rows, (int)K, W, bias, (int)C, 1.f / keep_prob, keep_threshold(keep_prob), 0, seed, step_dev, Y, ldy, rows); break;
+            case 1: hipLaunchKernelGGL((small_fwd_kernel<1, TX, ROWS>), dim3(blocks), dim3(kThreads), lds, stream, X, ldx, n_rows, (int)K, W, bias, (int)C, 1.f / keep_prob, keep_threshold(keep_prob), 1, seed, step_dev, Y, ldy, rows); break;
+            default: hipLaunchKernelGGL((small_fwd_kernel<2, TX, ROWS>), dim3(blocks), dim3(kThreads), lds, stream, X, ldx, n_rows, (int)K, W, bias, (int)C, 1.f / keep_prob, keep_threshold(keep_prob), 1, seed, step_dev, Y, ldy, rows); break;
         }
         H2GCN_HIP_TRY(hipGetLastError());
         return H2GCN_OK;
@@ -700,19 +757,19 @@ int dropout_dense_forward(const TX* X, int64_t ldx, int64_t n_rows, int32_t K, c
     const int64_t n_groups = (n_rows + kRowsPerGroup - 1) / kRowsPerGroup;
     return with_nt_mask(s.nt, mask_mode(keep_prob), [&](auto nt_c, auto mask_c) -> int {
         constexpr int NT = decltype(nt_c)::value, MASK = decltype(mask_c)::value;
-        H2GCN_HIP_TRY(hipFuncSetAttribute((const void*)dropout_dense_fwd_kernel<NT, MASK, TX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-        const unsigned grid = persistent_grid(dropout_dense_fwd_kernel<NT, MASK, TX>, lds_bytes, n_groups);
-        hipLaunchKernelGGL((dropout_dense_fwd_kernel<NT, MASK, TX>), dim3(grid), dim3(kThreads), lds_bytes, stream, X, ldx, n_rows, (int)K, (const float*)wp,
-                           s.kpad, bias, (int)C, 1.f / keep_prob, keep_threshold(keep_prob), mask_on, seed, step_dev, Y, ldy);
+        H2GCN_HIP_TRY(hipFuncSetAttribute((const void*)dropout_dense_fwd_kernel<NT, MASK, TX, ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        const unsigned grid = persistent_grid(dropout_dense_fwd_kernel<NT, MASK, TX, ROWS>, lds_bytes, n_groups);
+        hipLaunchKernelGGL((dropout_dense_fwd_kernel<NT, MASK, TX, ROWS>), dim3(grid), dim3(kThreads), lds_bytes, stream, X, ldx, n_rows, (int)K, (const float*)wp,
+                           s.kpad, bias, (int)C, 1.f / keep_prob, keep_threshold(keep_prob), mask_on, seed, step_dev, Y, ldy, rows);
         H2GCN_HIP_TRY(hipGetLastError());
         return H2GCN_OK;
     });
 }
 
-template <typename TX, typename TD>
+template <typename TX, typename TD, bool ROWS = false>
 int dropout_dense_backward(const TX* X, int64_t ldx, int64_t n_rows, int32_t K, const float* W, int32_t C, const float* G, int64_t ldg,
                            float keep_prob, uint64_t seed, const int64_t* step_dev, TD* dX, int64_t lddx, float* dW, void* workspace,
-                           size_t workspace_bytes, void* stream_v) {
+                           size_t workspace_bytes, void* stream_v, const int32_t* rows = nullptr) {
     int st = check_common(X, ldx, n_rows, K, W, C, keep_prob);
     if (st != H2GCN_OK) return st;
     if (!G && n_rows > 0) return fail(H2GCN_ERR_INVALID_ARGUMENT, "dropout_dense_backward: G is NULL");
@@ -733,9 +790,9 @@ int dropout_dense_backward(const TX* X, int64_t ldx, int64_t n_rows, int32_t K, 
         const unsigned blocks = (unsigned)std::min<int64_t>((total + kThreads - 1) / kThreads, 2 * (int64_t)cu_count());   // W^T is staged once per workgroup
         const size_t lds = small_lds_bytes(K, C);
         switch (mask_mode(keep_prob)) {
-            case 0: hipLaunchKernelGGL((small_dx_kernel<0, TD>), dim3(blocks), dim3(kThreads), lds, stream, G, ldg, n_rows, (int)K, (int)C, W, inv_keep, thr, 0, seed, step_dev, dX, lddx); break;
-            case 1: hipLaunchKernelGGL((small_dx_kernel<1, TD>), dim3(blocks), dim3(kThreads), lds, stream, G, ldg, n_rows, (int)K, (int)C, W, inv_keep, thr, 1, seed, step_dev, dX, lddx); break;
-            default: hipLaunchKernelGGL((small_dx_kernel<2, TD>), dim3(blocks), dim3(kThreads), lds, stream, G, ldg, n_rows, (int)K, (int)C, W, inv_keep, thr, 1, seed, step_dev, dX, lddx); break;
+            case 0: hipLaunchKernelGGL((small_dx_kernel<0, TD, ROWS>), dim3(blocks), dim3(kThreads), lds, stream, G, ldg, n_rows, (int)K, (int)C, W, inv_keep, thr, 0, seed, step_dev, dX, lddx, rows); break;
+            case 1: hipLaunchKernelGGL((small_dx_kernel<1, TD, ROWS>), dim3(blocks), dim3(kThreads), lds, stream, G, ldg, n_rows, (int)K, (int)C, W, inv_keep, thr, 1, seed, step_dev, dX, lddx, rows); break;
+            default: hipLaunchKernelGGL((small_dx_kernel<2, TD, ROWS>), dim3(blocks), dim3(kThreads), lds, stream, G, ldg, n_rows, (int)K, (int)C, W, inv_keep, thr, 1, seed, step_dev, dX, lddx, rows); break;
         }
         H2GCN_HIP_TRY(hipGetLastError());
         dX = nullptr;   // done
@@ -748,10 +805,10 @@ int dropout_dense_backward(const TX* X, int64_t ldx, int64_t n_rows, int32_t K, 
         const int64_t n_groups = (n_rows + kRowsPerGroup - 1) / kRowsPerGroup;
         st = with_nt_mask(s.nt, mask_mode(keep_prob), [&](auto nt_c, auto mask_c) -> int {
             constexpr int NT = decltype(nt_c)::value, MASK = decltype(mask_c)::value;
-            H2GCN_HIP_TRY(hipFuncSetAttribute((const void*)dropout_dense_dx_kernel<NT, MASK, TD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
-            const unsigned grid = persistent_grid(dropout_dense_dx_kernel<NT, MASK, TD>, lds_bytes, n_groups);
-            hipLaunchKernelGGL((dropout_dense_dx_kernel<NT, MASK, TD>), dim3(grid), dim3(kThreads), lds_bytes, stream, G, ldg, n_rows, (int)K, (int)C,
-                               (const float*)wtp, s.n_chunks, inv_keep, thr, mask_on, seed, step_dev, dX, lddx);
+            H2GCN_HIP_TRY(hipFuncSetAttribute((const void*)dropout_dense_dx_kernel<NT, MASK, TD, ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+            const unsigned grid = persistent_grid(dropout_dense_dx_kernel<NT, MASK, TD, ROWS>, lds_bytes, n_groups);
+            hipLaunchKernelGGL((dropout_dense_dx_kernel<NT, MASK, TD, ROWS>), dim3(grid), dim3(kThreads), lds_bytes, stream, G, ldg, n_rows, (int)K, (int)C,
+                               (const float*)wtp, s.n_chunks, inv_keep, thr, mask_on, seed, step_dev, dX, lddx, rows);
             H2GCN_HIP_TRY(hipGetLastError());
             return H2GCN_OK;
         });
@@ -761,8 +818,8 @@ int dropout_dense_backward(const TX* X, int64_t ldx, int64_t n_rows, int32_t K, 
         float* part = (float*)((char*)workspace + s.off_partial);
         st = with_nt_mask(s.nt, mask_mode(keep_prob), [&](auto nt_c, auto mask_c) -> int {
             constexpr int NT = decltype(nt_c)::value, MASK = decltype(mask_c)::value;
-            hipLaunchKernelGGL((dropout_dense_dw_kernel<NT, MASK, TX>), dim3((unsigned)s.gx, (unsigned)s.gy), dim3(kThreads), 0, stream, X, ldx, n_rows, (int)K,
-                               G, ldg, (int)C, inv_keep, thr, mask_on, seed, step_dev, s.rows_per_wg, part, s.kp, s.row_split);
+            hipLaunchKernelGGL((dropout_dense_dw_kernel<NT, MASK, TX, ROWS>), dim3((unsigned)s.gx, (unsigned)s.gy), dim3(kThreads), 0, stream, X, ldx, n_rows, (int)K,
+                               G, ldg, (int)C, inv_keep, thr, mask_on, seed, step_dev, s.rows_per_wg, part, s.kp, s.row_split, rows);
             H2GCN_HIP_TRY(hipGetLastError());
             return H2GCN_OK;
         });

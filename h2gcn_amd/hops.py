@@ -74,6 +74,8 @@ class HopPlan:
             _require(rp.dim() == 1 and rp.numel() == n_rows + 1, f"hop {k}: rowptr has {rp.numel()} entries, expected {n_rows + 1}")
             _require(ci.dim() == 1 and va.dim() == 1 and ci.numel() == va.numel(), f"hop {k}: colidx/vals sizes differ")
             _require(rp.is_contiguous() and ci.is_contiguous() and va.is_contiguous(), f"hop {k}: operands must be contiguous")
+        # the schedule tunables, so that select_rows can build its sub-plan the same way
+        self._tunables = dict(long_row_threshold=long_row_threshold, rows_per_wave=rows_per_wave, variant=variant, slice_cols=slice_cols)
         self.n_hops = H
         self.n_rows = int(n_rows)
         self.n_cols = int(n_cols)
@@ -143,6 +145,55 @@ class HopPlan:
             _capi.check(_capi.lib().h2gcn_plan_set_values(self._handle, int(hop), C.c_void_p(vals.data_ptr()), C.c_void_p(stream)))
         self.vals[hop] = vals
         self.values_version = getattr(self, "values_version", 0) + 1   # anything cached as a function of the values is stale
+
+    def select_rows(self, rows, build_transpose: bool = True) -> "RowSelection":
+        """The hop matrices restricted to a set of rows: ``RowSelection(rows, plan, n_rows_full)`` with ``plan`` a
+        :class:`HopPlan` of ``A_k[rows, :]`` (shape ``[m, n_cols]``) -- what the backward of a loss that lives on these rows
+        needs (``sel.plan.spmm_t`` gathers a COMPACT ``[m, H, d]`` gradient through ``A_k[rows]^T``), and what
+        ``DropoutDense(x, rows=sel)`` takes for logits of a node subset.
+
+        ``rows``: a bool mask ``[n_rows]`` or an integer index tensor / sequence (any order; it is sorted).  Duplicates,
+        indices outside ``[0, n_rows)`` and an empty selection raise ``ValueError``.  ``sel.rows`` is int32, ascending and
+        unique, on the plan's device.
+
+        The sub-CSR is built on the device with torch ops (row-length gather, cumsum, segmented index arithmetic); it keeps
+        the per-row column order and the values of this plan, so its launches give the bits of a plan built from the same
+        sub-matrices.  One-off set-up (it synchronises: the checks and the sub-matrix sizes are read back) -- call it before
+        any hipGraph capture, never inside one.
+
+        Memory: the sub-plan holds its own copy of the selected rows' column ids and values, and of their transpose when
+        ``build_transpose`` -- about ``2 * m / n_rows`` of this operand's bytes for a selection of average row length
+        (``m / n_rows`` without the transpose), plus two ``[m]`` index arrays."""
+        _require(self.device.type == "cuda", f"select_rows: the plan must live on a GPU, got {self.device} (no CPU fallback)")
+        t = rows if isinstance(rows, torch.Tensor) else torch.as_tensor(rows)
+        if t.dtype == torch.bool:
+            _require(t.dim() == 1 and t.numel() == self.n_rows, f"select_rows: a bool mask must have shape [{self.n_rows}], got {tuple(t.shape)}")
+            idx = torch.nonzero(t.to(self.device)).flatten()
+            _require(idx.numel() > 0, "select_rows: empty selection")
+        else:
+            _require(not (t.is_floating_point() or t.is_complex()), f"select_rows: rows must be a bool mask or integer indices, got {t.dtype}")
+            _require(t.dim() == 1, f"select_rows: an index tensor must be one-dimensional, got shape {tuple(t.shape)}")
+            _require(t.numel() > 0, "select_rows: empty selection")
+            idx = torch.sort(t.to(self.device, torch.int64)).values
+            lo, hi = int(idx[0]), int(idx[-1])
+            _require(lo >= 0 and hi < self.n_rows, f"select_rows: row index {lo if lo < 0 else hi} outside [0, {self.n_rows})")
+            _require(not bool((idx[1:] == idx[:-1]).any()), "select_rows: duplicate row indices")
+        m = int(idx.numel())
+        rowptr, colidx, vals = [], [], []
+        for k in range(self.n_hops):
+            rp = self.rowptr[k]
+            begin = rp[idx]
+            lens = rp[idx + 1] - begin
+            sub_rp = torch.zeros(m + 1, dtype=torch.int64, device=self.device)
+            torch.cumsum(lens, 0, out=sub_rp[1:])
+            nnz = int(sub_rp[-1])
+            # entry e of the sub-matrix, in row i, is entry begin[i] + (e - sub_rp[i]) of the parent
+            src = torch.arange(nnz, dtype=torch.int64, device=self.device) + torch.repeat_interleave(begin - sub_rp[:-1], lens, output_size=nnz)
+            rowptr.append(sub_rp)
+            colidx.append(self.colidx[k][src].contiguous())
+            vals.append(self.vals[k][src].contiguous())
+        plan = HopPlan(rowptr, colidx, vals, self.n_cols, build_transpose=build_transpose, validate=False, **self._tunables)
+        return RowSelection(idx.to(torch.int32), plan, self.n_rows)
 
     # ------------------------------------------------------------------ introspection
     @property
@@ -336,3 +387,20 @@ class HopPlan:
             except Exception:
                 pass
             self._handle = C.c_void_p()
+
+
+class RowSelection:
+    """A set of rows of a :class:`HopPlan` (see :meth:`HopPlan.select_rows`).
+
+    ``rows``: int32 ``[m]``, ascending and unique, on the plan's device; ``plan``: the :class:`HopPlan` of ``A_k[rows, :]``;
+    ``n_rows_full``: the row count of the plan the selection was taken from.  ``rows_long`` is the same list as int64 (what
+    torch's indexing ops take)."""
+
+    def __init__(self, rows: torch.Tensor, plan: HopPlan, n_rows_full: int):
+        self.rows = rows
+        self.rows_long = rows.to(torch.int64)
+        self.plan = plan
+        self.n_rows_full = int(n_rows_full)
+
+    def __len__(self) -> int:
+        return int(self.rows.numel())

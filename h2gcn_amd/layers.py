@@ -15,7 +15,7 @@ import os
 
 import torch
 
-from .hops import HopPlan
+from .hops import HopPlan, RowSelection
 
 
 class _HopSpMM(torch.autograd.Function):
@@ -422,6 +422,173 @@ class _DropoutDenseFn(torch.autograd.Function):
         return dx, dw, db, None, None, None
 
 
+def _rows_symbols() -> None:
+    from . import _capi
+    if not _capi.has("h2gcn_dropout_dense_rows_f32"):
+        raise RuntimeError(f"{_capi.library_path()} predates the row-selected classifier (h2gcn_dropout_dense_rows_f32): rebuild it")
+
+
+def _dd_rows_forward(x, w, bias, keep_prob, seed, step_dev, sel: RowSelection) -> torch.Tensor:
+    """``Z_c [m, C]``: the logits of rows ``sel.rows`` of ``x`` (``h2gcn_dropout_dense_rows_f32 / _bf16``)."""
+    import ctypes as C
+
+    from . import _capi
+    n, k = x.shape
+    c, m = w.shape[1], len(sel)
+    z = torch.empty((m, c), dtype=torch.float32, device=x.device)
+    ws = _dd_workspace(m, k, c, x.device)
+    with torch.cuda.device(x.device):
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        fn = _capi.lib().h2gcn_dropout_dense_rows_bf16 if x.dtype == torch.bfloat16 else _capi.lib().h2gcn_dropout_dense_rows_f32
+        _capi.check(fn(
+            C.c_void_p(x.data_ptr()), x.stride(0), n, k, C.c_void_p(w.data_ptr()), c,
+            C.c_void_p(bias.data_ptr()) if bias is not None else None, float(keep_prob), int(seed),
+            C.c_void_p(step_dev.data_ptr()) if step_dev is not None else None, C.c_void_p(z.data_ptr()), z.stride(0),
+            C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(stream), C.c_void_p(sel.rows.data_ptr()), m))
+    return z
+
+
+def _dd_rows_backward(x, w, g, keep_prob, seed, step_dev, sel: RowSelection, need_dx: bool, need_dw: bool):
+    """``(dX_c [m, K] in x's dtype, dW [K, C])`` for the compact logit gradient ``g [m, C]`` (either may be None)."""
+    import ctypes as C
+
+    from . import _capi
+    n, k = x.shape
+    c, m = w.shape[1], len(sel)
+    bf16 = x.dtype == torch.bfloat16
+    dx = torch.empty((m, k + (k % 2 if bf16 else 0)), dtype=x.dtype, device=x.device)[:, :k] if need_dx else None
+    dw = torch.empty((k, c), dtype=torch.float32, device=x.device) if need_dw else None
+    if need_dx or need_dw:
+        ws = _dd_workspace(m, k, c, x.device)
+        with torch.cuda.device(x.device):
+            stream = torch.cuda.current_stream(x.device).cuda_stream
+            fn, dx_dtype = ((_capi.lib().h2gcn_dropout_dense_backward_rows_bf16, (_capi.DTYPE_BF16,)) if bf16
+                            else (_capi.lib().h2gcn_dropout_dense_backward_rows_f32, ()))
+            _capi.check(fn(
+                C.c_void_p(x.data_ptr()), x.stride(0), n, k, C.c_void_p(w.data_ptr()), c, C.c_void_p(g.data_ptr()), g.stride(0),
+                float(keep_prob), int(seed), C.c_void_p(step_dev.data_ptr()) if step_dev is not None else None, *dx_dtype,
+                C.c_void_p(dx.data_ptr()) if need_dx else None, dx.stride(0) if need_dx else k,
+                C.c_void_p(dw.data_ptr()) if need_dw else None, C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(stream),
+                C.c_void_p(sel.rows.data_ptr()), m))
+    return dx, dw
+
+
+class _DropoutDenseRowsFn(torch.autograd.Function):
+    """``DropoutDense(x, rows=sel)`` on its own: compact logits, gradients for ``kernel`` and ``bias`` only -- the compact
+    ``dX`` has no place in an autograd graph whose node must return a gradient of ``x``'s shape (the training path that needs
+    it is :func:`fused_propagation_classify_rows`)."""
+
+    @staticmethod
+    def forward(ctx, x, kernel, bias, keep_prob, seed, step_dev, sel):
+        w = kernel.contiguous()
+        ctx.save_for_backward(x, w, step_dev if step_dev is not None else torch.empty(0, device=x.device))
+        ctx.keep_prob, ctx.seed, ctx.has_bias, ctx.has_step, ctx.sel = float(keep_prob), int(seed), bias is not None, step_dev is not None, sel
+        return _dd_rows_forward(x, w, bias, keep_prob, seed, step_dev, sel)
+
+    @staticmethod
+    def backward(ctx, g):
+        x, w, step = ctx.saved_tensors
+        g = g.contiguous()
+        _, dw = _dd_rows_backward(x, w, g, ctx.keep_prob, ctx.seed, step if ctx.has_step else None, ctx.sel, False, ctx.needs_input_grad[1])
+        db = g.sum(0) if ctx.has_bias and ctx.needs_input_grad[2] else None
+        return None, dw, db, None, None, None, None
+
+
+class _PropagationClassifyRowsFn(torch.autograd.Function):
+    """Propagation + classifier on selected rows as ONE autograd node: inputs ``r0``, ``kernel``, ``bias``; output the compact
+    logits ``Z_c [m, C]``.  One node because the classifier's input gradient is compact (``[m, W]``: the rows of the concat
+    buffer's gradient that are not zero) and a node boundary between the two would need it at the buffer's shape.
+
+    Forward: the full ``[N, W]`` propagation exactly as :class:`_FusedPropagation` runs it (same buffer, ``out`` / ``reuse``,
+    bfloat16), then the row-selected classifier forward.  Backward, with ``g_c = dX_c`` and ``rows = sel.rows``::
+
+        round K:          t = sel.plan.spmm_t(g_c[:, slot_K])      [N, w_{K-1}]   (gathers m rows' gradient, not N)
+                          t[rows] += g_c[:, slot_{K-1}]                           (rows are unique: deterministic)
+        rounds K-1 .. 1:  t = plan.spmm_t(g_k);  t[rows] += g_c[:, slot_{k-1}]
+
+    bfloat16 keeps :class:`_FusedPropagation`'s order of roundings: ``t`` is accumulated in fp32, the slot addend is widened
+    exactly, one rounding to bfloat16 per round for ``k > 1``, the last round stays fp32."""
+
+    @staticmethod
+    def forward(ctx, r0, kernel, bias, plan, sel, rounds, out, reuse, dtype, keep_prob, seed, step_dev):
+        prop = _NoCtx()
+        buf = _FusedPropagation.forward(prop, r0, plan, rounds, out, reuse, False, dtype)
+        w = kernel.contiguous()
+        z = _dd_rows_forward(buf, w, bias, keep_prob, seed, step_dev, sel)
+        ctx.save_for_backward(buf, w, step_dev if step_dev is not None else torch.empty(0, device=buf.device))
+        ctx.plan, ctx.sel, ctx.rounds, ctx.widths, ctx.off = plan, sel, rounds, prop.widths, prop.off
+        ctx.keep_prob, ctx.seed, ctx.has_bias, ctx.has_step = float(keep_prob), int(seed), bias is not None, step_dev is not None
+        return z
+
+    @staticmethod
+    def backward(ctx, g):
+        buf, w, step = ctx.saved_tensors
+        plan, sel, K, widths, off = ctx.plan, ctx.sel, ctx.rounds, ctx.widths, ctx.off
+        H = plan.n_hops
+        g = g.contiguous()
+        need_r0 = ctx.needs_input_grad[0]
+        g_c, dw = _dd_rows_backward(buf, w, g, ctx.keep_prob, ctx.seed, step if ctx.has_step else None, sel, need_r0, ctx.needs_input_grad[1])
+        db = g.sum(0) if ctx.has_bias and ctx.needs_input_grad[2] else None
+        d_r0 = None
+        if need_r0:
+            bf16 = buf.dtype == torch.bfloat16
+            g_k, p = g_c[:, off[K]:off[K] + widths[K]], sel.plan    # round K gathers through A_k[rows]^T, the others through A_k^T
+            for k in range(K, 0, -1):
+                t = p.spmm_t(g_k.unflatten(1, (H, widths[k - 1])), out_dtype=torch.float32)
+                slot = g_c[:, off[k - 1]:off[k - 1] + widths[k - 1]]
+                t.index_add_(0, sel.rows_long, slot.float() if bf16 else slot)
+                g_k, p = (t.to(torch.bfloat16) if bf16 and k > 1 else t), plan
+            d_r0 = g_k
+        return d_r0, dw, db, None, None, None, None, None, None, None, None, None
+
+
+def fused_propagation_classify_rows(plan: HopPlan, sel: RowSelection, r0: torch.Tensor, rounds: int, dense_layer: "DropoutDense",
+                                    out: Optional[torch.Tensor] = None, reuse: bool = False,
+                                    dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+    """``dense_layer(fused_propagation(plan, r0, rounds))[sel.rows]`` -- the logits of the selected rows, ``[m, units]`` -- with
+    a backward that works on those rows only (:class:`_PropagationClassifyRowsFn`): a loss that lives on ``sel.rows`` has a
+    zero logit gradient everywhere else, so the classifier's backward and the widest adjoint launch need ``m`` rows, not ``N``.
+
+    ``sel = plan.select_rows(...)`` (with its transpose); ``out`` / ``reuse`` / ``dtype`` as in :func:`fused_propagation`.
+    ``dense_layer`` is the :class:`DropoutDense` that consumes the buffer: its step counter advances exactly as in the full
+    path, so with equal seeds both paths draw the same dropout mask, and the logits are bit-identical to the full path's rows.
+    Gradients equal the full path's up to summation order."""
+    if not isinstance(sel, RowSelection):
+        raise TypeError(f"sel must be a RowSelection (HopPlan.select_rows), got {type(sel).__name__}")
+    if not isinstance(plan, HopPlan):
+        raise ValueError(f"fused_propagation_classify_rows: plan must be a HopPlan, got {type(plan).__name__} "
+                         "(row-partitioned hops are not covered)")
+    if sel.n_rows_full != plan.n_rows or sel.plan.n_cols != plan.n_cols or sel.plan.n_hops != plan.n_hops:
+        raise ValueError("fused_propagation_classify_rows: sel was not taken from this plan")
+    if not isinstance(dense_layer, DropoutDense):
+        raise ValueError(f"fused_propagation_classify_rows: dense_layer must be a DropoutDense, got {type(dense_layer).__name__}")
+    if dense_layer.kernel.shape[1] > 64:
+        raise ValueError(f"fused_propagation_classify_rows: the classifier kernels cover units <= 64, got {dense_layer.kernel.shape[1]}")
+    if rounds < 1:
+        raise ValueError("rounds must be >= 1")
+    if dtype not in (None, torch.float32, torch.bfloat16):
+        raise ValueError(f"fused_propagation_classify_rows: dtype must be float32 or bfloat16, got {dtype}")
+    if r0.dim() != 2 or r0.shape[0] != plan.n_cols or plan.n_rows != plan.n_cols or not r0.is_cuda or r0.dtype != torch.float32:
+        raise ValueError(f"r0 must be a float32 CUDA tensor [{plan.n_cols}, d] and the hop matrices square")
+    if dtype == torch.bfloat16 and r0.shape[1] % 2:
+        raise ValueError(f"fused_propagation_classify_rows: a bfloat16 buffer needs an even embedding width, got {r0.shape[1]}")
+    if reuse and out is None:
+        raise ValueError("fused_propagation_classify_rows: reuse=True needs the buffer that holds the propagation (out=)")
+    _rows_symbols()
+    keep_prob, step = dense_layer._draw_step()
+    args = (plan, sel, rounds, out, reuse, dtype, keep_prob, dense_layer.seed, step)
+    if torch.is_grad_enabled() and (r0.requires_grad or dense_layer.kernel.requires_grad):
+        if not sel.plan.has_transpose and r0.requires_grad:
+            raise ValueError("fused_propagation_classify_rows: sel was built without its transpose (select_rows(build_transpose=True))")
+        return _PropagationClassifyRowsFn.apply(r0, dense_layer.kernel, dense_layer.bias, *args)
+    return _PropagationClassifyRowsFn.forward(_NoCtxSave(), r0, dense_layer.kernel, dense_layer.bias, *args)
+
+
+class _NoCtxSave(_NoCtx):
+    def save_for_backward(self, *tensors) -> None:
+        pass
+
+
 class DropoutDense(torch.nn.Module):
     """keras ``Dropout(rate)`` followed by ``Dense(units)`` -- the ``D0.5-MO`` tail of the network setup (reference
     ``h2gcn/models/H2GCN.py:235-257``, called in order at ``:308-325``) -- as ONE pass over the ``[N, K]`` input per
@@ -457,7 +624,20 @@ class DropoutDense(torch.nn.Module):
             self.seed = (self.seed ^ (torch.distributed.get_rank() * 0x9E3779B97F4A7C15)) & 0x7FFFFFFFFFFFFFFF
         self.register_buffer("_step", torch.zeros(1, dtype=torch.int64), persistent=False)
 
-    def forward(self, x: torch.Tensor) -> torch.Tensor:
+    def _draw_step(self):
+        """``(keep_prob, step)`` of one forward: in training the step counter advances (stream-ordered: a captured graph
+        bumps it on every replay) and ``step`` is the value this forward and its backward use."""
+        if not (self.training and self.drop_prob > 0.0):
+            return 1.0, None
+        self._step += 1
+        return 1.0 - self.drop_prob, self._step.clone()
+
+    def forward(self, x: torch.Tensor, rows: Optional[RowSelection] = None) -> torch.Tensor:
+        """``rows``: a :class:`h2gcn_amd.hops.RowSelection` -- the logits of those rows only, ``[m, units]``, bit-identical to
+        the same rows of the full result (the mask is keyed by the original row).  Meant for inference on a node subset
+        (``torch.no_grad()``); with gradients enabled ``kernel`` and ``bias`` get theirs, ``x`` must not require one."""
+        if rows is not None:
+            return self._forward_rows(x, rows)
         training = self.training and self.drop_prob > 0.0
         fused_ok = (x.is_cuda and x.dim() == 2 and x.dtype in (torch.float32, torch.bfloat16) and self.kernel.shape[1] <= 64
                     and (x.shape[1] <= 1 or x.stride(1) == 1) and x.stride(0) >= x.shape[1])
@@ -478,6 +658,24 @@ class DropoutDense(torch.nn.Module):
             self._step += 1                      # stream-ordered: a captured graph bumps it on every replay
             step = self._step.clone()            # the value this forward (and its backward) uses
         return _DropoutDenseFn.apply(x, self.kernel, self.bias, 1.0 - self.drop_prob if training else 1.0, self.seed, step)
+
+    def _forward_rows(self, x: torch.Tensor, sel: RowSelection) -> torch.Tensor:
+        if not isinstance(sel, RowSelection):
+            raise TypeError(f"rows must be a RowSelection (HopPlan.select_rows), got {type(sel).__name__}")
+        ok = (x.is_cuda and x.dim() == 2 and x.dtype in (torch.float32, torch.bfloat16) and self.kernel.shape[1] <= 64
+              and (x.shape[1] <= 1 or x.stride(1) == 1) and x.stride(0) >= x.shape[1]
+              and (x.dtype != torch.bfloat16 or (x.stride(0) % 2 == 0 and x.data_ptr() % 4 == 0)))
+        if not ok:   # no stock path here: it would draw another mask
+            raise ValueError("DropoutDense(x, rows=...) runs on the row-selected classifier kernels only: x must be a 2-D float32 or "
+                             "bfloat16 CUDA tensor with unit column stride (bfloat16: even row stride) and units <= 64")
+        if x.shape[0] != sel.n_rows_full or sel.rows.device != x.device:
+            raise ValueError(f"rows were selected from {sel.n_rows_full} rows on {sel.rows.device}, x has {x.shape[0]} rows on {x.device}")
+        if x.requires_grad and torch.is_grad_enabled():
+            raise ValueError("DropoutDense(x, rows=...) cannot return a gradient for x (it would be compact): train through "
+                             "layers.fused_propagation_classify_rows, or detach x")
+        _rows_symbols()
+        keep_prob, step = self._draw_step()
+        return _DropoutDenseRowsFn.apply(x, self.kernel, self.bias, keep_prob, self.seed, step, sel)
 
     def extra_repr(self) -> str:
         return f"in={self.kernel.shape[0]}, units={self.kernel.shape[1]}, bias={self.bias is not None}, drop={self.drop_prob}"

@@ -50,6 +50,10 @@ def add_subparser_args(parser):
                    help="dtype of the propagated embeddings (the concat buffer of the fused propagation and the input of the layer "
                         "that consumes it): bfloat16 halves the bytes of every hop launch and of the classifier's passes; "
                         "parameters, optimizer state, logits, loss and all accumulation stay float32 (default: %(default)s)")
+    g.add_argument("--train_rows_only", action="store_true",
+                   help="run the training step's classifier and backward pass on the labelled rows only (the loss lives on the "
+                        "train mask, so every other row's logit gradient is zero): row-selected classifier kernels and the widest "
+                        "adjoint launch on the hop matrices' labelled rows; same results up to summation order (default: off)")
     g.add_argument("--sparse_dropout_at_eval", action="store_true",
                    help="reproduce the reference's SparseDropout, which Keras never switches off (it drops sparse feature "
                         "values during evaluation as well); default: inactive in evaluation like every other dropout")
@@ -116,7 +120,8 @@ def initialize_model(args, layer_setups, optimizer, lr, l2_regularize_weight, ea
                   sparse_dropout_at_eval=getattr(args, "sparse_dropout_at_eval", False),
                   fused_classifier=not getattr(args, "no_fused_classifier", False),
                   reuse_propagation=not getattr(args, "no_propagation_reuse", False),
-                  embedding_dtype=EMBEDDING_DTYPES[getattr(args, "embedding_dtype", "float32")]).to(device)
+                  embedding_dtype=EMBEDDING_DTYPES[getattr(args, "embedding_dtype", "float32")],
+                  train_rows_only=getattr(args, "train_rows_only", False)).to(device)
     sharded = _is_sharded()
     if sharded:  # replicas must start identical whatever the seeding on each rank (e.g. --random_seed 0)
         for p_ in model.parameters():
@@ -148,10 +153,29 @@ def initialize_model(args, layer_setups, optimizer, lr, l2_regularize_weight, ea
     model.fused_l2 = fused_l2
     penalty = model.regularization_value if fused_l2 else model.regularization_loss
 
+    # --train_rows_only: the labelled rows as a RowSelection of the hop plan, the labels of those rows and an all-ones mask --
+    # static, built once per train mask (eagerly, in the warm-up epochs before any capture: select_rows synchronises)
+    rows_cache = {}
+
+    def _train_rows(adj_hops, y_train, train_mask):
+        key = (id(adj_hops), train_mask.data_ptr(), y_train.data_ptr())
+        if rows_cache.get("key") != key:
+            if not isinstance(adj_hops, L.HopPlan):
+                raise ValueError("train_rows_only does not cover row-partitioned hops (ShardedHops): run on one GPU or without "
+                                 "--train_rows_only")
+            sel = adj_hops.select_rows(train_mask != 0, build_transpose=True)
+            rows_cache.update(key=key, sel=sel, labels=y_train[sel.rows_long].contiguous(),
+                              ones=torch.ones(len(sel), dtype=torch.float32, device=y_train.device))
+        return rows_cache
+
     def train_step(adj, adj_hops, features, y_train, train_mask, **kwargs):
         model.train()
         optimizer.zero_grad(set_to_none=True)
-        predictions = model(adj, features, adj_hops)
+        if model.train_rows_only:   # compact logits of the labelled rows; the mean over them is the masked mean over all rows
+            c = _train_rows(adj_hops, y_train, train_mask)
+            predictions, y_train, train_mask = model(adj, features, adj_hops, rows=c["sel"]), c["labels"], c["ones"]
+        else:
+            predictions = model(adj, features, adj_hops)
         if fused_l2:
             data_loss = model.data_loss(predictions, y_train, train_mask)
             data_loss.backward()
@@ -508,11 +532,19 @@ class H2GCN(torch.nn.Module):
     with ``dtype=``) and the layer that consumes the buffer reads it in bfloat16 (``DropoutDense``: the ``_bf16`` classifier
     kernels; a plain ``Dense`` upcasts -- the slow path).  Parameters, logits, loss and every accumulation stay float32.  What
     this does not cover is refused with a ``ValueError``, never run in float32 behind the caller's back: a network set-up
-    without a fusable block, an odd width at the block's input, row-partitioned runs."""
+    without a fusable block, an odd width at the block's input, row-partitioned runs.
+
+    ``train_rows_only=True``: ``forward(..., rows=sel)`` (``sel = adjhops.select_rows(...)``) returns the logits of the selected
+    rows only, ``[m, units]``, and its backward works on those rows (``layers.fused_propagation_classify_rows``) -- for a loss
+    that lives on those rows, as the semi-supervised training loss does on the train mask.  It covers the fused propagation
+    block followed directly by the final fused dropout+dense layer; anything else is refused with a ``ValueError`` at
+    construction (no fusable block, a tag on the block's last layer, a buffer whose consumer is not the final
+    ``DropoutDense``: ``units > 64`` or ``fused_classifier=False``) or at the call (row-partitioned hops, ``fuse=False``), never
+    run the full way instead."""
 
     def __init__(self, layer_setups, input_dim: int, n_hops: int = 2, sparse_input: bool = True,
                  l2_regularize_weight: float = 0.0, sparse_dropout_at_eval: bool = False, fused_classifier: bool = True,
-                 reuse_propagation: bool = True, embedding_dtype: torch.dtype = torch.float32):
+                 reuse_propagation: bool = True, embedding_dtype: torch.dtype = torch.float32, train_rows_only: bool = False):
         super().__init__()
         if embedding_dtype not in (torch.float32, torch.bfloat16):
             raise ValueError(f"embedding_dtype must be torch.float32 or torch.bfloat16, got {embedding_dtype}")
@@ -625,9 +657,30 @@ class H2GCN(torch.nn.Module):
         self.reuse_propagation = (bool(reuse_propagation) and self.fused is not None
                                   and os.environ.get("H2GCN_PROPAGATION_REUSE", "1") != "0"
                                   and all(self._same_in_both_modes(m) for m in list(self.layer_objs)[: self.fused[0]]))
+        self.train_rows_only = bool(train_rows_only)
+        if self.train_rows_only:
+            self._check_rows_only_setup()
         self._weights_tag = 0        # bumped whenever the parameters change (note_update)
         self._prop_key = None        # what the persistent buffer currently holds
         self._prop_buf = None
+
+    def _check_rows_only_setup(self) -> None:
+        """train_rows_only covers: fused propagation block -> (placeholders) -> the FINAL layer, a DropoutDense."""
+        if self.fused is None:
+            raise ValueError("train_rows_only needs the fused propagation block (`...-T1-G-V-T2-G-V-C1-C2-...`); this network "
+                             "set-up has none -- change the set-up or drop --train_rows_only")
+        end = self.fused[1]
+        if (end - 1) in self.tags:
+            raise ValueError("train_rows_only: the propagation block's last layer is tagged, so the concat buffer has a consumer "
+                             "besides the classifier -- drop the tag or --train_rows_only")
+        rest = list(self.layer_objs)[end:]
+        while rest and isinstance(rest[0], torch.nn.Identity) and (len(self.layer_objs) - len(rest)) not in self.tags:
+            rest = rest[1:]
+        if len(rest) != 1 or not isinstance(rest[0], L.DropoutDense):
+            raise ValueError("train_rows_only needs the concat buffer to feed the final fused dropout+dense layer directly "
+                             "(`...-C1-C2-D0.5-MO` with at most 64 units and the fused classifier on); this set-up puts "
+                             f"{[type(m).__name__ for m in rest] or 'nothing'} behind it -- units > 64 and --no_fused_classifier "
+                             "are not covered: drop --train_rows_only")
 
     @staticmethod
     def _same_in_both_modes(layer) -> bool:
@@ -681,8 +734,18 @@ class H2GCN(torch.nn.Module):
         return None
 
     def forward(self, adj, inputs, adjhops, return_before: int = 0, execute_after: int = 0, tagged_out: dict = None,
-                fuse: bool = True):
+                fuse: bool = True, rows=None):
         n_layers = len(self.layer_objs)
+        if rows is not None:
+            if not self.train_rows_only:
+                raise ValueError("forward(rows=...) needs a model built with train_rows_only=True")
+            if hasattr(adjhops, "fused_propagation"):
+                raise ValueError("train_rows_only does not cover row-partitioned hops (ShardedHops): run on one GPU or call "
+                                 "the model without rows=")
+            if (not fuse or adjhops is None or adjhops.n_rows != adjhops.n_cols or return_before not in (0, n_layers)
+                    or execute_after > self.fused[0]):
+                raise ValueError("train_rows_only runs the fused propagation block and the final classifier only (square hop "
+                                 "matrices, fuse=True, the whole network): call the model without rows= for this")
         if return_before <= 0:
             return_before = n_layers + return_before
         if execute_after < 0:
@@ -712,6 +775,10 @@ class H2GCN(torch.nn.Module):
                 sharded_hops = hasattr(adjhops, "fused_propagation")
                 propagate = adjhops.fused_propagation if sharded_hops else functools.partial(
                     L.fused_propagation, adjhops, private_grad=self._buffer_grad_is_private(end), **({"dtype": torch.bfloat16} if bf16 else {}))
+                if rows is not None:   # propagation + final classifier on the selected rows, one autograd node
+                    def propagate(r0, K_, out=None, reuse=False):
+                        return L.fused_propagation_classify_rows(adjhops, rows, r0, K_, self.layer_objs[-1], out=out, reuse=reuse,
+                                                                 dtype=self.embedding_dtype)
                 if self.reuse_propagation and inputs.is_cuda:
                     # (row-partitioned runs: every rank takes the same branch -- the decision depends only on the call
                     # sequence, which is the same on all ranks)
@@ -735,6 +802,8 @@ class H2GCN(torch.nn.Module):
                         inputs = propagate(inputs, K)
                 else:
                     inputs = propagate(inputs, K)
+                if rows is not None:
+                    return inputs          # the compact logits [m, units]: the classifier was the last layer
                 skip_until = end
                 w0 = tagged[tags[0]].shape[1]
                 H = adjhops.n_hops

@@ -446,6 +446,46 @@ int h2gcn_dropout_dense_backward_bf16(const uint16_t* X_dev, int64_t ldx, int64_
                                       const float* G_dev, int64_t ldg, float keep_prob, uint64_t seed, const int64_t* step_dev,
                                       int dx_dtype, void* dX_dev, int64_t lddx, float* dW_dev, void* workspace_dev,
                                       size_t workspace_bytes, void* stream);
+/*
+ * The four calls restricted to a SELECTION of rows (an additive extension of ABI 5: look the symbols up before calling a build
+ * that may predate them).  A semi-supervised loss lives on the labelled rows only, so its logit gradient is zero everywhere
+ * else: these calls compute the logits of, and the gradient through, n_sel selected rows and touch no other row of X.
+ * Arguments: those of the full calls, followed by
+ *   rows_dev  int32 [n_sel], ASCENDING and UNIQUE, every entry in [0, n_rows) -- guaranteed by the caller (not checked on the
+ *             device; h2gcn_amd's HopPlan.select_rows builds and checks such a list)
+ *   n_sel     its length (0 <= n_sel <= n_rows; 0: dW is zero-filled, nothing else is written)
+ * X stays the full [n_rows, K] matrix; Z, G and dX are COMPACT, one row per list entry.  With r = rows_dev[i]:
+ *     forward    Z_c[i, c]  = sum_k D[r, k] * W[k, c] + bias[c]                         Z_c  fp32 [n_sel, C], row stride ldz
+ *     backward   dX_c[i, k] = keep(r, k) ? (sum_c G_c[i, c] * W[k, c]) / keep_prob : 0  G_c  fp32 [n_sel, C], row stride ldg
+ *                dW[k, c]   = sum_i D[rows_dev[i], k] * G_c[i, c]                       dX_c [n_sel, K], row stride lddx, or NULL
+ * The dropout mask is keyed by the ORIGINAL row r (gid = r * ceil(K / 4) + k / 4), not by i, and every summation over k and c
+ * runs in the full call's order.  Hence, for fp32 and bf16 X alike:
+ *   Z_c    bit-identical to rows rows_dev[] of the full call's Z
+ *   dX_c   bit-identical to rows rows_dev[] of the full call's dX when that call gets G_c scattered into a zero [n_rows, C] G
+ *   dW     deterministic (fixed-order reduction over the list); equal to the full call's dW on the scattered G up to the
+ *          summation tree over rows, not bit for bit
+ * The small-operand rule (h2gcn_dropout_dense_small_rows) applies to n_sel, and the workspace is
+ * h2gcn_dropout_dense_workspace_bytes(n_sel, K, C).  Arguments are validated before the device is touched -- a negative
+ * n_sel or n_rows, n_sel > n_rows, a NULL rows_dev with n_sel > 0, a NULL operand and the layout rules of the full calls give
+ * H2GCN_ERR_INVALID_ARGUMENT with a message that names the argument.  hipGraph capture: no condition (nothing is allocated,
+ * rows_dev is read by the kernels only).
+ */
+int h2gcn_dropout_dense_rows_f32(const float* X_dev, int64_t ldx, int64_t n_rows, int32_t k, const float* W_dev, int32_t c,
+                                 const float* bias_dev, float keep_prob, uint64_t seed, const int64_t* step_dev,
+                                 float* Z_dev, int64_t ldz, void* workspace_dev, size_t workspace_bytes, void* stream,
+                                 const int32_t* rows_dev, int64_t n_sel);
+int h2gcn_dropout_dense_rows_bf16(const uint16_t* X_dev, int64_t ldx, int64_t n_rows, int32_t k, const float* W_dev, int32_t c,
+                                  const float* bias_dev, float keep_prob, uint64_t seed, const int64_t* step_dev,
+                                  float* Z_dev, int64_t ldz, void* workspace_dev, size_t workspace_bytes, void* stream,
+                                  const int32_t* rows_dev, int64_t n_sel);
+int h2gcn_dropout_dense_backward_rows_f32(const float* X_dev, int64_t ldx, int64_t n_rows, int32_t k, const float* W_dev, int32_t c,
+                                          const float* G_dev, int64_t ldg, float keep_prob, uint64_t seed, const int64_t* step_dev,
+                                          float* dX_dev, int64_t lddx, float* dW_dev, void* workspace_dev, size_t workspace_bytes,
+                                          void* stream, const int32_t* rows_dev, int64_t n_sel);
+int h2gcn_dropout_dense_backward_rows_bf16(const uint16_t* X_dev, int64_t ldx, int64_t n_rows, int32_t k, const float* W_dev, int32_t c,
+                                           const float* G_dev, int64_t ldg, float keep_prob, uint64_t seed, const int64_t* step_dev,
+                                           int dx_dtype, void* dX_dev, int64_t lddx, float* dW_dev, void* workspace_dev,
+                                           size_t workspace_bytes, void* stream, const int32_t* rows_dev, int64_t n_sel);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Masked softmax cross-entropy and masked accuracy (reference h2gcn/models/_metrics.py:8-25; called per mask by train_step /

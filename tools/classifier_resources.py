@@ -1,7 +1,8 @@
 """Register / scratch / occupancy table of the classifier kernels (compiler remarks; no GPU needed): the fp32 instantiations of
-classifier.hip and the bf16 ones of classifier_bf16.hip, one line per kernel, element type of X / dX last.
+classifier.hip, the bf16 ones of classifier_bf16.hip and the row-selected ones of classifier_rows.hip ("rows"), one line per kernel,
+element type of X / dX last.
 usage: python tools/classifier_resources.py [unit.hip ...] [extra hipcc flags]
-  (default units: h2gcn_amd/csrc/classifier.hip h2gcn_amd/csrc/classifier_bf16.hip; name another file -- e.g. an older
+  (default units: h2gcn_amd/csrc/classifier.hip, classifier_bf16.hip, classifier_rows.hip; name another file -- e.g. an older
    commit's classifier.hip -- to put its table next to this one)"""
 import re
 import subprocess
@@ -13,9 +14,9 @@ ROOT = Path(__file__).resolve().parent.parent
 units = [a for a in sys.argv[1:] if a.endswith(".hip")]
 flags = [a for a in sys.argv[1:] if not a.endswith(".hip")]
 if not units:
-    units = [str(ROOT / "h2gcn_amd/csrc" / u) for u in ("classifier.hip", "classifier_bf16.hip")]
+    units = [str(ROOT / "h2gcn_amd/csrc" / u) for u in ("classifier.hip", "classifier_bf16.hip", "classifier_rows.hip")]
 KERNEL = re.compile(r"(small_fwd_kernel|small_dx_kernel|dropout_dense_fwd_kernel|dropout_dense_dx_kernel|dropout_dense_dw_kernel|"
-                    r"pack_w_fwd_kernel|pack_w_dx_kernel|reduce_dw_kernel)((?:ILi\d+E(?:Li\d+E)?)?)(f|NS_4bf16E)?")
+                    r"pack_w_fwd_kernel|pack_w_dx_kernel|reduce_dw_kernel)((?:ILi\d+E(?:Li\d+E)?)?)(f|NS_4bf16E)?(?:Lb([01])E)?")
 for unit in units:
     with tempfile.TemporaryDirectory() as tmp:
         cmd = ["/opt/rocm/bin/hipcc", "-O3", "-std=c++17", "-fPIC", f"-I{ROOT}/include", f"-I{ROOT}/h2gcn_amd/csrc", "--offload-arch=gfx950",
@@ -33,7 +34,7 @@ for unit in units:
         if not m:
             continue
         ints = re.findall(r"Li(\d+)E", m.group(2))
-        label = m.group(1) + ("<" + ", ".join(ints) + ">" if ints else "") + {None: "", "f": " f32", "NS_4bf16E": " bf16"}[m.group(3)]
+        label = m.group(1) + ("<" + ", ".join(ints) + ">" if ints else "") + {None: "", "f": " f32", "NS_4bf16E": " bf16"}[m.group(3)] + (" rows" if m.group(4) == "1" else "")
         scratch, occ, lds = g(r"ScratchSize \[bytes/lane\]"), g(r"Occupancy \[waves/SIMD\]"), g(r"LDS Size \[bytes/block\]")
         rows.append(f"{label:40s} vgpr {g('VGPRs'):3d} agpr {g('AGPRs'):3d} sgpr {g('SGPRs'):3d} scratch {scratch:3d} occupancy {occ} lds {lds}")
     print("\n".join(sorted(rows)))
