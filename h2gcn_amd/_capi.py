@@ -35,6 +35,7 @@ PLAN_BUILD_TRANSPOSE = 0x1
 PLAN_SKIP_VALIDATION = 0x2
 PLAN_HOST_TRANSPOSE = 0x4
 PLAN_KEEP_PERMUTATION = 0x8
+PLAN_SYMMETRIC_PATTERN = 0x10
 
 #: every symbol include/h2gcn_hip.h declares (tests check the built library exports all of them)
 EXPORTED_SYMBOLS = (
@@ -45,6 +46,8 @@ EXPORTED_SYMBOLS = (
     "h2gcn_plan_destroy",
     "h2gcn_plan_info",
     "h2gcn_plan_set_values",
+    "h2gcn_plan_transpose_sharing",
+    "h2gcn_plan_device_bytes",
     "h2gcn_spmm_hops_f32",
     "h2gcn_spmm_hops_T_f32",
     "h2gcn_plan_schedule",
@@ -184,6 +187,11 @@ def lib() -> C.CDLL:
     if hasattr(L, "h2gcn_plan_segment_classes"):   # (absent from pre-ABI-4 builds loaded for A/B runs)
         L.h2gcn_plan_segment_classes.restype = C.c_int
         L.h2gcn_plan_segment_classes.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_int64, C.c_int32] + [C.POINTER(C.c_int64)] * 3
+    if hasattr(L, "h2gcn_plan_transpose_sharing"):   # (symmetric plans, added within ABI 5)
+        L.h2gcn_plan_transpose_sharing.restype = C.c_int
+        L.h2gcn_plan_transpose_sharing.argtypes = [C.c_void_p, C.c_int]
+        L.h2gcn_plan_device_bytes.restype = C.c_size_t
+        L.h2gcn_plan_device_bytes.argtypes = [C.c_void_p]
     L.h2gcn_spmm_workspace_bytes.restype = C.c_size_t
     L.h2gcn_spmm_workspace_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int32]
     L.h2gcn_spmm_hops_opts_f32.restype = C.c_int
@@ -308,8 +316,8 @@ def lib() -> C.CDLL:
     # An explicitly named ABI-3 or ABI-4 build (H2GCN_HIP_LIBRARY: the interleaved A/B tools time an older kernel) is accepted.  It
     # lacks what later rounds ADDED -- h2gcn_plan_segment_classes, h2gcn_adam_keras_l2_f32 / h2gcn_l2_penalty_*,
     # h2gcn_xchg_allgather_pull_rows (ABI 4), the bf16 launches h2gcn_spmm_hops_bf16 / _T_bf16 (ABI 5), the bf16 classifier
-    # h2gcn_dropout_dense_bf16 / _backward_bf16 and the row-selected h2gcn_dropout_dense_rows_* / _backward_rows_* (added within
-    # ABI 5) -- and every caller of those
+    # h2gcn_dropout_dense_bf16 / _backward_bf16 and the row-selected h2gcn_dropout_dense_rows_* / _backward_rows_* and the symmetric
+    # plans' h2gcn_plan_transpose_sharing / h2gcn_plan_device_bytes (added within ABI 5) -- and every caller of those
     # asks `has()` first: the front end then keeps the l2 penalty in the autograd graph, pulls whole shards, and
     # HopPlan.segment_classes / a bf16 HopPlan launch raise a message instead of an AttributeError.
     if got != ABI_VERSION and not (os.environ.get("H2GCN_HIP_LIBRARY") and got in (3, 4)):

@@ -12,6 +12,19 @@ namespace h2gcn {
 // Records the message behind h2gcn_last_error() for the calling thread and returns `st` as int.
 int fail(h2gcn_status st, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
+// What the mirror pass of H2GCN_PLAN_SYMMETRIC_PATTERN (symmetric.hip) reports for one hop.
+struct MirrorStatus {
+    unsigned long long missing_key;  // row << 32 | col of the first entry (in (row, col) order) without a mirror; ~0: none
+    unsigned flags;                  // kMirror*
+    unsigned pad;
+};
+constexpr unsigned kMirrorValuesDiffer = 1u;  // some vals[partner[e]] differs from vals[e] in its bits
+constexpr unsigned kMirrorUnsorted = 2u;      // a row's columns are not strictly ascending
+constexpr unsigned kMirrorRange = 4u;         // a column id outside [0, n)
+
+hipError_t mirror_pass(int64_t n, int64_t nnz, const int64_t* rowptr, const int32_t* colidx, const float* vals,
+                       uint32_t* partner, float* t_vals, MirrorStatus* status, hipStream_t stream);
+
 }  // namespace h2gcn
 
 #define H2GCN_HIP_TRY(expr)                                                                          \

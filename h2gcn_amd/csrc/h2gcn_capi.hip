@@ -96,8 +96,12 @@ struct h2gcn_plan {
     bool has_transpose = false;
     int device = 0;
     std::vector<HopOperand> fwd;  // A_k       [n_rows x n_cols], caller-owned arrays
-    std::vector<HopOperand> adj;  // A_k^T     [n_cols x n_rows], plan-owned arrays
+    std::vector<HopOperand> adj;  // A_k^T     [n_cols x n_rows], plan-owned arrays (or the caller's: see `sharing`)
     std::deque<DeviceBuf> owned;  // storage behind `adj` (deque: references stay valid on growth)
+    // H2GCN_PLAN_SYMMETRIC_PATTERN, per hop: 0 -- `adj` is plan-owned throughout; 1 -- its rowptr / colidx are the caller's
+    // forward arrays (borrowed: never in `owned`); 2 -- its vals too
+    std::vector<int> sharing;
+    size_t transpose_bytes = 0;   // device bytes behind `owned`
     // long-segment lists are specific to a hop selection; built on first use, then cached
     mutable std::mutex mu;
     mutable std::map<uint64_t, LongList> long_cache;  // key = mask | (adjoint << 32)
@@ -626,6 +630,64 @@ int resolve_mask(const h2gcn_plan* plan, uint32_t hop_mask, uint32_t* out) {
     return H2GCN_OK;
 }
 
+// H2GCN_PLAN_SYMMETRIC_PATTERN: the adjoint operands of a plan whose (square) hop matrices are symmetric in pattern.  The
+// mirror pass (symmetric.hip) verifies the caller's statement for every hop and produces the values of A_k^T in the same walk;
+// rowptr / colidx of the adjoint operand ARE the forward arrays (A^T of a pattern-symmetric A has the same canonical CSR
+// pattern), and so are the values when they turn out bit-symmetric.  Host-side metadata is copied from the forward operand.
+// Everything allocated here sits in a DeviceBuf: a refused plan leaves nothing behind.
+int share_symmetric(h2gcn_plan* plan, bool keep_perm, hipStream_t stream) {
+    using h2gcn::MirrorStatus;
+    const int H = plan->n_hops;
+    const int64_t n = plan->n_rows;
+    std::vector<MirrorStatus> h_status((size_t)H, MirrorStatus{~0ull, 0u, 0u});
+    DeviceBuf d_status;
+    H2GCN_HIP_TRY(hipMalloc(&d_status.p, (size_t)H * sizeof(MirrorStatus)));
+    H2GCN_HIP_TRY(hipMemcpyAsync(d_status.p, h_status.data(), (size_t)H * sizeof(MirrorStatus), hipMemcpyHostToDevice, stream));
+    std::vector<DeviceBuf> t_vals((size_t)H), partner((size_t)H);
+    for (int k = 0; k < H; ++k) {
+        const HopOperand& f = plan->fwd[k];
+        if (f.nnz == 0) continue;
+        H2GCN_HIP_TRY(hipMalloc(&t_vals[k].p, (size_t)f.nnz * sizeof(float)));
+        if (keep_perm) H2GCN_HIP_TRY(hipMalloc(&partner[k].p, (size_t)f.nnz * sizeof(uint32_t)));
+        H2GCN_HIP_TRY(h2gcn::mirror_pass(n, f.nnz, f.rowptr, f.colidx, f.vals, (uint32_t*)partner[k].p, (float*)t_vals[k].p,
+                                         (MirrorStatus*)d_status.p + k, stream));
+    }
+    H2GCN_HIP_TRY(hipMemcpyAsync(h_status.data(), d_status.p, (size_t)H * sizeof(MirrorStatus), hipMemcpyDeviceToHost, stream));
+    H2GCN_HIP_TRY(hipStreamSynchronize(stream));
+    for (int k = 0; k < H; ++k) {
+        const MirrorStatus& ms = h_status[k];
+        if (ms.flags & h2gcn::kMirrorRange)
+            return fail(H2GCN_ERR_BAD_INDEX, "hop %d: a column index lies outside [0, %lld)", k, (long long)n);
+        if (ms.flags & h2gcn::kMirrorUnsorted)
+            return fail(H2GCN_ERR_BAD_INDEX, "hop %d: the column ids of a row are not strictly ascending (H2GCN_PLAN_SYMMETRIC_PATTERN "
+                        "searches rows by column and relies on the documented order)", k);
+        if (ms.missing_key != ~0ull) {
+            const long long r = (long long)(ms.missing_key >> 32), c = (long long)(ms.missing_key & 0xffffffffull);
+            return fail(H2GCN_ERR_BAD_INDEX, "hop %d: entry (%lld, %lld) has no mirror entry (%lld, %lld): pattern not symmetric", k, r, c, c, r);
+        }
+    }
+    plan->adj.resize(H);
+    for (int k = 0; k < H; ++k) {
+        const HopOperand& f = plan->fwd[k];
+        HopOperand& a = plan->adj[k];
+        a = f;   // pattern, segment classes and long rows of A_k^T are those of A_k
+        a.perm = nullptr;
+        const bool own_vals = f.nnz > 0 && (keep_perm || (h_status[k].flags & h2gcn::kMirrorValuesDiffer));
+        plan->sharing[k] = own_vals ? 1 : 2;
+        if (own_vals) {
+            a.vals = (const float*)t_vals[k].p;
+            plan->owned.emplace_back(std::move(t_vals[k]));
+            plan->transpose_bytes += (size_t)f.nnz * sizeof(float);
+        }
+        if (keep_perm && f.nnz > 0) {
+            a.perm = (const uint32_t*)partner[k].p;
+            plan->owned.emplace_back(std::move(partner[k]));
+            plan->transpose_bytes += (size_t)f.nnz * sizeof(uint32_t);
+        }
+    }
+    return H2GCN_OK;   // (unkept t_vals are freed with the vector)
+}
+
 }  // namespace
 
 extern "C" {
@@ -665,6 +727,13 @@ int h2gcn_plan_create(int n_hops, int64_t n_rows, int64_t n_cols, const int64_t*
         if (o.long_row_threshold < 0 || o.rows_per_wave < 0 || o.rows_per_wave > h2gcn::kMaxRowsPerWave)
             return fail(H2GCN_ERR_INVALID_ARGUMENT, "bad tunable (long_row_threshold %d, rows_per_wave %d, max %d)",
                         o.long_row_threshold, o.rows_per_wave, h2gcn::kMaxRowsPerWave);
+        const bool symmetric = (o.flags & H2GCN_PLAN_SYMMETRIC_PATTERN) != 0;
+        if (symmetric && !(o.flags & H2GCN_PLAN_BUILD_TRANSPOSE))
+            return fail(H2GCN_ERR_INVALID_ARGUMENT, "H2GCN_PLAN_SYMMETRIC_PATTERN modifies H2GCN_PLAN_BUILD_TRANSPOSE, which is not set");
+        if (symmetric && (o.flags & H2GCN_PLAN_HOST_TRANSPOSE))
+            return fail(H2GCN_ERR_INVALID_ARGUMENT, "H2GCN_PLAN_SYMMETRIC_PATTERN builds no transpose: it cannot be combined with H2GCN_PLAN_HOST_TRANSPOSE");
+        if (symmetric && n_rows != n_cols)
+            return fail(H2GCN_ERR_INVALID_ARGUMENT, "H2GCN_PLAN_SYMMETRIC_PATTERN needs square operands, got %lld x %lld", (long long)n_rows, (long long)n_cols);
         hipStream_t stream = (hipStream_t)stream_v;
 
         std::unique_ptr<h2gcn_plan> plan(new h2gcn_plan());
@@ -714,6 +783,8 @@ int h2gcn_plan_create(int n_hops, int64_t n_rows, int64_t n_cols, const int64_t*
             op.vals = vals_dev[k];
             op.nnz = h_rowptr[k][n_rows];
             if (op.nnz > 0 && (!op.colidx || !op.vals)) return fail(H2GCN_ERR_INVALID_ARGUMENT, "hop %d: colidx/vals is NULL", k);
+            if (symmetric && op.nnz >= (1LL << 32))
+                return fail(H2GCN_ERR_INVALID_ARGUMENT, "hop %d: H2GCN_PLAN_SYMMETRIC_PATTERN supports < 2^32 nonzeros per hop", k);
             collect_long_rows(h_rowptr[k], n_rows, plan->long_threshold, op.long_rows);
             collect_segment_lengths(h_rowptr[k], n_rows, plan->short_max, plan->long_threshold, op);
             if (!(o.flags & H2GCN_PLAN_SKIP_VALIDATION) && op.nnz > 0) {
@@ -728,7 +799,12 @@ int h2gcn_plan_create(int n_hops, int64_t n_rows, int64_t n_cols, const int64_t*
         H2GCN_HIP_TRY(hipStreamSynchronize(stream));
         if (h_flag) return fail(H2GCN_ERR_BAD_INDEX, "a column index lies outside [0, %lld)", (long long)n_cols);
 
-        if (o.flags & H2GCN_PLAN_BUILD_TRANSPOSE) {
+        plan->sharing.assign(n_hops, 0);
+        if (symmetric) {
+            int st = share_symmetric(plan.get(), (o.flags & H2GCN_PLAN_KEEP_PERMUTATION) != 0, stream);
+            if (st != H2GCN_OK) return st;
+            plan->has_transpose = true;
+        } else if (o.flags & H2GCN_PLAN_BUILD_TRANSPOSE) {
             if (n_rows > 0x7fffffffLL) return fail(H2GCN_ERR_INVALID_ARGUMENT, "transpose needs n_rows < 2^31");
             plan->adj.resize(n_hops);
             for (int k = 0; k < n_hops; ++k) {
@@ -753,6 +829,7 @@ int h2gcn_plan_create(int n_hops, int64_t n_rows, int64_t n_cols, const int64_t*
                     plan->owned.emplace_back(); plan->owned.back().p = t_ci;
                     plan->owned.emplace_back(); plan->owned.back().p = t_va;
                     plan->owned.emplace_back(); plan->owned.back().p = t_perm;
+                    plan->transpose_bytes += (size_t)(n_cols + 1) * sizeof(int64_t) + (size_t)nnz * (t_perm ? 12 : 8);
                     H2GCN_HIP_TRY(hipMemcpy(t_rowptr.data(), t_rp, (n_cols + 1) * sizeof(int64_t), hipMemcpyDeviceToHost));
                 } else if (st == -3) {
                     return fail(H2GCN_ERR_OUT_OF_MEMORY, "transposition of hop %d: %s", k, terr.c_str());
@@ -781,6 +858,7 @@ int h2gcn_plan_create(int n_hops, int64_t n_rows, int64_t n_cols, const int64_t*
                         H2GCN_HIP_TRY(hipMalloc(&d_va.p, nnz * sizeof(float)));
                         H2GCN_HIP_TRY(hipMemcpy(d_va.p, t_val.data(), nnz * sizeof(float), hipMemcpyHostToDevice));
                     }
+                    plan->transpose_bytes += (size_t)(n_cols + 1) * sizeof(int64_t) + (size_t)nnz * 8;
                     t_rp = (int64_t*)d_rp.p;
                     t_ci = (int32_t*)d_ci.p;
                     t_va = (float*)d_va.p;
@@ -859,6 +937,22 @@ int h2gcn_plan_info(const h2gcn_plan_t* plan, int hop, int64_t* n_rows, int64_t*
     if (n_long_segments) *n_long_segments = (int64_t)plan->fwd[hop].long_rows.size();
     if (has_transpose) *has_transpose = plan->has_transpose ? 1 : 0;
     return H2GCN_OK;
+}
+
+int h2gcn_plan_transpose_sharing(const h2gcn_plan_t* plan, int hop) {
+    if (!plan) return fail(H2GCN_ERR_INVALID_ARGUMENT, "plan is NULL");
+    if (hop < 0 || hop >= plan->n_hops) return fail(H2GCN_ERR_INVALID_ARGUMENT, "hop %d outside 0..%d", hop, plan->n_hops - 1);
+    return plan->sharing[(size_t)hop];
+}
+
+size_t h2gcn_plan_device_bytes(const h2gcn_plan_t* plan) {
+    if (!plan) return 0;
+    std::lock_guard<std::mutex> lock(plan->mu);
+    size_t bytes = plan->transpose_bytes;
+    for (const auto& kv : plan->long_cache) bytes += (size_t)kv.second.n * sizeof(int64_t);
+    for (const auto& kv : plan->class_cache)
+        if (kv.second.built) bytes += (size_t)(kv.second.n_short + kv.second.n_med) * sizeof(int32_t);
+    return bytes;
 }
 
 namespace {

@@ -140,16 +140,23 @@ class PlanetoidData:
         return HopPlan.from_scipy([f], device, build_transpose=build_transpose, keep_permutation=True)  # SparseDropout
 
     def get_tensors(self, device, adj_norm_hops: Optional[Sequence[str]] = None, norm: str = operands.SYM_NORMALIZED,
-                    build_transpose: bool = True, host_hops: bool = False, shard=None) -> dict:
+                    build_transpose: bool = True, host_hops: bool = False, shard=None,
+                    symmetric_hops: bool = False) -> dict:
         """``adj`` / ``features`` / ``adj_hops`` as device operands + dense label/mask tensors (keys as the
         reference's ``tensors`` namespace: ``H2GCN.py:66,77-79``).
 
         ``shard = (rank, world)``: row-partitioned run -- this rank gets rows ``[r0, r1)`` of the features, of every
-        hop matrix (as :class:`~h2gcn_amd.partition.ShardedHops`) and of the labels/masks."""
+        hop matrix (as :class:`~h2gcn_amd.partition.ShardedHops`) and of the labels/masks.
+
+        ``symmetric_hops``: build ``adj_hops`` as a symmetric plan (``HopPlan(symmetric_pattern=True)``): the backward runs on
+        the forward arrays instead of a transposed copy.  The rings of an undirected graph qualify (the library verifies it);
+        one-GPU plans only."""
         import torch
 
         from ..hops import HopPlan
 
+        if symmetric_hops and shard is not None:
+            raise ValueError("symmetric_hops covers one-GPU plans (a row block of a symmetric matrix is not square)")
         if shard is not None:
             return self._get_tensors_sharded(device, adj_norm_hops, norm, shard)
         t = {}
@@ -157,10 +164,10 @@ class PlanetoidData:
         t["adj"] = HopPlan.from_scipy([self.sparse_adj], device)
         if adj_norm_hops and host_hops:      # scipy SpGEMM on the host, as the reference does
             hops = operands.build_adj_norm_hops(self.sparse_adj, adj_norm_hops, norm)
-            t["adj_hops"] = HopPlan.from_scipy(hops, device, build_transpose=build_transpose)
+            t["adj_hops"] = HopPlan.from_scipy(hops, device, build_transpose=build_transpose, symmetric_pattern=symmetric_hops)
         elif adj_norm_hops:                  # exact-k-hop rings grown on the GPU (bit-identical operands)
             rp, ci, va, n = operands.build_adj_norm_hops_device(self.sparse_adj, adj_norm_hops, norm, device)
-            t["adj_hops"] = HopPlan(rp, ci, va, n, build_transpose=build_transpose)
+            t["adj_hops"] = HopPlan(rp, ci, va, n, build_transpose=build_transpose, symmetric_pattern=symmetric_hops)
         else:
             t["adj_hops"] = None
         for name in ("y_all", "y_train", "y_val", "y_test"):

@@ -49,13 +49,18 @@ class SyntheticShapeData:
     def adj_remove_eye(self):           # generated without self loops
         pass
 
-    def get_tensors(self, device, adj_norm_hops=None, norm=None, build_transpose: bool = True, shard=None, **_):
+    def get_tensors(self, device, adj_norm_hops=None, norm=None, build_transpose: bool = True, shard=None,
+                    symmetric_hops: bool = False, **_):
+        """``symmetric_hops``: forwarded to :class:`HopPlan` (``symmetric_pattern``).  The random operands generated here are
+        not symmetric, so the library's refusal -- the first entry without a mirror -- is what the caller sees."""
         import torch
 
         from .. import synth
         from ..hops import HopPlan
         from ..partition import RowPartition, ShardedHops
 
+        if symmetric_hops and shard is not None:
+            raise ValueError("symmetric_hops covers one-GPU plans (a row block of a symmetric matrix is not square)")
         n = self.num_samples
         rank, world = shard if shard is not None else (0, 1)
         part = RowPartition.equal(n, world)
@@ -63,7 +68,8 @@ class SyntheticShapeData:
         seeds = (synth.SEED_A1, synth.SEED_A2)
         degs = synth.hop_degrees(self.cfg, seeds)
         csr = [synth.synth_hop_rows(degs[k], n, seeds[k], r0, r1, device) for k in range(2)]
-        plan = HopPlan([c[0] for c in csr], [c[1] for c in csr], [c[2] for c in csr], n, build_transpose=build_transpose)
+        plan = HopPlan([c[0] for c in csr], [c[1] for c in csr], [c[2] for c in csr], n, build_transpose=build_transpose,
+                       symmetric_pattern=symmetric_hops)
         t = {"adj": None, "partition": part}
         t["adj_hops"] = plan if shard is None else ShardedHops(plan, n, device, partition=part)
         t["features"] = synth.synth_features(self.feature_dim, synth.SEED_X, r0, r1, device)

@@ -52,13 +52,18 @@ class HopPlan:
     build_transpose : also build ``A_k^T`` on the device (needed for ``backward``)
     long_row_threshold, rows_per_wave, variant, slice_cols : schedule tunables (0 = library default)
     validate : run the one-time column-range check (TensorFlow validates indices per call; this once)
+    symmetric_pattern : the caller states that every ``A_k`` is square and stores ``(j, i)`` exactly when it stores ``(i, j)``
+        (the adjacency rings of an undirected graph).  With ``build_transpose=True`` the backward then runs on these very
+        arrays: no transposed copy is built or held (``H2GCN_PLAN_SYMMETRIC_PATTERN``).  The library verifies the statement
+        on the device and refuses an operand that breaks it, naming the first entry without a mirror; results are bit for bit
+        those of a plan with built transposes.  See :attr:`transpose_sharing` and :meth:`device_bytes`.
     """
 
     def __init__(self, rowptr: Sequence[torch.Tensor], colidx: Sequence[torch.Tensor],
                  vals: Sequence[torch.Tensor], n_cols: int, *, build_transpose: bool = False,
                  long_row_threshold: int = 0, rows_per_wave: int = 0, variant: int = 0,
                  slice_cols: int = 0, validate: bool = True, host_transpose: bool = False,
-                 keep_permutation: bool = False):
+                 keep_permutation: bool = False, symmetric_pattern: bool = False):
         H = len(rowptr)
         _require(1 <= H <= _capi.MAX_HOPS, f"need 1..{_capi.MAX_HOPS} hop matrices, got {H}")
         _require(len(colidx) == H and len(vals) == H, "rowptr/colidx/vals lists differ in length")
@@ -74,6 +79,12 @@ class HopPlan:
             _require(rp.dim() == 1 and rp.numel() == n_rows + 1, f"hop {k}: rowptr has {rp.numel()} entries, expected {n_rows + 1}")
             _require(ci.dim() == 1 and va.dim() == 1 and ci.numel() == va.numel(), f"hop {k}: colidx/vals sizes differ")
             _require(rp.is_contiguous() and ci.is_contiguous() and va.is_contiguous(), f"hop {k}: operands must be contiguous")
+        if symmetric_pattern:
+            _require(build_transpose, "symmetric_pattern=True modifies build_transpose=True, which is not set")
+            _require(not host_transpose, "symmetric_pattern=True builds no transpose: it cannot be combined with host_transpose=True")
+            _require(n_rows == int(n_cols), f"symmetric_pattern=True needs square operands, got {n_rows} x {int(n_cols)}")
+            if not _capi.has("h2gcn_plan_transpose_sharing"):   # (it would ignore the unknown flag bit silently)
+                raise RuntimeError(f"{_capi.library_path()} predates symmetric plans (H2GCN_PLAN_SYMMETRIC_PATTERN)")
         # the schedule tunables, so that select_rows can build its sub-plan the same way
         self._tunables = dict(long_row_threshold=long_row_threshold, rows_per_wave=rows_per_wave, variant=variant, slice_cols=slice_cols)
         self.n_hops = H
@@ -101,7 +112,8 @@ class HopPlan:
         opts.struct_size = C.sizeof(_capi.PlanOpts)
         opts.flags = ((_capi.PLAN_BUILD_TRANSPOSE if build_transpose else 0) | (0 if validate else _capi.PLAN_SKIP_VALIDATION)
                       | (_capi.PLAN_HOST_TRANSPOSE if host_transpose else 0)
-                      | (_capi.PLAN_KEEP_PERMUTATION if keep_permutation and build_transpose else 0))
+                      | (_capi.PLAN_KEEP_PERMUTATION if keep_permutation and build_transpose else 0)
+                      | (_capi.PLAN_SYMMETRIC_PATTERN if symmetric_pattern else 0))
         opts.long_row_threshold = int(long_row_threshold)
         opts.rows_per_wave = int(rows_per_wave)
         opts.variant = int(variant)
@@ -158,7 +170,8 @@ class HopPlan:
 
         The sub-CSR is built on the device with torch ops (row-length gather, cumsum, segmented index arithmetic); it keeps
         the per-row column order and the values of this plan, so its launches give the bits of a plan built from the same
-        sub-matrices.  One-off set-up (it synchronises: the checks and the sub-matrix sizes are read back) -- call it before
+        sub-matrices.  ``A_k[rows, :]`` is not square: the sub-plan of a ``symmetric_pattern`` plan builds its own transpose like
+        any other.  One-off set-up (it synchronises: the checks and the sub-matrix sizes are read back) -- call it before
         any hipGraph capture, never inside one.
 
         Memory: the sub-plan holds its own copy of the selected rows' column ids and values, and of their transpose when
@@ -208,6 +221,28 @@ class HopPlan:
                                       C.byref(n_long), C.byref(has_t)))
         return dict(n_rows=n_rows.value, n_cols=n_cols.value, nnz=nnz.value, n_long_segments=n_long.value,
                     has_transpose=bool(has_t.value))
+
+    @property
+    def transpose_sharing(self) -> list:
+        """Per hop, what the backward's operand shares with the forward arrays: ``"none"`` (a built transpose, or no transpose),
+        ``"indices"`` or ``"indices+values"`` (``symmetric_pattern`` plans; the values are shared when they are bit-symmetric and
+        ``keep_permutation`` is off)."""
+        if not _capi.has("h2gcn_plan_transpose_sharing"):
+            return ["none"] * self.n_hops
+        L = _capi.lib()
+        out = []
+        for k in range(self.n_hops):
+            v = L.h2gcn_plan_transpose_sharing(self._handle, k)
+            _capi.check(v)
+            out.append(("none", "indices", "indices+values")[v])
+        return out
+
+    def device_bytes(self) -> int:
+        """Device memory the plan owns now, in bytes: transposed arrays, permutations, a symmetric plan's transposed values, and
+        the row lists built so far -- never the operand arrays it borrows (``h2gcn_plan_device_bytes``)."""
+        if not _capi.has("h2gcn_plan_device_bytes"):
+            raise RuntimeError(f"{_capi.library_path()} predates h2gcn_plan_device_bytes")
+        return int(_capi.lib().h2gcn_plan_device_bytes(self._handle))
 
     def schedule(self, d: int, ld_src: Optional[int] = None, hops=None, adjoint: bool = False) -> dict:
         """What a launch at feature width ``d`` (source row stride ``ld_src``, default contiguous) would do."""

@@ -54,6 +54,13 @@ def add_subparser_args(parser):
                    help="run the training step's classifier and backward pass on the labelled rows only (the loss lives on the "
                         "train mask, so every other row's logit gradient is zero): row-selected classifier kernels and the widest "
                         "adjoint launch on the hop matrices' labelled rows; same results up to summation order (default: off)")
+    g.add_argument("--symmetric_hops", action="store_true",
+                   help="state that the hop matrices are symmetric in pattern (the rings of an undirected graph: every dataset "
+                        "loaded through adjacency lists) and run the backward pass on the forward arrays instead of building and "
+                        "holding a transposed copy of every hop: same bits, half the plan's memory under --adj_norm sym (the "
+                        "values are shared too), a quarter less under rw (index sharing only).  The library verifies the "
+                        "statement when the plan is built and refuses operands that break it; one-GPU runs only, combines with "
+                        "--embedding_dtype bfloat16, --train_rows_only and hipGraph replay (default: off)")
     g.add_argument("--sparse_dropout_at_eval", action="store_true",
                    help="reproduce the reference's SparseDropout, which Keras never switches off (it drops sparse feature "
                         "values during evaluation as well); default: inactive in evaluation like every other dropout")
@@ -85,8 +92,10 @@ def preprocessing_data(args, adj_norm_hops=None):
         dataset.row_normalize_features()
     dataset.adj_remove_eye()
     shard = (dist.get_rank(), dist.get_world_size()) if _is_sharded() else None
+    # (the keyword travels only when the option is on: dataset plugins that predate it keep working)
+    symmetric = {"symmetric_hops": True} if getattr(args, "symmetric_hops", False) else {}
     args.objects["tensors"] = dataset.get_tensors(torch.device(args._device), adj_norm_hops=adj_norm_hops,
-                                                  norm=args.adj_norm, shard=shard)
+                                                  norm=args.adj_norm, shard=shard, **symmetric)
 
 
 def _is_sharded() -> bool:

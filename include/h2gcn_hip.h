@@ -61,6 +61,10 @@ typedef enum h2gcn_status {
 #define H2GCN_PLAN_KEEP_PERMUTATION 0x8u /* with BUILD_TRANSPOSE: remember which forward entry every transposed entry
                                            came from, so that h2gcn_plan_set_values can refresh A_k^T (+4 B/nonzero) */
 
+#define H2GCN_PLAN_SYMMETRIC_PATTERN 0x10u /* with BUILD_TRANSPOSE: every A_k is square and stores (j, i) exactly when it stores
+                                           (i, j); the adjoint then runs on the caller's arrays, no transposed copy is built
+                                           (verified at creation -- see h2gcn_plan_create)                                   */
+
 /* Tunables of the CSR-adaptive schedule.  Zero in a field means "library default". */
 typedef struct h2gcn_plan_opts {
     uint32_t struct_size;        /* = sizeof(h2gcn_plan_opts), for forward compatibility                   */
@@ -122,6 +126,27 @@ int h2gcn_device_count(void);
  *
  * Index validity (monotone rowptr, 0 <= col < n_cols) is checked here, once -- not per launch.  TensorFlow's
  * CPU kernel reports out-of-range indices as InvalidArgument at run time; this returns H2GCN_ERR_BAD_INDEX.
+ *
+ * H2GCN_PLAN_SYMMETRIC_PATTERN (opt-in; modifies H2GCN_PLAN_BUILD_TRANSPOSE).  The caller states that every A_k is square and
+ * symmetric in PATTERN -- what the adjacency rings of an undirected graph are.  A^T of such a matrix has the row pointers and
+ * column ids of A itself, so the adjoint operand of hop k aliases rowptr_dev[k] / colidx_dev[k]: no radix transposition runs and
+ * no transposed index arrays are stored.  Everything that works on a plan with built transposes works unchanged (adjoint
+ * launches, h2gcn_plan_schedule / h2gcn_plan_segment_classes with adjoint = 1, the adjoint row lists; h2gcn_plan_info reports
+ * has_transpose = 1), and the adjoint's arrays hold exactly what the transposition would have produced: the same bits come out.
+ *   The statement is always verified -- by the pass that also constructs what is left to construct.  For every stored entry
+ *   e = (i, j) a device kernel binary-searches row j for column i (this relies on the ascending column order of the layout
+ *   above, which the pass checks too, strictly); the position found is partner[e], and vals[partner[e]] is the value of
+ *   entry e of A_k^T.  H2GCN_PLAN_SKIP_VALIDATION still skips only the separate column-range check.
+ *   Values, per hop:  bit-symmetric (bits(vals[partner[e]]) == bits(vals[e]) for all e, e.g. SYM normalisation) and no
+ *   H2GCN_PLAN_KEEP_PERMUTATION: the adjoint aliases vals_dev[k] as well, the plan owns nothing per nonzero.  Otherwise (e.g.
+ *   RW normalisation) the plan owns t_vals[e] = vals[partner[e]], 4 B per nonzero.  With H2GCN_PLAN_KEEP_PERMUTATION the plan
+ *   always owns t_vals and keeps partner (uint32) as the hop's permutation -- "the forward entry transposed entry e came
+ *   from", as for a built transpose -- so h2gcn_plan_set_values works for any new values, symmetric or not.
+ *   Errors:  an entry without a mirror: H2GCN_ERR_BAD_INDEX, "hop 1: entry (12, 40) has no mirror entry (40, 12): pattern not
+ *   symmetric" -- of the lowest such hop, the entry that comes first in (row, col) order (a deterministic function of the
+ *   operands); a row whose columns are not strictly ascending: H2GCN_ERR_BAD_INDEX; n_rows != n_cols, the flag together with
+ *   H2GCN_PLAN_HOST_TRANSPOSE or without H2GCN_PLAN_BUILD_TRANSPOSE, a hop of >= 2^32 nonzeros: H2GCN_ERR_INVALID_ARGUMENT.
+ *   A refused creation leaves nothing allocated.
  */
 int h2gcn_plan_create(int n_hops, int64_t n_rows, int64_t n_cols,
                       const int64_t* const* rowptr_dev, const int32_t* const* colidx_dev,
@@ -138,12 +163,24 @@ void h2gcn_plan_destroy(h2gcn_plan_t* plan);
  * (dropped entries as explicit zeros) and points the plan at them; transposed operands are refreshed on `stream`
  * (needs H2GCN_PLAN_KEEP_PERMUTATION).  `vals_dev` must stay alive like the original array.  This MUTATES the plan:
  * it must not run concurrently with launches of the same plan on other streams.
+ * Plans created with H2GCN_PLAN_SYMMETRIC_PATTERN: the same rule -- with H2GCN_PLAN_KEEP_PERMUTATION the plan-owned values of
+ * A_k^T are refreshed through the mirror positions (the new values need not be symmetric; the PATTERN is what was verified),
+ * without it the call fails as on any plan with transposed operands, whether or not the adjoint aliased the old values.
  */
 int h2gcn_plan_set_values(h2gcn_plan_t* plan, int hop, const float* vals_dev, void* stream);
 
 /* Introspection (for reports and tests).  Any out pointer may be NULL. */
 int h2gcn_plan_info(const h2gcn_plan_t* plan, int hop, int64_t* n_rows, int64_t* n_cols, int64_t* nnz,
                     int64_t* n_long_segments, int32_t* has_transpose);
+
+/* What the adjoint operand of hop `hop` shares with the caller's forward arrays: 0 = nothing (built transpose, or a plan without
+ * transposes), 1 = rowptr and colidx, 2 = rowptr, colidx and vals (see H2GCN_PLAN_SYMMETRIC_PATTERN).  Negative: h2gcn_status. */
+int h2gcn_plan_transpose_sharing(const h2gcn_plan_t* plan, int hop);
+
+/* Device memory the plan owns at this moment, in bytes: transposed arrays, permutations, the values of A_k^T of a symmetric
+ * plan, and the device row lists built so far (they grow with the first launch of a hop selection).  Never the caller's
+ * arrays.  0 for NULL. */
+size_t h2gcn_plan_device_bytes(const h2gcn_plan_t* plan);
 
 /* The schedule a launch of this plan would use for feature width d and source row stride ld_src (reports, tests):
  * columns per slice of the slice-major schedule, number of slices, segment walk (0 = wave per segment, 1 = the same
