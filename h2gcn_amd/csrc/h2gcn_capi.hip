@@ -1215,6 +1215,40 @@ int spmm_hops(bool adjoint, const h2gcn_plan_t* plan, uint32_t hop_mask, Dense s
 }
 }  // namespace
 
+// The plan as the SDDMM launch of sddmm.hip sees it (capi_internal.h; C++ linkage: called across translation units).
+extern "C++" {
+namespace h2gcn {
+int sddmm_plan_view(const h2gcn_plan* plan, uint32_t hop_mask, SddmmPlanView* out) {
+    if (!plan) return fail(H2GCN_ERR_INVALID_ARGUMENT, "plan is NULL");
+    memset(out, 0, sizeof(*out));
+    const int st = resolve_mask(plan, hop_mask, &out->mask);
+    if (st != H2GCN_OK) return st;
+    out->n_rows = plan->n_rows;
+    out->n_cols = plan->n_cols;
+    out->long_threshold = plan->long_threshold;
+    out->rows_per_wave = plan->rows_per_wave;
+    int s = 0;
+    for (int k = 0; k < plan->n_hops; ++k) {
+        if (!(out->mask & (1u << k))) continue;
+        const HopOperand& op = plan->fwd[k];
+        out->rowptr[s] = op.rowptr;
+        out->colidx[s] = op.colidx;
+        out->nnz[s] = op.nnz;
+        ++s;
+    }
+    out->n_sel = s;
+    return H2GCN_OK;
+}
+
+int sddmm_long_list(const h2gcn_plan* plan, uint32_t mask, hipStream_t stream, const int64_t** list_dev, int* n_long) {
+    const int st = check_device(plan);
+    if (st != H2GCN_OK) return st;
+    CaptureScope capture_scope(stream);
+    return get_long_list(plan, false, mask, list_dev, n_long);
+}
+}  // namespace h2gcn
+}  // extern "C++"
+
 int h2gcn_spmm_hops_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* X, int64_t ldx, int32_t d,
                         float* Y, int64_t ldy_row, int64_t ldy_hop, void* stream_v) {
     return h2gcn_spmm_hops_opts_f32(plan, hop_mask, X, ldx, d, Y, ldy_row, ldy_hop, nullptr, stream_v);

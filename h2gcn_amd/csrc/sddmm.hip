@@ -1,0 +1,322 @@
+// sddmm.hip -- the gradient of the hop aggregation with respect to the stored adjacency values: a sampled dense-dense
+// product over the CSR pattern of every selected hop (SDDMM),
+//
+//     dV_s[e] = sum_c dY[i, s, c] * X[j, c]          for every stored entry e = (i, j) of selected hop s.
+//
+// Stands in for the gradient TensorFlow registers for SparseTensorDenseMatMul wrt the values of its sparse operand (the
+// reference never asks for it: its adjacency is constant; a caller with learned / gated / attention edge weights does).
+// A translation unit of its own: no existing kernel is compiled differently because of it.
+//
+// Mapping (gfx950, wave64; gather-bound like the forward launch, no MFMA, no LDS memory, no atomics):
+//   * ONE lane geometry: 16 lanes x 4 columns cover a 64-column block of a feature row, so the 4 lane groups of a wave
+//     gather 4 neighbour rows of X per load instruction (16 bytes per lane fp32, 8 bytes bf16);
+//   * a wave walks the (row, hop) segments of its row tile (the forward's block -> row-tile map: every XCD gets a contiguous
+//     row range; the wave's row pointers come from one wave-wide load).  Per segment it keeps the dY row in registers -- lane
+//     (group, quad q) holds columns 4q..4q+3 of up to four 64-column blocks, replicated over the groups;
+//   * column ids are fetched 64 at a time -- lane (group gi, quad q) loads entry 4q + gi of the chunk, so the 64 lanes read
+//     the chunk's 256 bytes once -- and handed to the group's lanes with ds_bpermute; in round r group gi serves entry
+//     4r + gi: a chunk of n entries takes ceil(n / 4) rounds, whatever n;
+//   * rounds are issued in batches: all gathers of a batch (8 load instructions fp32 = 8 KiB per wave; bf16 16, or the 8
+//     rounds of a one-block row) go out before the first multiply;
+//   * the 16 quads of a block are summed by an xor butterfly in DPP (one row of 16 lanes), the lane with q == r keeps the
+//     entry's result, and after the last round the 64 results of the chunk leave with ONE store instruction into the chunk's
+//     256 bytes of dV;
+//   * segments with >= long_row_threshold nonzeros belong to workgroups of their own (the plan's forward long-segment list):
+//     the 4 waves take 64-entry chunks in turn.  Every result belongs to one entry, so nothing is summed across waves.
+//
+// Arithmetic (documented in include/h2gcn_hip.h): one order per element, a function of d alone -- see dot_block / walk_chunk.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <algorithm>
+#include <cstring>
+#include <type_traits>
+
+#include "h2gcn_hip.h"
+#include "capi_internal.h"
+
+namespace h2gcn {
+namespace sddmm {
+
+constexpr int kWave = 64;
+constexpr int kWavesPerBlock = 4;
+constexpr int kBlock = kWave * kWavesPerBlock;
+constexpr int kNumXcd = 8;
+constexpr int kBlockCols = 64;   // columns one lane group covers per load: 16 lanes x 4
+constexpr int kMaxBlocks = 4;    // 64-column blocks of the dY row a lane keeps in registers (one column pass: 256 columns)
+
+struct bf16 {
+    uint16_t bits;
+};
+
+struct Params {
+    const int64_t* rowptr[H2GCN_MAX_HOPS];   // the selected hops, packed
+    const int32_t* colidx[H2GCN_MAX_HOPS];
+    float* dvals[H2GCN_MAX_HOPS];
+    int n_sel;
+    int d;
+    int64_t n_rows;
+    const void* g;   // dY, [n_rows, n_sel, d] through ldg_row / ldg_hop (elements)
+    int64_t ldg_row, ldg_hop;
+    const void* x;   // X, [n_cols, d] through ldx
+    int64_t ldx;
+    const int64_t* long_list;   // row << 4 | s per long segment
+    int n_long;
+    int long_threshold;
+    int rows_per_wave;
+    int64_t n_tiles, tiles_per_xcd;
+};
+
+typedef float float4u __attribute__((ext_vector_type(4), aligned(4)));     // 16-byte loads need only dword alignment on gfx950
+typedef uint32_t uint2u __attribute__((ext_vector_type(2), aligned(4)));
+
+struct Quad {
+    float v[4];
+};
+
+// Columns c0 .. c0+3 of a feature row, widened to fp32; columns >= d read as +0 and are never loaded.
+__device__ __forceinline__ Quad load_quad(const float* row, int c0, int d) {
+    Quad r;
+    if (c0 + 3 < d) {
+        const float4u t = *reinterpret_cast<const float4u*>(row + c0);
+        r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) r.v[k] = c0 + k < d ? row[c0 + k] : 0.f;
+    }
+    return r;
+}
+// bf16: d is even and every row starts on a dword, so a quad holds 4, 2 or 0 valid columns
+__device__ __forceinline__ Quad load_quad(const bf16* row, int c0, int d) {
+    Quad r;
+    uint32_t lo = 0, hi = 0;
+    if (c0 + 3 < d) {
+        const uint2u t = *reinterpret_cast<const uint2u*>(row + c0);
+        lo = t.x; hi = t.y;
+    } else if (c0 + 1 < d) {
+        lo = *reinterpret_cast<const uint32_t*>(row + c0);
+    }
+    r.v[0] = __uint_as_float(lo << 16); r.v[1] = __uint_as_float(lo & 0xffff0000u);
+    r.v[2] = __uint_as_float(hi << 16); r.v[3] = __uint_as_float(hi & 0xffff0000u);
+    return r;
+}
+
+template <int CTRL>
+__device__ __forceinline__ float dpp_add(float v) {
+    const int o = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false);
+    return v + __int_as_float(o);
+}
+
+// The total of one 64-column block: the quad's value t = g0*x0, then fma(g1, x1, t), fma(g2, x2, t), fma(g3, x3, t), and the 16
+// quads summed by the xor butterfly over lane distances 1, 2, 4, 8 (afterwards all 16 lanes hold the same bits; the partner of
+// the distance-4 / distance-8 step is reached with row_half_mirror / row_ror:8, whose source lanes hold the partner's value).
+__device__ __forceinline__ float dot_block(const Quad& g, const Quad& x) {
+    float t = g.v[0] * x.v[0];
+    t = __builtin_fmaf(g.v[1], x.v[1], t);
+    t = __builtin_fmaf(g.v[2], x.v[2], t);
+    t = __builtin_fmaf(g.v[3], x.v[3], t);
+    t = dpp_add<0xB1>(t);    // quad_perm [1,0,3,2]: lane ^ 1
+    t = dpp_add<0x4E>(t);    // quad_perm [2,3,0,1]: lane ^ 2
+    t = dpp_add<0x141>(t);   // row_half_mirror: the neighbouring group of four lanes (lane ^ 4 up to a permutation of equals)
+    t = dpp_add<0x128>(t);   // row_ror:8: lane ^ 8
+    return t;
+}
+
+// One batch of U rounds of a chunk: group gi serves entry 4r + gi in round r.  FULL: every round of the batch exists.
+template <typename TS, int NB, int U, bool FULL>
+__device__ __forceinline__ void batch(const Params& p, const Quad (&g)[NB], int cbase, int r0, int rounds, int mycol, int lane,
+                                      float& res) {
+    const int q = lane & 15;
+    const TS* x = reinterpret_cast<const TS*>(p.x);
+    Quad xv[U][NB];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        if (FULL || r0 + u < rounds) {
+            const int c = __builtin_amdgcn_ds_bpermute(((lane & 48) + r0 + u) << 2, mycol);
+            const TS* xrow = x + (int64_t)c * p.ldx;
+#pragma unroll
+            for (int b = 0; b < NB; ++b) xv[u][b] = load_quad(xrow, cbase + b * kBlockCols + 4 * q, p.d);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        if (FULL || r0 + u < rounds) {
+#pragma unroll
+            for (int b = 0; b < NB; ++b) {
+                // (blocks that start at or beyond d hold +0 on both sides: they add +0, as the documented order says)
+                const float t = dot_block(g[b], xv[u][b]);
+                if (q == r0 + u) res = res + t;   // block totals in ascending block order, starting from +0
+            }
+        }
+    }
+}
+
+// `count` (1..64) consecutive entries of one segment: cols / out point at the chunk's first entry, grow at the segment's dY row.
+// Column passes of NB blocks each (one pass up to 64 * NB columns); the entry's running total stays in a register across passes.
+template <typename TS, int NB, int U>
+__device__ __forceinline__ void walk_chunk(const Params& p, const TS* grow, const int32_t* cols, int count, float* out, int lane) {
+    const int q = lane & 15, gi = lane >> 4;
+    const int my_n = q * 4 + gi;
+    const int mycol = cols[my_n < count ? my_n : count - 1];
+    const int rounds = (count + 3) >> 2;
+    float res = 0.f;
+    for (int cbase = 0; cbase < p.d; cbase += NB * kBlockCols) {
+        Quad g[NB];
+#pragma unroll
+        for (int b = 0; b < NB; ++b) g[b] = load_quad(grow, cbase + b * kBlockCols + 4 * q, p.d);
+        int r0 = 0;
+        for (; r0 + U <= rounds; r0 += U) batch<TS, NB, U, true>(p, g, cbase, r0, rounds, mycol, lane, res);
+        if (r0 < rounds) batch<TS, NB, U, false>(p, g, cbase, r0, rounds, mycol, lane, res);
+    }
+    if (my_n < count) out[my_n] = res;
+}
+
+__device__ __forceinline__ int64_t readlane64(int64_t v, int src) {
+    const uint32_t lo = __builtin_amdgcn_readlane((int)(uint32_t)v, src);
+    const uint32_t hi = __builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), src);
+    return (int64_t)(((uint64_t)hi << 32) | lo);
+}
+
+template <typename TS, int NB>
+__global__ __launch_bounds__(kBlock) void sddmm_hops_kernel(const Params p) {
+    // rounds per batch: 8 load instructions in flight (fp32: 8 KiB per wave), 16 for bf16 (8 KiB again), at most 8 rounds
+    constexpr int kLoads = std::is_same<TS, bf16>::value ? 16 : 8;
+    constexpr int U = kLoads / NB < 8 ? kLoads / NB : 8;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const TS* g = reinterpret_cast<const TS*>(p.g);
+    if ((int)blockIdx.x < p.n_long) {
+        // ---- a long segment: 64-entry chunks over the 4 waves ----
+        const int64_t e = p.long_list[blockIdx.x];
+        const int64_t row = e >> 4;
+        const int s = (int)(e & 15);
+        const int64_t beg = p.rowptr[s][row], end = p.rowptr[s][row + 1];
+        const TS* grow = g + row * p.ldg_row + (int64_t)s * p.ldg_hop;
+        for (int64_t c = beg + (int64_t)wave * kWave; c < end; c += kBlock) {
+            const int count = (int)(end - c < kWave ? end - c : kWave);
+            walk_chunk<TS, NB, U>(p, grow, p.colidx[s] + c, count, p.dvals[s] + c, lane);
+        }
+        return;
+    }
+    // ---- regular path: XCD-aware tile map, each wave walks rows_per_wave consecutive rows ----
+    const int64_t tb = (int64_t)blockIdx.x - p.n_long;
+    const int64_t tile = (tb % kNumXcd) * p.tiles_per_xcd + tb / kNumXcd;
+    if (tile >= p.n_tiles) return;
+    const int rpw = p.rows_per_wave;
+    const int64_t row0 = (tile * kWavesPerBlock + wave) * rpw;
+    if (row0 >= p.n_rows) return;
+    // the wave's row pointers: lane s * (rpw + 1) + i holds rowptr_s[row0 + i]  ((rpw + 1) * n_sel <= 64: plan invariant)
+    int64_t rp = 0;
+    if (lane < (rpw + 1) * p.n_sel) {
+        const int s = lane / (rpw + 1), i = lane - s * (rpw + 1);
+        const int64_t r = row0 + i < p.n_rows ? row0 + i : p.n_rows;
+        rp = p.rowptr[s][r];
+    }
+    for (int i = 0; i < rpw && row0 + i < p.n_rows; ++i) {
+        for (int s = 0; s < p.n_sel; ++s) {
+            const int64_t beg = readlane64(rp, s * (rpw + 1) + i), end = readlane64(rp, s * (rpw + 1) + i + 1);
+            const int64_t len = end - beg;
+            if (len <= 0 || len >= p.long_threshold) continue;
+            const TS* grow = g + (row0 + i) * p.ldg_row + (int64_t)s * p.ldg_hop;
+            for (int64_t c = beg; c < end; c += kWave) {
+                const int count = (int)(end - c < kWave ? end - c : kWave);
+                walk_chunk<TS, NB, U>(p, grow, p.colidx[s] + c, count, p.dvals[s] + c, lane);
+            }
+        }
+    }
+}
+
+// bf16 arrays: 4-byte aligned base, even strides (elements) and an even width (the rule of the bf16 SpMM launches)
+int check_bf16_layout(const char* what, const void* ptr, int64_t ld_row, int64_t ld_hop, int32_t d) {
+    if (reinterpret_cast<uintptr_t>(ptr) & 3u)
+        return fail(H2GCN_ERR_INVALID_ARGUMENT, "bf16 %s: the base address must be 4-byte aligned", what);
+    if ((ld_row & 1) || (ld_hop & 1))
+        return fail(H2GCN_ERR_INVALID_ARGUMENT, "bf16 %s: row / hop strides must be even (got %lld / %lld elements)", what,
+                    (long long)ld_row, (long long)ld_hop);
+    if (d & 1) return fail(H2GCN_ERR_INVALID_ARGUMENT, "bf16 %s: the feature width d must be even (got %d)", what, d);
+    return H2GCN_OK;
+}
+
+template <typename TS>
+int sddmm_hops(const h2gcn_plan_t* plan, uint32_t hop_mask, const void* dY, int64_t ldg_row, int64_t ldg_hop, const void* X,
+               int64_t ldx, int32_t d, float* const* dvals, void* stream_v) {
+    constexpr bool kBf16 = std::is_same<TS, bf16>::value;
+    try {
+        // every check below comes before the device is touched
+        SddmmPlanView v;
+        int st = sddmm_plan_view(plan, hop_mask, &v);
+        if (st != H2GCN_OK) return st;
+        if (d < 1) return fail(H2GCN_ERR_INVALID_ARGUMENT, "d = %d", d);
+        if (ldx < d) return fail(H2GCN_ERR_INVALID_ARGUMENT, "ldx = %lld < d = %d", (long long)ldx, d);
+        if (ldg_row < d) return fail(H2GCN_ERR_INVALID_ARGUMENT, "ldg_row = %lld < d = %d", (long long)ldg_row, d);
+        if (ldg_hop < 0 || (v.n_sel > 1 && ldg_hop < d))
+            return fail(H2GCN_ERR_INVALID_ARGUMENT, "ldg_hop = %lld < d = %d: the hops' gradients would overlap", (long long)ldg_hop, d);
+        if (kBf16) {
+            if ((st = check_bf16_layout("dY", dY, ldg_row, ldg_hop, d)) != H2GCN_OK) return st;
+            if ((st = check_bf16_layout("X", X, ldx, 0, d)) != H2GCN_OK) return st;
+        }
+        int64_t nnz_sel = 0;
+        for (int s = 0; s < v.n_sel; ++s) nnz_sel += v.nnz[s];
+        if (nnz_sel > 0) {
+            if (!dY) return fail(H2GCN_ERR_INVALID_ARGUMENT, "dY is NULL");
+            if (!X) return fail(H2GCN_ERR_INVALID_ARGUMENT, "X is NULL");
+            if (!dvals) return fail(H2GCN_ERR_INVALID_ARGUMENT, "dvals is NULL");
+            for (int s = 0; s < v.n_sel; ++s)
+                if (v.nnz[s] > 0 && !dvals[s])
+                    return fail(H2GCN_ERR_INVALID_ARGUMENT, "dvals[%d] is NULL (selected hop %d of the launch has %lld nonzeros)", s, s,
+                                (long long)v.nnz[s]);
+        }
+        if (nnz_sel == 0 || v.n_rows == 0) return H2GCN_OK;
+        hipStream_t stream = (hipStream_t)stream_v;
+        Params p;
+        memset(&p, 0, sizeof(p));
+        if ((st = sddmm_long_list(plan, v.mask, stream, &p.long_list, &p.n_long)) != H2GCN_OK) return st;
+        for (int s = 0; s < v.n_sel; ++s) {
+            p.rowptr[s] = v.rowptr[s];
+            p.colidx[s] = v.colidx[s];
+            p.dvals[s] = dvals[s];
+        }
+        p.n_sel = v.n_sel;
+        p.d = d;
+        p.n_rows = v.n_rows;
+        p.g = dY;
+        p.ldg_row = ldg_row;
+        p.ldg_hop = ldg_hop;
+        p.x = X;
+        p.ldx = ldx;
+        p.long_threshold = v.long_threshold;
+        p.rows_per_wave = v.rows_per_wave;
+        const int64_t rows_per_tile = (int64_t)p.rows_per_wave * kWavesPerBlock;
+        p.n_tiles = (p.n_rows + rows_per_tile - 1) / rows_per_tile;
+        p.tiles_per_xcd = (p.n_tiles + kNumXcd - 1) / kNumXcd;
+        const int64_t n_blocks = (int64_t)p.n_long + p.tiles_per_xcd * kNumXcd;
+        if (n_blocks > 0x7fffffffLL) return fail(H2GCN_ERR_INVALID_ARGUMENT, "grid too large (%lld blocks)", (long long)n_blocks);
+        const dim3 grid((unsigned)n_blocks), block(kBlock);
+        // blocks of the dY row a lane keeps: the narrowest geometry that covers d in one column pass, four blocks beyond 256
+        // columns (the bits are the same for all three: the order of summation is a function of d alone)
+        if (d <= kBlockCols) hipLaunchKernelGGL((sddmm_hops_kernel<TS, 1>), grid, block, 0, stream, p);
+        else if (d <= 2 * kBlockCols) hipLaunchKernelGGL((sddmm_hops_kernel<TS, 2>), grid, block, 0, stream, p);
+        else hipLaunchKernelGGL((sddmm_hops_kernel<TS, kMaxBlocks>), grid, block, 0, stream, p);
+        H2GCN_HIP_TRY(hipGetLastError());
+        return H2GCN_OK;
+    } catch (...) {
+        return fail(H2GCN_ERR_INTERNAL, "unexpected exception in sddmm_hops_%s", kBf16 ? "bf16" : "f32");
+    }
+}
+
+}  // namespace sddmm
+}  // namespace h2gcn
+
+extern "C" {
+
+int h2gcn_sddmm_hops_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* dY, int64_t ldg_row, int64_t ldg_hop,
+                         const float* X, int64_t ldx, int32_t d, float* const* dvals, void* stream) {
+    return h2gcn::sddmm::sddmm_hops<float>(plan, hop_mask, dY, ldg_row, ldg_hop, X, ldx, d, dvals, stream);
+}
+
+int h2gcn_sddmm_hops_bf16(const h2gcn_plan_t* plan, uint32_t hop_mask, const uint16_t* dY, int64_t ldg_row, int64_t ldg_hop,
+                          const uint16_t* X, int64_t ldx, int32_t d, float* const* dvals, void* stream) {
+    return h2gcn::sddmm::sddmm_hops<h2gcn::sddmm::bf16>(plan, hop_mask, dY, ldg_row, ldg_hop, X, ldx, d, dvals, stream);
+}
+
+}  // extern "C"

@@ -50,6 +50,8 @@ class HopPlan:
     rowptr, colidx, vals : sequences of H CUDA tensors (int64 ``[n_rows+1]``, int32 ``[nnz]``, float32 ``[nnz]``)
     n_cols : number of columns (rows of the dense operand ``X``)
     build_transpose : also build ``A_k^T`` on the device (needed for ``backward``)
+    keep_permutation : with ``build_transpose``: remember where every transposed entry came from, so that :meth:`set_values`
+        can refresh ``A_k^T`` (kept as the attribute ``keep_permutation``)
     long_row_threshold, rows_per_wave, variant, slice_cols : schedule tunables (0 = library default)
     validate : run the one-time column-range check (TensorFlow validates indices per call; this once)
     symmetric_pattern : the caller states that every ``A_k`` is square and stores ``(j, i)`` exactly when it stores ``(i, j)``
@@ -92,6 +94,8 @@ class HopPlan:
         self.n_cols = int(n_cols)
         self.device = dev
         self.has_transpose = bool(build_transpose)
+        #: the plan can refresh its transposed operands when :meth:`set_values` brings new values
+        self.keep_permutation = bool(keep_permutation and build_transpose)
         # the plan borrows these arrays: keep them alive
         self.rowptr = list(rowptr)
         self.colidx = list(colidx)
@@ -413,6 +417,58 @@ class HopPlan:
                     C.byref(opts) if opts is not None else None, C.c_void_p(stream))
         _capi.check(st)
         return dx
+
+    def sddmm(self, grad: torch.Tensor, x: torch.Tensor, hops=None, out: Optional[Sequence[torch.Tensor]] = None) -> list:
+        """Gradient wrt the stored values: ``dvals[s][e] = sum_c grad[i, s, c] * x[j, c]`` for every stored entry ``e = (i, j)``
+        of selected hop ``s`` -> one contiguous float32 ``[nnz_k]`` tensor per selected hop, in the entry order of
+        ``colidx[k]`` (``h2gcn_sddmm_hops_*``).  The pattern decides: the plan's current values are not read, and no
+        transposed operand is needed.
+
+        ``grad`` ``[n_rows, H_sel, d]`` and ``x`` ``[n_cols, d]`` are both float32 or both bfloat16 (widened exactly; fp32
+        arithmetic and result, bit-identical to the launch on ``.float()`` operands).  Views with a row / hop stride pass
+        through (a slot of a concat buffer); a non-unit last stride is made contiguous.  ``out``: a list of ``H_sel``
+        contiguous float32 ``[nnz_k]`` tensors to overwrite."""
+        h_sel = self.n_selected(hops)
+        _require(grad.dim() == 3 and grad.shape[0] == self.n_rows and grad.shape[1] == h_sel,
+                 f"grad must be [{self.n_rows}, {h_sel}, d], got {tuple(grad.shape)}")
+        d = int(grad.shape[2])
+        _require(d >= 1, "grad needs at least one column")
+        _require(x.dim() == 2 and tuple(x.shape) == (self.n_cols, d), f"x must be [{self.n_cols}, {d}], got {tuple(x.shape)}")
+        _require(grad.dtype in (torch.float32, torch.bfloat16), f"grad must be float32 or bfloat16, got {grad.dtype}")
+        _require(x.dtype == grad.dtype, f"grad and x must have the same dtype (both float32 or both bfloat16), got {grad.dtype} and {x.dtype}")
+        _require(grad.device == self.device and x.device == self.device, f"grad on {grad.device}, x on {x.device}, plan on {self.device}")
+        bf16 = grad.dtype == torch.bfloat16
+        if grad.stride(2) != 1 or grad.stride(0) < d or (h_sel > 1 and grad.stride(1) < d):
+            grad = grad.contiguous()  # e.g. an expanded (stride-0) gradient coming out of a reduction
+        if x.stride(1) != 1 or x.stride(0) < d:
+            x = x.contiguous()
+        sel = list(range(self.n_hops)) if hops is None else sorted({int(h) for h in hops})
+        mask = self._mask(hops)
+        if out is None:
+            out = [torch.empty(self.colidx[k].numel(), dtype=torch.float32, device=self.device) for k in sel]
+        else:
+            out = list(out)
+            _require(len(out) == h_sel, f"out must list {h_sel} tensors (one per selected hop), got {len(out)}")
+            for s, k in enumerate(sel):
+                nnz = self.colidx[k].numel()
+                _require(isinstance(out[s], torch.Tensor) and out[s].dtype == torch.float32 and out[s].device == self.device
+                         and tuple(out[s].shape) == (nnz,) and out[s].is_contiguous(),
+                         f"out[{s}] must be a contiguous float32 [{nnz}] tensor on the plan's device (hop {k})")
+        ld_row, ld_hop = (grad.stride(0) if self.n_rows > 1 else h_sel * d), (grad.stride(1) if h_sel > 1 else d)
+        ldx = x.stride(0) if self.n_cols > 1 else d
+        if bf16:
+            _bf16_layout("grad", grad, d, (ld_row, ld_hop))
+            _bf16_layout("x", x, d, (ldx,))
+        _require(_capi.has("h2gcn_sddmm_hops_f32"), f"{_capi.library_path()} predates the values gradient (h2gcn_sddmm_hops_*)")
+        L = _capi.lib()
+        ptrs = (C.c_void_p * h_sel)(*[t.data_ptr() if t.numel() else None for t in out])
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            fn = L.h2gcn_sddmm_hops_bf16 if bf16 else L.h2gcn_sddmm_hops_f32
+            st = fn(self._handle, mask, C.c_void_p(grad.data_ptr()), ld_row, ld_hop, C.c_void_p(x.data_ptr()), ldx, d,
+                    ptrs, C.c_void_p(stream))
+        _capi.check(st)
+        return out
 
     def __del__(self):
         h = getattr(self, "_handle", None)

@@ -20,8 +20,8 @@ from .hops import HopPlan, RowSelection
 
 class _HopSpMM(torch.autograd.Function):
     """forward: fused multi-hop SpMM; backward: adjoint SpMM on the plan's transposed operands (the gradient
-    TF registers for SparseTensorDenseMatMul wrt its dense input; the gradient wrt the adjacency values, which
-    TF also computes and the reference never uses, is not produced)."""
+    TF registers for SparseTensorDenseMatMul wrt its dense input).  The gradient wrt the adjacency values is
+    :class:`_HopSpMMValues`, reached through ``hop_spmm(..., values=...)``."""
 
     @staticmethod
     def forward(ctx, x: torch.Tensor, plan: HopPlan, hops):
@@ -34,11 +34,91 @@ class _HopSpMM(torch.autograd.Function):
         return ctx.plan.spmm_t(grad_out, hops=ctx.hops), None, None
 
 
-def hop_spmm(adjhops: HopPlan, inputs: torch.Tensor, hops: Optional[Iterable[int]] = None) -> torch.Tensor:
-    """Functional form of :class:`GCNLayer`: ``[n_cols, d] -> [n_rows, H_sel, d]``, differentiable wrt ``inputs``."""
+class _HopSpMMValues(torch.autograd.Function):
+    """The hop SpMM as a function of the dense input AND of the stored values of the hop matrices: forward -- install the given
+    values in the plan (``set_values``), then the fused SpMM; backward -- the adjoint SpMM for the input and the SDDMM launch
+    (``HopPlan.sddmm``) for the values of the hops that want a gradient (the other hops are not part of that launch)."""
+
+    @staticmethod
+    def forward(ctx, x: torch.Tensor, plan: HopPlan, hops, *values):
+        for k, v in enumerate(values):
+            if v is not None:
+                plan.set_values(k, v.detach().contiguous())
+        ctx.plan = plan
+        ctx.hops = hops
+        ctx.sel = tuple(range(plan.n_hops)) if hops is None else hops
+        ctx.version = getattr(plan, "values_version", 0)
+        ctx.save_for_backward(x)
+        return plan.spmm(x, hops=hops)
+
+    @staticmethod
+    def backward(ctx, grad_out: torch.Tensor):
+        plan = ctx.plan
+        if getattr(plan, "values_version", 0) != ctx.version:
+            raise RuntimeError("the plan's values changed between the forward and the backward of hop_spmm(..., values=...) "
+                               "(a set_values call, or another forward with values= on the same plan): the adjoint would run on "
+                               "the wrong values.  Run the backward before the plan's values are replaced")
+        (x,) = ctx.saved_tensors
+        dx = plan.spmm_t(grad_out, hops=ctx.hops) if ctx.needs_input_grad[0] else None
+        # values of hop k are argument 3 + k; only selected hops reach the output
+        want = [k for k in ctx.sel if ctx.needs_input_grad[3 + k]]
+        dvals = [None] * plan.n_hops
+        if want:
+            # the launch over the wanted hops reads their slots of the gradient: a strided view when some hop is left out
+            pos = [ctx.sel.index(k) for k in want]
+            g = _hop_slots(grad_out, pos)
+            for k, dv in zip(want, plan.sddmm(g, x, hops=want)):
+                dvals[k] = dv
+        return (dx, None, None, *dvals)
+
+
+def _hop_slots(grad: torch.Tensor, pos) -> torch.Tensor:
+    """``grad[:, pos, :]`` for ascending hop slots ``pos``: a strided view when the slots are evenly spaced, else a copy."""
+    steps = {b - a for a, b in zip(pos, pos[1:])}
+    if len(steps) <= 1:
+        return grad[:, pos[0]:pos[-1] + 1:(steps.pop() if steps else 1), :]
+    return grad[:, list(pos), :]
+
+
+def _check_values(adjhops: HopPlan, inputs: torch.Tensor, values) -> tuple:
+    values = tuple(values)
+    if len(values) != adjhops.n_hops:
+        raise ValueError(f"values must have one entry per hop of the plan ({adjhops.n_hops}; None keeps a hop's current values), got {len(values)}")
+    for k, v in enumerate(values):
+        if v is None:
+            continue
+        nnz = adjhops.colidx[k].numel()
+        if not isinstance(v, torch.Tensor) or v.dtype != torch.float32 or v.device != adjhops.device or tuple(v.shape) != (nnz,):
+            what = f"{v.dtype} {tuple(v.shape)} on {v.device}" if isinstance(v, torch.Tensor) else type(v).__name__
+            raise ValueError(f"values[{k}] must be a float32 [{nnz}] tensor on {adjhops.device} (one value per stored entry of hop {k}, "
+                             f"in the order of colidx[{k}]), got {what}")
+    if inputs.requires_grad and torch.is_grad_enabled() and adjhops.has_transpose and not adjhops.keep_permutation:
+        raise ValueError("hop_spmm(..., values=...) with inputs that require a gradient: this plan holds transposed operands for the "
+                         "adjoint but cannot refresh them for new values.  Build the plan with keep_permutation=True")
+    return values
+
+
+def hop_spmm(adjhops: HopPlan, inputs: torch.Tensor, hops: Optional[Iterable[int]] = None, values=None) -> torch.Tensor:
+    """Functional form of :class:`GCNLayer`: ``[n_cols, d] -> [n_rows, H_sel, d]``, differentiable wrt ``inputs``.
+
+    ``values``: optional sequence of ``n_hops`` entries -- per hop a float32 ``[nnz_k]`` tensor on the plan's device (the stored
+    values of ``A_k`` in the order of ``colidx[k]``), or ``None`` to keep the plan's current values of that hop.  The result is
+    then differentiable wrt these tensors too (learned or signed edge weights, attention coefficients, a per-edge gate): the
+    backward computes ``d values[k][e] = sum_c grad[i, s, c] * inputs[j, c]`` over the stored entries with
+    :meth:`HopPlan.sddmm`, for the hops whose values require a gradient.  The given values are installed with
+    ``plan.set_values(k, values[k].detach().contiguous())``, and the plan KEEPS POINTING AT THEM afterwards, exactly as
+    ``set_values`` documents: later launches of the plan use them until they are replaced.  Replacing them between this call
+    and its backward raises a ``RuntimeError`` in the backward.  A plan with transposed operands must have been built with
+    ``keep_permutation=True`` when ``inputs`` requires a gradient; row-partitioned operands (``ShardedHops``) are not covered.
+    ``values=None`` is today's code path, untouched."""
+    if values is not None and hasattr(adjhops, "aggregate"):
+        raise ValueError("values= is not supported on row-partitioned operands (ShardedHops): pass a single-GPU HopPlan, or set the "
+                         "shards' values yourself")
     if not isinstance(adjhops, HopPlan):
         raise TypeError(f"adjhops must be a HopPlan, got {type(adjhops).__name__}")
     sel = None if hops is None else tuple(sorted(set(int(h) for h in hops)))
+    if values is not None:
+        return _HopSpMMValues.apply(inputs, adjhops, sel, *_check_values(adjhops, inputs, values))
     if inputs.requires_grad and torch.is_grad_enabled():
         return _HopSpMM.apply(inputs, adjhops, sel)
     return adjhops.spmm(inputs, hops=sel)
@@ -50,6 +130,8 @@ class GCNLayer(torch.nn.Module):
     ``hops``: optional set of hop indices to keep (the ``G0`` / ``G0_1`` forms of the network-setup DSL,
     ``h2gcn/models/__init__.py:88-95``); ``None`` keeps every hop of ``adjhops``.  Unknown indices are ignored
     like the reference's ``if ind in self.hops`` filter does -- unless nothing is left, which raises.
+    ``forward(adjhops, inputs, values=None)``: ``values`` makes the stored values of the hop matrices differentiable inputs
+    (see :func:`hop_spmm`).
     """
 
     SIGNATURE = ["adjhops", "inputs"]
@@ -58,15 +140,17 @@ class GCNLayer(torch.nn.Module):
         super().__init__()
         self.hops = None if hops is None else set(int(h) for h in hops)
 
-    def forward(self, adjhops: HopPlan, inputs: torch.Tensor) -> torch.Tensor:
+    def forward(self, adjhops: HopPlan, inputs: torch.Tensor, values=None) -> torch.Tensor:
         sel = None
         if hasattr(adjhops, "aggregate"):  # partition.ShardedHops: all-gather + local SpMM (+ reduce-scatter backward)
+            if values is not None:
+                raise ValueError("values= is not supported on row-partitioned operands (ShardedHops): pass a single-GPU HopPlan")
             return adjhops.aggregate(inputs, None if self.hops is None else sorted(self.hops))
         if self.hops is not None:
             sel = [h for h in range(adjhops.n_hops) if h in self.hops]
             if not sel:
                 raise ValueError(f"GCNLayer(hops={sorted(self.hops)}) selects none of the {adjhops.n_hops} hops")
-        return hop_spmm(adjhops, inputs, sel)
+        return hop_spmm(adjhops, inputs, sel, values)
 
     def extra_repr(self) -> str:
         return f"hops={None if self.hops is None else sorted(self.hops)}"

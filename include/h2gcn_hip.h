@@ -8,7 +8,8 @@
  *
  * (reference h2gcn/models/_layers.py:54-81; the op underneath is TensorFlow's SparseTensorDenseMatMul,
  * call sites _layers.py:74,76) and its gradient wrt X (`dX = sum_k A_k^T dY[:,k,:]`, reached from
- * tape.gradient at h2gcn/models/H2GCN.py:66-74).  There is no native boundary in the reference to copy:
+ * tape.gradient at h2gcn/models/H2GCN.py:66-74) -- and, for callers whose adjacency values are trainable, the op's
+ * other gradient, wrt the stored values (h2gcn_sddmm_hops_*).  There is no native boundary in the reference to copy:
  * the reference's native boundary is TensorFlow's op registry.  Each entry point below cites the reference
  * behaviour it stands in for.
  *
@@ -288,7 +289,7 @@ int h2gcn_spmm_hops_opts_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const 
  * Stands in for the TF-registered gradient of SparseTensorDenseMatMul wrt its dense operand
  * (adjoint_a=True SpMM), summed over the hops that `tf.stack` fanned out, as reached from
  * tape.gradient (reference h2gcn/models/H2GCN.py:66-74).  The gradient wrt the adjacency values, which TF
- * also computes and the reference discards, is not computed.  Requires H2GCN_PLAN_BUILD_TRANSPOSE.
+ * also computes and the reference discards, is a launch of its own: h2gcn_sddmm_hops_f32 below.  Requires H2GCN_PLAN_BUILD_TRANSPOSE.
  * dX is overwritten (not accumulated into).
  */
 int h2gcn_spmm_hops_T_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* dY_dev, int64_t ldg_row,
@@ -345,6 +346,61 @@ int h2gcn_spmm_hops_bf16(const h2gcn_plan_t* plan, uint32_t hop_mask, const uint
                          int y_dtype, void* Y_dev, int64_t ldy_row, int64_t ldy_hop, const h2gcn_launch_opts* opts, void* stream);
 int h2gcn_spmm_hops_T_bf16(const h2gcn_plan_t* plan, uint32_t hop_mask, const uint16_t* dY_dev, int64_t ldg_row, int64_t ldg_hop,
                            int32_t d, int dx_dtype, void* dX_dev, int64_t ldx, const h2gcn_launch_opts* opts, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
+ * Gradient with respect to the adjacency VALUES (an additive extension of ABI 5: look the symbols up before calling a build
+ * that may predate it).  The second gradient of SparseTensorDenseMatMul -- a sampled dense-dense product over the CSR
+ * pattern (SDDMM):
+ *
+ *     dvals[s][e] = sum_c dY[i*ldg_row + s*ldg_hop + c] * X[j*ldx + c]      for every stored entry e = (i, j) of hop k
+ *
+ * for every selected hop k (s = rank of k among the selected hops, ascending).  The reference never needs it (its adjacency is
+ * constant); a caller whose hop values depend on something trainable -- learned or signed edge weights, attention coefficients
+ * over the 1-hop / 2-hop rings, a per-edge gate -- does.
+ *
+ *   dY_dev     [n_rows, H_sel, d] through ldg_row / ldg_hop (elements; ldg_row >= d, ldg_hop >= d when H_sel > 1)
+ *   X_dev      [n_cols, d], row stride ldx >= d.  n_rows != n_cols is allowed (shard plans, row-selected sub-plans)
+ *   d          any width >= 1
+ *   dvals_dev  HOST array of H_sel device pointers; entry s receives nnz_k fp32 values in the entry order of colidx_dev[k] and
+ *              is OVERWRITTEN (never accumulated into).  An entry may be NULL only when its hop has no nonzeros.
+ *
+ * Only the plan's forward arrays rowptr / colidx are read -- neither its values nor its transposes -- so the call works on a
+ * plan created without H2GCN_PLAN_BUILD_TRANSPOSE, and a stored entry whose current value is an explicit zero is computed like
+ * any other: the pattern decides.  All offsets are 64-bit.  The call allocates nothing besides the long-segment list of a hop
+ * selection that has not been launched before (see the capture rule).
+ *
+ * bf16 (h2gcn_sddmm_hops_bf16): BOTH operands are bf16; every element is widened exactly, all arithmetic is fp32 and the output
+ * is fp32.  Layout as for the bf16 launches above: 4-byte aligned bases, even strides, even d -- anything else is
+ * H2GCN_ERR_INVALID_ARGUMENT with a message that names the rule.
+ *
+ * Arithmetic: ONE order per element, a function of d alone.  The columns are cut into blocks of 64 (block b: columns
+ * 64b .. 64b+63) and every block into 16 quads of 4 (quad q of block b: columns 64b+4q .. 64b+4q+3); a column >= d enters as +0
+ * on both sides.
+ *   quad value    t = g0*x0;  t = fma(g1, x1, t);  t = fma(g2, x2, t);  t = fma(g3, x3, t)
+ *   block total   the 16 quad values summed by the xor butterfly over quad distances 1, 2, 4, 8:
+ *                 v1[q] = t[q] + t[q^1],  v2[q] = v1[q] + v1[q^2],  v4[q] = v2[q] + v2[q^4],  B = v4[q] + v4[q^8]
+ *   element       ((((+0 + B_0) + B_1) + B_2) ... + B_last),  blocks in ascending order, ceil(d / 64) of them
+ * The bits therefore never depend on row length or segment class, long_row_threshold, rows_per_wave, slice_cols, the hop
+ * selection, strides, or on which kernel geometry (1, 2 or 4 blocks in registers; column passes beyond 256 columns) served the
+ * launch; and since bf16 widens exactly into the same order, h2gcn_sddmm_hops_bf16(g, x) is BIT-IDENTICAL to
+ * h2gcn_sddmm_hops_f32 on the widened operands.  No atomics: two launches give the same bits.
+ * Error bound: any order of a d-term fp32 dot product satisfies |dV - exact| <= gamma_d * sum_c |g_c x_c| (+ d * 2^-149 for
+ * underflow), gamma_d = d*u / (1 - d*u), u = 2^-24.
+ *
+ * hipGraph capture: the condition of the forward launch of the same hop selection.  Segments with >= long_row_threshold
+ * nonzeros are served from the plan's forward long-segment list of the selection -- the list h2gcn_spmm_hops_* uses; it is
+ * built by the FIRST launch of that selection, whichever of the two it is, and the all-hops list at plan creation.  A launch
+ * that would have to build it while its stream is being captured returns H2GCN_ERR_INVALID_ARGUMENT with the same advice (run
+ * the launch once eagerly first).
+ *
+ * Validation, all before the device is touched, each H2GCN_ERR_INVALID_ARGUMENT with a message naming the argument: a NULL
+ * plan ("plan is NULL"), a hop mask outside the plan, d < 1, ldx / ldg_row / ldg_hop smaller than d, the bf16 layout rules, a
+ * NULL dY / X / dvals table when the selection has nonzeros, a NULL dvals entry of a selected hop with nonzeros.
+ */
+int h2gcn_sddmm_hops_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* dY_dev, int64_t ldg_row, int64_t ldg_hop,
+                         const float* X_dev, int64_t ldx, int32_t d, float* const* dvals_dev, void* stream);
+int h2gcn_sddmm_hops_bf16(const h2gcn_plan_t* plan, uint32_t hop_mask, const uint16_t* dY_dev, int64_t ldg_row, int64_t ldg_hop,
+                          const uint16_t* X_dev, int64_t ldx, int32_t d, float* const* dvals_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
  * Operand construction on the device: exact-k-hop neighbourhood rings and their normalisation -- the step that
