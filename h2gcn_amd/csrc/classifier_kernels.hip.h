@@ -352,9 +352,9 @@ __global__ __launch_bounds__(kThreads) void small_dx_kernel(const float* __restr
                 for (int j = 0; j < 4; ++j) out[j] = fmaf(gc, w[j], out[j]);
             }
         }
-        f4u keep = {inv_keep, inv_keep, inv_keep, inv_keep};
-        keep = apply_mask<MASK>(keep, mk, src_row<ROWS>(rows, n_rows, row), k);        // inv_keep where kept, 0 where dropped
-        const f4u o = {out[0] * keep[0], out[1] * keep[1], out[2] * keep[2], out[3] * keep[3]};
+        // the mask is a SELECT, as in the matrix-core kernels: a dropped element is 0 even when its sum is Inf / NaN
+        const f4u scaled = {out[0] * inv_keep, out[1] * inv_keep, out[2] * inv_keep, out[3] * inv_keep};
+        const f4u o = apply_mask<MASK>(scaled, mk, src_row<ROWS>(rows, n_rows, row), k);
         store_row4<false>(dX + row * lddx + k, o, k, K);
     }
 }

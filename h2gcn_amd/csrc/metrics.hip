@@ -81,8 +81,10 @@ __device__ __forceinline__ int grp_argmax(const f4u& v, int c0, int C) {
     }
     return bi;
 }
-// max and log-sum-exp of a row
-__device__ __forceinline__ void row_lse(const f4u& z, int c0, int C, float& mx, float& lse) {
+// max of a row and log(sum_c exp(z_c - max)).  Callers work on the SHIFTED logits z_c - mx (softmax cross-entropy is
+// shift-invariant): forming mx + log(sum) first would round it to ulp(|z|) and cost the loss and the softmax an error that grows
+// with the logits' magnitude.
+__device__ __forceinline__ void row_lse(const f4u& z, int c0, int C, float& mx, float& lsum) {
     float m = -INFINITY;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -92,7 +94,7 @@ __device__ __forceinline__ void row_lse(const f4u& z, int c0, int C, float& mx, 
 #pragma unroll
     for (int i = 0; i < 4; ++i)
         if (c0 + i < C) e += expf(z[i] - mx);
-    lse = mx + logf(grp_sum(e));
+    lsum = logf(grp_sum(e));
 }
 
 __global__ __launch_bounds__(kThreads) void masked_metrics_kernel(const float* __restrict__ Z, int64_t ldz, int64_t n_rows, int C, Sets s,
@@ -135,17 +137,20 @@ __global__ __launch_bounds__(kThreads) void masked_metrics_kernel(const float* _
         load_zy(row + stride, w_b, any_b, z_b, ys_b);
         const bool any_a = load_w(row + 2 * stride, w_a);
         if (any_c) {
-            float mx, lse;
-            row_lse(z_c, c0, C, mx, lse);
+            float mx, lsum;
+            row_lse(z_c, c0, C, mx, lsum);
+            f4u zs;   // shifted logits; columns beyond C hold y = 0 and must not turn a large |mx| into 0 * inf
+#pragma unroll
+            for (int i = 0; i < 4; ++i) zs[i] = c0 + i < C ? z_c[i] - mx : 0.f;
             const int zi = grp_argmax(z_c, c0, C);
 #pragma unroll
             for (int m = 0; m < kMaxSets; ++m) {
                 if (m >= s.n || w_c[m] == 0.f) continue;
                 const f4u y = ys_c[m];
-                const float ydot = grp_sum(y[0] * z_c[0] + y[1] * z_c[1] + y[2] * z_c[2] + y[3] * z_c[3]);
+                const float ydot = grp_sum(y[0] * zs[0] + y[1] * zs[1] + y[2] * zs[2] + y[3] * zs[3]);
                 const float ysum = grp_sum((y[0] + y[1]) + (y[2] + y[3]));
                 const int yi = grp_argmax(y, c0, C);
-                loss_acc[m] += (double)w_c[m] * (double)(ysum * lse - ydot);   // - sum_c y_c (z_c - lse)
+                loss_acc[m] += (double)w_c[m] * (double)(ysum * lsum - ydot);   // - sum_c y_c ((z_c - mx) - log sum)
                 hit_acc[m] += zi == yi ? (double)w_c[m] : 0.0;
             }
         }
@@ -208,12 +213,12 @@ __global__ __launch_bounds__(kThreads) void masked_ce_backward_kernel(const floa
         if (wr != 0.f) {
             const f4u z = load_quad(Z + row * ldz, c0, C);
             const f4u y = load_quad(Y + row * ldy, c0, C);
-            float mx, lse;
-            row_lse(z, c0, C, mx, lse);
+            float mx, lsum;
+            row_lse(z, c0, C, mx, lsum);
             const float ysum = grp_sum((y[0] + y[1]) + (y[2] + y[3]));
             const float gw = g * wr;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) o[i] = gw * (expf(z[i] - lse) * ysum - y[i]);
+            for (int i = 0; i < 4; ++i) o[i] = gw * (expf((z[i] - mx) - lsum) * ysum - y[i]);
         }
         float* dst = dZ + row * lddz + c0;
         if (c0 + 4 <= C) {

@@ -512,6 +512,10 @@ __device__ __forceinline__ void combine_partials(const float (&part)[kTreeParts]
     for (int i = 0; i < VEC; ++i) acc[i] = (part[0][i] + part[1][i]) + (part[2][i] + part[3][i]);
 }
 
+// ReLU that propagates NaN, as torch.relu / tf.nn.relu / np.maximum do (fmaxf would return the non-NaN operand and store a
+// diverged sum as 0): every comparison with NaN is false, so NaN takes the `t` arm.  -Inf -> 0, +Inf stays.
+__device__ __forceinline__ float relu_keep_nan(float t) { return t < 0.f ? 0.f : t; }
+
 // Optional fused epilogue of the store (reference SparseDense.call, h2gcn/models/_layers.py:45-52: `+ bias`, then the
 // activation): applied to the finished sum of an output element, columns col .. col+VEC-1.
 template <int VEC>
@@ -522,7 +526,7 @@ __device__ __forceinline__ void epilogue(float (&acc)[VEC], const float* __restr
     }
     if (relu) {
 #pragma unroll
-        for (int i = 0; i < VEC; ++i) acc[i] = fmaxf(acc[i], 0.f);
+        for (int i = 0; i < VEC; ++i) acc[i] = relu_keep_nan(acc[i]);
     }
 }
 
@@ -600,7 +604,7 @@ __device__ __forceinline__ void store_out(const P& p, TD* row, int col0, int eco
                     float t = tot[i];
                     if (kF32 && p.accumulate) t += reinterpret_cast<const float*>(row)[c];
                     if (p.bias) t += p.bias[c];
-                    if (p.relu) t = fmaxf(t, 0.f);
+                    if (p.relu) t = relu_keep_nan(t);
                     store_one<TD>(row + c, t);
                 }
             }
@@ -1093,7 +1097,7 @@ __global__ __launch_bounds__(kBlock, (min_waves_per_simd<VEC, LPR, EXACT, SUM, O
                     if constexpr (std::is_same<TD, float>::value)
                         if (p.accumulate) t += dst_ptr<float>(p.dst)[off];
                     if (p.bias) t += p.bias[col0 + c];
-                    if (p.relu) t = fmaxf(t, 0.f);
+                    if (p.relu) t = relu_keep_nan(t);
                 }
                 store_one<TD>(dst_ptr<TD>(p.dst) + off, t);
             }

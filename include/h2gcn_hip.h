@@ -233,6 +233,10 @@ int h2gcn_plan_segment_classes(const h2gcn_plan_t* plan, uint32_t hop_mask, int 
  * scratch copy and segment walk (rows with >= long_row_threshold nonzeros: the same tree per wave over the wave's
  * 64-neighbour chunks, wave totals added in order).  The bits of Y depend only on the row's nonzeros, X and
  * long_row_threshold: a row-partitioned multi-GPU run equals the single-GPU run bit-for-bit.
+ * Subnormals are kept: the library is built without any flush-to-zero option, and the multiply-adds, the bf16 conversion of the
+ * store and the SDDMM chains below handle fp32 / bf16 subnormal operands, partial sums and results as IEEE 754 does (checked bit
+ * for bit against the CPU restatements on all-subnormal operands, tests/test_special_values_gpu.py).  NaN and Inf propagate: a
+ * stored entry whose value is an explicit zero still multiplies its neighbour (0 * Inf = NaN, the pattern decides).
  *
  * hipGraph capture: a launch may be issued on a capturing stream, with one proviso.  The device-side row lists of a hop
  * selection (its long-segment list; its per-class lists once a launch is list-driven) are built by the FIRST launch of
@@ -261,6 +265,9 @@ int h2gcn_spmm_hops_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float
  * bias / H2GCN_LAUNCH_RELU: fused epilogue of the store, Y = act(A X + bias[c]) -- what SparseDense.call applies
  *   after its sparse product (reference h2gcn/models/_layers.py:45-52: `+ self.bias`, then `self.activation`), so
  *   that the feature embedding needs no second pass over its output.  bias: d floats (device) or NULL.  Forward only.
+ *   The ReLU is `t < 0 ? 0 : t` on the finished fp32 sum (after the bias): a NaN sum stays NaN -- as tf.nn.relu, torch.relu and
+ *   np.maximum propagate it, and unlike C's fmaxf, which would return the other operand and store 0 -- so an embedding
+ *   kernel that has diverged stays visible downstream; -Inf becomes 0, +Inf stays +Inf.
  *
  * h2gcn_spmm_workspace_bytes: adjoint != 0 asks about h2gcn_spmm_hops_T_opts_f32; src_dev / ld_src / ld_src_hop
  *   describe the gather source of that launch (forward: X_dev, ldx, 0; adjoint: dY_dev, ldg_row, ldg_hop); the pointer
@@ -477,6 +484,8 @@ int h2gcn_hop_normalize_rows(int64_t n_rows, const int64_t* rowptr_dev, const in
  *     forward    Z[n, c]  = sum_k D[n, k] * W[k, c] + bias[c]          D[n, k] = keep(n, k) ? X[n, k] / keep_prob : 0
  *     backward   dX[n, k] = keep(n, k) ? (sum_c G[n, c] * W[k, c]) / keep_prob : 0
  *                dW[k, c] = sum_n D[n, k] * G[n, c]                     (db = column sums of G: left to the caller)
+ *   The mask is a SELECT in every kernel (matrix-core and small-operand alike), never a multiplication by 0: a dropped element of
+ *   D or dX is exactly 0 even where X or the sum over c is Inf / NaN.
  *
  * The dropout mask is COUNTER-BASED, recomputed wherever it is needed instead of stored.  One keyed hash per aligned group
  * of four columns of a row:
@@ -591,6 +600,11 @@ int h2gcn_dropout_dense_backward_rows_bf16(const uint16_t* X_dev, int64_t ldx, i
  *
  * Rows whose weight is zero in every set are not read; a label matrix is read only at the rows of non-zero weight.  Per-row
  * terms are fp32, the sums over rows run in fp64 per workgroup and are combined in a fixed order (deterministic).
+ * Accuracy at any offset: softmax cross-entropy is shift-invariant, and both kernels work on the SHIFTED logits z_c - max_c z --
+ * the row's term is (sum_c Y_c) * log(sum_c exp(z_c - max)) - sum_c Y_c * (z_c - max), the softmax of the gradient is
+ * exp((z_c - max) - log(sum)) -- like the reference's tf.nn.softmax_cross_entropy_with_logits.  The error of a row's term
+ * therefore does not grow with the magnitude of the logits (unnormalised features, confident late-epoch models): the tolerances
+ * that hold for logits around 0 hold for logits around 1e6.
  * DIVERGENCE from the reference on non-finite logits: the reference MULTIPLIES every row's term by its mask weight
  * (_metrics.py:12-14, 22-24), so a NaN / Inf logit in a row the mask excludes still yields NaN there (0 * NaN); here such a
  * row is skipped and the result stays finite.  Rows the mask includes propagate NaN / Inf exactly as the reference does, so a

@@ -160,3 +160,23 @@ def gcn_layer_grad_tree(hops, dy, n_cols, long_threshold=256):
                                 dy.ctypes.data_as(C.c_void_p), C.c_int64(H * d), C.c_int64(d), C.c_int64(d),
                                 C.c_int(long_threshold), C.c_int(1), dx.ctypes.data_as(C.c_void_p), C.c_int64(d), C.c_int64(0))
     return dx
+
+
+def sddmm_order(hops, grad, x):
+    """Order restatement of HopPlan.sddmm (see ``oracle_sddmm_order_f32``): the gradient with respect to the stored values,
+    one float32 array per hop in entry order, in the ONE arithmetic order include/h2gcn_hip.h documents -- the bit-exact
+    target of h2gcn_sddmm_hops_f32 / _bf16 (bf16 operands: pass them widened).  grad [n_rows, H, d], x [n_cols, d]."""
+    grad = np.ascontiguousarray(grad, dtype=np.float32)
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    n_rows, H, d = grad.shape
+    assert H == len(hops) and x.shape[1] == d
+    out = []
+    for k, m in enumerate(hops):
+        ip, ix, _ = _csr_parts(m)
+        assert len(ip) - 1 == n_rows
+        dv = np.zeros(len(ix), dtype=np.float32)
+        _lib().oracle_sddmm_order_f32(C.c_int64(n_rows), ip.ctypes.data_as(C.c_void_p), ix.ctypes.data_as(C.c_void_p),
+                                      C.c_void_p(grad.ctypes.data + 4 * k * d), C.c_int64(H * d),
+                                      x.ctypes.data_as(C.c_void_p), C.c_int64(d), C.c_int64(d), dv.ctypes.data_as(C.c_void_p))
+        out.append(dv)
+    return out

@@ -233,6 +233,50 @@ void oracle_spmm_tree_f32_mt(int n_hops, int64_t n_rows, const int64_t* const* r
 }
 
 /* ---------------------------------------------------------------------------------------------------------------
+ * SDDMM order restatement (TEST INFRASTRUCTURE).  include/h2gcn_hip.h documents ONE arithmetic order per element of
+ * h2gcn_sddmm_hops_*, a function of d alone; this is that text, literally, for one hop:
+ *     dvals[e] = sum_c g[i, c] * x[j, c]      for every stored entry e = (i, j)
+ *   - columns in blocks of 64, every block in 16 quads of 4; a column >= d enters as +0 on both sides;
+ *   - quad value: t = g0*x0, then fmaf(g1, x1, t), fmaf(g2, x2, t), fmaf(g3, x3, t);
+ *   - block total: the xor butterfly over quad distances 1, 2, 4, 8 (v[q] + v[q ^ dist] for all 16 q at every step;
+ *     afterwards all 16 hold the same bits -- fp32 addition is commutative -- and B is v[0]);
+ *   - element: ((+0 + B_0) + B_1) ... over the ceil(d / 64) blocks in ascending order.
+ * g: row i of the hop's slot of dY at g + i * ldg; x: row j at x + j * ldx. */
+void oracle_sddmm_order_f32(int64_t n_rows, const int64_t* rowptr, const int32_t* colidx, const float* g, int64_t ldg,
+                            const float* x, int64_t ldx, int64_t d, float* dvals) {
+    const int64_t n_blocks = (d + 63) / 64;
+    for (int64_t i = 0; i < n_rows; ++i) {
+        const float* gr = g + i * ldg;
+        for (int64_t e = rowptr[i]; e < rowptr[i + 1]; ++e) {
+            const float* xr = x + (int64_t)colidx[e] * ldx;
+            float res = 0.f;
+            for (int64_t b = 0; b < n_blocks; ++b) {
+                float v[16], n[16];
+                for (int q = 0; q < 16; ++q) {
+                    float gq[4], xq[4];
+                    for (int k = 0; k < 4; ++k) {
+                        const int64_t c = 64 * b + 4 * q + k;
+                        gq[k] = c < d ? gr[c] : 0.f;
+                        xq[k] = c < d ? xr[c] : 0.f;
+                    }
+                    float t = gq[0] * xq[0];
+                    t = fmaf(gq[1], xq[1], t);
+                    t = fmaf(gq[2], xq[2], t);
+                    t = fmaf(gq[3], xq[3], t);
+                    v[q] = t;
+                }
+                for (int dist = 1; dist < 16; dist <<= 1) {
+                    for (int q = 0; q < 16; ++q) n[q] = v[q] + v[q ^ dist];
+                    memcpy(v, n, sizeof(v));
+                }
+                res = res + v[0];
+            }
+            dvals[e] = res;
+        }
+    }
+}
+
+/* ---------------------------------------------------------------------------------------------------------------
  * Whole-array comparisons for the full-size checks (OpenMP; plain reductions over integers / maxima, so the result
  * does not depend on the thread count). */
 

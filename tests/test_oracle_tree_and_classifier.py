@@ -62,6 +62,50 @@ def test_tree_of_one_row_by_hand():
     assert got == np.float32(np.float32(P[0] + P[1]) + np.float32(P[2] + P[3]))
 
 
+def test_sddmm_order_restatement():
+    """oracle_sddmm_order_f32 restates the ONE order include/h2gcn_hip.h documents for h2gcn_sddmm_hops_*: fma quad chains from
+    g0 * x0, columns >= d as +0, the xor butterfly over 16 quads, block totals added in ascending order to +0."""
+    rng = np.random.default_rng(5)
+    n_rows, n_cols = 9, 23
+    m = sp.random(n_rows, n_cols, 0.4, format="csr", random_state=5, dtype=np.float32)
+    m.sort_indices()
+    rows = np.repeat(np.arange(n_rows), np.diff(m.indptr))
+    # (a) integer-valued operands: every partial sum is exact in fp32 (|sum| <= 516 * 16 < 2^24), so every order gives the integer dot product
+    for d in (1, 3, 4, 5, 63, 64, 65, 130, 516):
+        g = rng.integers(-4, 5, (n_rows, 2, d)).astype(np.float32)
+        x = rng.integers(-4, 5, (n_cols, d)).astype(np.float32)
+        got = og.sddmm_order([m, m], g, x)
+        for k in range(2):
+            want = (g[rows, k, :].astype(np.int64) * x[m.indices].astype(np.int64)).sum(-1)
+            assert got[k].dtype == np.float32 and np.array_equal(got[k].astype(np.int64), want), (d, k)
+    # (b) by hand, d = 8, x = 1 everywhere, g = [1, 0, 0, 0, 2^-24, 2^-24, 0, 0] (every product exact).
+    #   documented order: quad 0 = fma chain over columns 0..3 = 1;  quad 1 = 2^-24 + 2^-24 = 2^-23 (exact);  quads 2..15 = +0;
+    #     butterfly distance 1: v[0] = quad 0 + quad 1 = 1 + 2^-23, representable (1 + one ulp of 1), bits 0x3F800001; the
+    #     distances 2, 4, 8 add +0, and the element is +0 + B_0 = 1 + 2^-23.
+    #   left to right: 1 + 2^-24 is a tie between 1 and 1 + 2^-23 and rounds to the even 1 -- twice; the sum is 1, bits 0x3F800000.
+    one = sp.csr_matrix((np.ones(1, np.float32), [0], [0, 1]), shape=(1, 1))
+    g = np.array([1, 0, 0, 0, 2.0 ** -24, 2.0 ** -24, 0, 0], np.float32).reshape(1, 1, 8)
+    x = np.ones((1, 8), np.float32)
+    left = np.float32(0)
+    for c in range(8):
+        left = np.float32(left + np.float32(g[0, 0, c] * x[0, c]))
+    got = og.sddmm_order([one], g, x)[0]
+    assert left.view(np.uint32) == 0x3F800000 and got.view(np.uint32)[0] == 0x3F800001
+    #   the chain is FUSED: d = 2, g = [-1, 1 + 2^-12], x = [1, 1 + 2^-12]: t = -1, then fma((1 + 2^-12)^2, t) = 2^-11 + 2^-24
+    #   exactly, where a rounded product (1 + 2^-11 + 2^-24 -> 1 + 2^-11, a tie to even) would leave 2^-11.
+    a = np.float32(1 + 2.0 ** -12)
+    got = og.sddmm_order([one], np.array([-1, a], np.float32).reshape(1, 1, 2), np.array([[1, a]], np.float32))[0]
+    assert float(got[0]) == 2.0 ** -11 + 2.0 ** -24
+    # (c) real-valued: within the bound of ANY order of a d-term fp32 dot product
+    u = 2.0 ** -24
+    for d in (5, 64, 130, 516):
+        g = rng.uniform(-1, 1, (n_rows, 1, d)).astype(np.float32)
+        x = rng.uniform(-1, 1, (n_cols, d)).astype(np.float32)
+        prod = g[rows, 0, :].astype(np.float64) * x[m.indices].astype(np.float64)
+        bound = d * u / (1 - d * u) * np.abs(prod).sum(-1) + d * 2.0 ** -149
+        assert (np.abs(og.sddmm_order([m], g, x)[0] - prod.sum(-1)) <= bound).all(), d
+
+
 def test_mask_generator_statistics_and_structure():
     for keep in (0.5, 0.9, 0.25):
         m = oc.keep_mask(4000, 448, keep, seed=0xDEADBEEF12345, step=3)
