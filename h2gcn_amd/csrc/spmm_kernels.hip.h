@@ -431,6 +431,101 @@ __device__ __forceinline__ void process_chunk(int c, float v, int n, int g, cons
     }
 }
 
+// ---- the index window's side of the gather (see window_tile_walk below) ----
+// WindowChunk: the chunk sits in the wave's index window (window_tile_walk below), an LDS ring of (column id, value)
+// pairs addressed by element index; one ds_read_b64 per step, the lanes of a group read the same pair and the G groups G
+// consecutive ones (32 contiguous bytes: no bank conflict).
+constexpr int kRingHops = 2;     // selected hops the window is sized for; launches that select more keep the register chunks
+constexpr int kRingCap = 256;    // pairs per (wave, hop) ring: 2 KiB, 16 KiB per workgroup
+constexpr int kRingBlock = 128;  // pairs per refill: 4 lines of 128 B of either array, one wave-wide 16-byte load
+constexpr int64_t kRingMaxRange = 0x7fff0000;  // longest range of a hop a wave walks through the window (32-bit relative indices)
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4), aligned(4)));
+struct WindowChunk {
+    const uint32_t* ring;  // this (wave, hop)'s ring: the pair of element e at dwords 2 * (e % kRingCap)
+    uint32_t e_lane;       // element index (low bits) of neighbour g of the chunk, g = this lane's group
+    template <int G>
+    __device__ __forceinline__ void fetch(int step, int g, int& cj, float& w) const {
+        static_assert(G > 1, "the one-neighbour-per-load geometry keeps v_readlane");
+        const u32x2 pr = *reinterpret_cast<const u32x2*>(ring + 2 * ((e_lane + (uint32_t)(step * G)) & (kRingCap - 1)));
+        cj = (int)pr[0];
+        w = __uint_as_float(pr[1]);
+    }
+};
+
+// gather_batch with the neighbours taken from the window: same steps, same partials.  (A function of its own, and a
+// process_chunk of its own below, rather than a chunk-source parameter of gather_batch: handing (c, v) over inside a struct
+// re-schedules the index loads of every kernel that shares gather_batch -- the in-tile short-row and list-driven ones too.)
+template <typename TS, int VEC, int LPR, int U, bool PREDICATED, bool OFF32, int PHASE = 0, int NP>
+__device__ __forceinline__ void gather_batch_window(const WindowChunk& ch, int t, int g, const GatherAddr<OFF32>& addr, bool take,
+                                             float (&acc)[NP][VEC]) {
+    constexpr int G = kWave / LPR;
+    typename LoadT<TS, VEC>::type x[U];
+    float w[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        int cj;
+        ch.template fetch<G>(t + u, g, cj, w[u]);
+        const void* p = addr.row(cj);
+        if constexpr (PREDICATED) {
+            if (take) {
+                x[u] = load_vec<TS, VEC>(p);
+            } else {
+                w[u] = 0.f;
+                x[u] = zero_load<TS, VEC>();
+            }
+        } else {
+            x[u] = load_vec<TS, VEC>(p);
+        }
+    }
+    // step t+u serves neighbour (t+u)*G + g -> canonical partial ((t+u)*G + g) % 4 = lane-local partial (t+u) % NP;
+    // the caller states t % NP as PHASE, so the partial of every step is a compile-time register choice
+#pragma unroll
+    for (int u = 0; u < U; ++u) fma_vec<TS, VEC>(acc[(PHASE + u) % NP], w[u], x[u]);
+}
+
+// process_chunk on a chunk of n (<= 64) neighbours that sits in the window: the same batches in the same order.
+// MAXB: deepest load batch (8 in the bandwidth kernels; 4 where register pressure matters more than the last few
+// percent on long segments -- the fallback walk of the short-row kernels).  The batch depth only re-times loads: the
+// accumulation order, hence the bits, do not depend on it.
+template <typename TS, int VEC, int LPR, bool MASKED, bool OFF32, int MAXB = H2GCN_MAIN_MAXB, int NP>
+__device__ __forceinline__ void process_chunk_window(const WindowChunk& ch, int n, int g, const GatherAddr<OFF32>& addr,
+                                              bool lane_active, float (&acc)[NP][VEC]) {
+    constexpr int G = kWave / LPR;
+    const int full = n / G;  // steps in which every lane group has a neighbour
+    int t = 0;               // batches of 8 / 4 start at t % 4 == 0: partial phase 0
+    if constexpr (MAXB >= 8)
+        for (; t + 8 <= full; t += 8) gather_batch_window<TS, VEC, LPR, 8, MASKED, OFF32>(ch, t, g, addr, lane_active, acc);
+    if constexpr (MAXB < 8)
+        for (; t + 4 <= full; t += 4) gather_batch_window<TS, VEC, LPR, 4, MASKED, OFF32>(ch, t, g, addr, lane_active, acc);
+    if (t + 4 <= full) {
+        gather_batch_window<TS, VEC, LPR, 4, MASKED, OFF32>(ch, t, g, addr, lane_active, acc);
+        t += 4;
+    }
+    // the last 0..3 full steps and (G > 1) the ragged step in which only the first (n - full*G) groups still have a
+    // neighbour, with the phase of every step spelled out
+    const int rem = n - full * G;
+    if (t + 2 <= full) {
+        gather_batch_window<TS, VEC, LPR, 2, MASKED, OFF32>(ch, t, g, addr, lane_active, acc);
+        t += 2;
+        if (t + 1 <= full) {
+            gather_batch_window<TS, VEC, LPR, 1, MASKED, OFF32, 2 % NP>(ch, t, g, addr, lane_active, acc);
+            if constexpr (G > 1)
+                if (rem > 0) gather_batch_window<TS, VEC, LPR, 1, true, OFF32, 3 % NP>(ch, full, g, addr, lane_active && g < rem, acc);
+        } else {
+            if constexpr (G > 1)
+                if (rem > 0) gather_batch_window<TS, VEC, LPR, 1, true, OFF32, 2 % NP>(ch, full, g, addr, lane_active && g < rem, acc);
+        }
+    } else if (t + 1 <= full) {
+        gather_batch_window<TS, VEC, LPR, 1, MASKED, OFF32>(ch, t, g, addr, lane_active, acc);
+        if constexpr (G > 1)
+            if (rem > 0) gather_batch_window<TS, VEC, LPR, 1, true, OFF32, 1 % NP>(ch, full, g, addr, lane_active && g < rem, acc);
+    } else {
+        if constexpr (G > 1)
+            if (rem > 0) gather_batch_window<TS, VEC, LPR, 1, true, OFF32>(ch, full, g, addr, lane_active && g < rem, acc);
+    }
+}
+
 // Accumulate sum_j val_j * src[col_j, :] over the nonzeros [seg_begin, seg_end) of one CSR row, taking the
 // 64-wide chunks chunk0, chunk0+chunk_step, ... (regular path: all of them; long path: this wave's share).
 // Each lane group accumulates its neighbours in ascending order into acc.
@@ -965,6 +1060,167 @@ __device__ __forceinline__ void in_tile_short_rows(const LaunchParams& p, int la
     }
 }
 
+// hop 0's or hop 1's value of a piece of per-hop state, selected BY VALUE (a conditional between the two variables themselves
+// is a choice of address, which keeps them in memory)
+template <typename T>
+__device__ __forceinline__ T pick(int s, T of_hop0, T of_hop1) { return s ? of_hop1 : of_hop0; }
+
+// ---- the index window of the tile walk (see uses_index_window) -----------------------------------------------------------
+// A wave's rows are consecutive, so per selected hop the nonzeros it walks are ONE contiguous range of colidx / vals:
+// [rowptr[row0], rowptr[row0 + rows_here]).  Fetched segment by segment (load_chunk), a segment of ~50 nonzeros that
+// starts at an arbitrary element touches ~2.5 lines of 128 B per array where 1.6 lines' worth are needed, and the line it
+// shares with the next row's segment is requested again a few microseconds later, after the gather fills have pushed it
+// out of the L2.  Here the wave streams the range through an LDS ring instead, in blocks of kRingBlock elements that are
+// line-aligned IN MEMORY (an array may start at any 4-byte offset, colidx and vals at different ones).  With x the index
+// of an element relative to the start of the range and m the number of elements by which x = 0 of an array lies past a
+// line boundary, block j of that array holds x in [j*128 - m, j*128 + 128 - m).  One wave-wide 16-byte load fetches a
+// block of both arrays (lanes 0-31 column ids, lanes 32-63 values), so each line of either array inside the range is
+// requested once per pass BY THAT WAVE; blocks only move forward.  (A line that straddles the ranges of two neighbouring
+// waves is still requested by both, and a line shared with a long segment also by that segment's workgroup.)  Lanes are predicated element by element to the wave's
+// own range (a lane whose four elements straddle an end of it loads them one by one), so nothing outside [0, nnz) is
+// ever read.  The block is written to the ring as (column id, value) pairs, the pair of element x at slot x % kRingCap,
+// and gather_batch reads a neighbour's pair with one ds_read_b64 (WindowChunk).
+// Refills are issued ahead of the chunk that needs them: before a chunk gathers, the block that the NEXT chunk (of this
+// segment, else the first of the next segment) is still missing is loaded into four registers, and written to the ring
+// after the gathers (loads retire in order, so it has landed by then); only a wave's first block, and a second block
+// missing for one chunk, are waited for.  Ring safety: a block is fetched only when a chunk [b, b + 64) needs it, i.e.
+// b + 64 > j*128 - max(m); the slots it overwrites held elements below j*128 - 128 - min(m) < b, which are consumed.
+// Segments of the long path (and, in SUM mode, every segment of a row that has one) are stepped over by whole blocks.
+// The arithmetic is process_chunk's: same neighbours, same order, same tree.
+template <typename TS, typename TD, int VEC, int LPR, bool SUM, bool OFF32, bool EPI, int MAXB>
+__device__ __forceinline__ void window_tile_walk(const LaunchParams& p, int lane, int rpw, int64_t row0, int rows_here, int64_t rp,
+                                                 int64_t lane_off0, int64_t src_col_begin, int lcol, int ecol,
+                                                 uint32_t (&ring)[kRingHops][2 * kRingCap]) {
+    using off_t = typename std::conditional<OFF32, uint32_t, int64_t>::type;
+    constexpr int NP = Tree<LPR>::NP;
+    static_assert(kRingBlock == 4 * (kWave / 2) && kRingCap >= 2 * kRingBlock && kWave + 31 < kRingBlock, "ring safety (see above)");
+    static_assert(kRingHops == 2, "hop state is selected with pick(s, hop 0's, hop 1's)");
+    const int g = lane / LPR;
+    const int n_sel = p.n_sel;
+    const int half = lane >> 5, l4 = 4 * (lane & 31);
+    auto misalign = [](const void* a) __attribute__((always_inline)) { return (int)((reinterpret_cast<uintptr_t>(a) >> 2) & 31); };  // elements past a line boundary
+    // per hop (0 / 1): x = 0 of its two arrays, the length of the range, the smaller / larger misalignment, the next block to fetch
+    const int32_t *col0 = nullptr, *col1 = nullptr;
+    const float *val0 = nullptr, *val1 = nullptr;
+    int len0 = 0, len1 = 0, mmin0 = 0, mmin1 = 0, mmax0 = 0, mmax1 = 0, blk0 = 0, blk1 = 0;
+    int rel = 0;  // lane l: row pointer of hop l / (rpw+1), row l % (rpw+1), relative to the hop's range (as the caller's rp)
+    auto init_hop = [&](int s, const int32_t*& col, const float*& val, int& len, int& mmin, int& mmax) __attribute__((always_inline)) {
+        const int l0 = s * (rpw + 1);
+        const int rp_lo = (int)(rp & 0xffffffff), rp_hi = (int)(rp >> 32);
+        const int64_t org = ((int64_t)__builtin_amdgcn_readlane(rp_hi, l0) << 32) | (uint32_t)__builtin_amdgcn_readlane(rp_lo, l0);
+        if (lane >= l0) rel = (int)(rp - org);
+        len = __builtin_amdgcn_readlane(rel, l0 + rows_here);
+        col = p.hop[s].colidx + org;
+        val = p.hop[s].vals + org;
+        const int mc = misalign(col), mv = misalign(val);
+        mmin = min(mc, mv);
+        mmax = max(mc, mv);
+    };
+    init_hop(0, col0, val0, len0, mmin0, mmax0);
+    if (n_sel > 1) init_hop(1, col1, val1, len1, mmin1, mmax1);
+    auto bound = [&](int l) __attribute__((always_inline)) { return __builtin_amdgcn_readlane(rel, l); };
+    auto lane_array = [&](int s) __attribute__((always_inline)) {
+        return reinterpret_cast<const uint32_t*>(pick<const void*>(half, pick(s, col0, col1), pick(s, val0, val1)));
+    };
+    // this lane's four elements of block `blk` of hop s (zero outside the wave's range); the first one's index is x0
+    auto block_load = [&](int s, int blk) __attribute__((always_inline)) {
+        const uint32_t* a = lane_array(s);
+        const int hi = pick(s, len0, len1);
+        const int x0 = blk * kRingBlock - misalign(a) + l4;
+        u32x4 st = {0u, 0u, 0u, 0u};
+        if (x0 >= 0 && x0 + 4 <= hi) {
+            st = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(a + x0));
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+                if (x0 + i >= 0 && x0 + i < hi) st[i] = __builtin_nontemporal_load(a + (x0 + i));
+        }
+        return st;
+    };
+    auto block_commit = [&](int s, int blk, const u32x4& st) __attribute__((always_inline)) {
+        const int x0 = blk * kRingBlock - misalign(lane_array(s)) + l4;
+        uint32_t* slots = ring[s];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) slots[2 * ((uint32_t)(x0 + i) & (kRingCap - 1)) + half] = st[i];
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    };
+    auto blk_of = [&](int s) __attribute__((always_inline)) { return pick(s, blk0, blk1); };
+    auto set_blk = [&](int s, int b) __attribute__((always_inline)) {
+        if (s) blk1 = b;
+        else blk0 = b;
+    };
+    // elements of hop s below this index are in the ring (or consumed) once the blocks below `blk` have been fetched
+    auto avail = [&](int s, int blk) __attribute__((always_inline)) { return blk * kRingBlock - pick(s, mmax0, mmax1); };
+
+    const int n_seg = rows_here * n_sel;
+    uint32_t skip = 0;  // bit q: segment q belongs to a workgroup of the long path
+    for (int q = 0; q < n_seg; ++q) {
+        const int r = q / n_sel, s_ = q - r * n_sel;
+        const int l0 = s_ * (rpw + 1) + r;
+        if (bound(l0 + 1) - bound(l0) >= p.long_threshold) skip |= SUM ? (((1u << n_sel) - 1u) << (r * n_sel)) : (1u << q);
+    }
+    float acc[NP][VEC];
+    zero_acc<VEC, NP>(acc);
+    for (int q = 0; q < n_seg; ++q) {
+        const int r = q / n_sel, s = q - r * n_sel;
+        const int l0 = s * (rpw + 1) + r;
+        const int sb = bound(l0), se = bound(l0 + 1);
+        const bool skipped = (skip >> q) & 1u;
+        if (skipped) {
+            // everything below `se` is dead: blocks that hold nothing else are never fetched
+            const int b = (se + pick(s, mmin0, mmin1)) / kRingBlock;
+            if (b > blk_of(s)) set_blk(s, b);
+        } else {
+            const GatherAddr<OFF32> addr{reinterpret_cast<const char*>(src_ptr<TS>(p.src) + p.src_hop_off[s] + src_col_begin - VEC),
+                                         (off_t)lane_off0, (off_t)(p.ld_src * sizeof(TS))};
+            for (int base = sb; base < se; base += kWave) {
+                const int n = min(se - base, kWave);
+                for (int b = blk_of(s); base + n > avail(s, b); set_blk(s, ++b)) {
+                    const u32x4 st = block_load(s, b);
+                    block_commit(s, b, st);
+                }
+                // what is processed next: this segment's next chunk, else the next segment's first one
+                int ps = s, pb = base + kWave, pe = se;
+                if (pb >= se) {
+                    pb = pe = 0;
+                    if (q + 1 < n_seg && !((skip >> (q + 1)) & 1u)) {
+                        const int r1 = (q + 1) / n_sel;
+                        ps = q + 1 - r1 * n_sel;
+                        pb = bound(ps * (rpw + 1) + r1);
+                        pe = bound(ps * (rpw + 1) + r1 + 1);
+                    }
+                }
+                const bool refill = pb < pe && min(pb + kWave, pe) > avail(ps, blk_of(ps));
+                u32x4 st = {0u, 0u, 0u, 0u};
+                if (refill) st = block_load(ps, blk_of(ps));
+                process_chunk_window<TS, VEC, LPR, false, OFF32, MAXB>(WindowChunk{ring[s], (uint32_t)(base + g)}, n, g, addr, true, acc);
+                if (refill) {
+                    block_commit(ps, blk_of(ps), st);
+                    set_blk(ps, blk_of(ps) + 1);
+                }
+            }
+        }
+        if (!SUM || s == n_sel - 1) {
+            if (!skipped) {
+                float tot[VEC];
+                fold_tree<VEC, LPR, NP>(acc, tot);
+                if (g == 0) store_out<TD, VEC, EPI>(p, dst_ptr<TD>(p.dst) + (row0 + r) * p.ld_dst + (SUM ? 0 : p.dst_hop_off[s]), lcol, ecol, tot);
+            }
+            zero_acc<VEC, NP>(acc);
+        }
+    }
+}
+
+// Which instantiations walk their tiles on the index window: the plain walk of 64-column slices with the plain store.  With
+// the staged block in registers the 128-column slices, the general store and the variant-2 prefetching walk do not fit the
+// register bounds they run at (scratch, or a wave per SIMD less: tools/kernel_resources.py); they keep the per-segment fetch.
+template <int LPR, bool EXACT, bool PIPE, bool SHORT, bool EPI, bool LISTS>
+constexpr bool uses_index_window() {
+    return EXACT && !SHORT && !LISTS && !PIPE && !EPI && LPR == 16;
+}
+
 // Waves per SIMD the register budget of an instantiation must allow: the second argument of the __launch_bounds__ of
 // spmm_hops_kernel (template parameters as there).  The H2GCN_*_MIN_WAVES macros are A/B knobs (tools/build_ab_lib.sh).
 template <int VEC, int LPR, bool EXACT, bool SUM, bool OFF32, bool PIPE, bool SHORT, bool EPI, int FB, bool LISTS, typename TS>
@@ -975,21 +1231,17 @@ constexpr int min_waves_per_simd() {
     if (SHORT) return FB == 4 && !SUM ? H2GCN_SHORT_FB4_MIN_WAVES : H2GCN_SHORT_MIN_WAVES;
     // bf16 gather sources: the instantiations whose fp32 bound leaves them short of registers (scratch; tools/kernel_resources.py)
     // run one wave per SIMD lower -- the list-driven adjoint at FB = 4 with 64-bit offsets, the general store of 128-column
-    // slices with 32-bit offsets, the prefetching adjoint walk of 64-column slices and the plain forward walk of 64-column
-    // slices with 64-bit offsets.  (Unpacking a bf16 pair costs a register per element in flight: the bf16 kernels are not
-    // lighter than the fp32 ones.)
+    // slices with 32-bit offsets and the prefetching adjoint walk of 64-column slices.  (Unpacking a bf16 pair costs a register
+    // per element in flight: the bf16 kernels are not lighter than the fp32 ones.)
     const bool bf16_less = std::is_same<TS, bf16>::value && VEC == 4 &&
-                           (LISTS ? FB == 4 && SUM && !OFF32
-                                  : (OFF32 && EPI && LPR == 32) || (SUM && OFF32 && PIPE && LPR == 16) ||
-                                        (!SUM && !OFF32 && !PIPE && !EPI && LPR == 16));
+                           (LISTS ? FB == 4 && SUM && !OFF32 : (OFF32 && EPI && LPR == 32) || (SUM && OFF32 && PIPE && LPR == 16));
     // list-driven kernels with shallow load batches (FB = 4)
     if (LISTS && FB == 4) return H2GCN_SHORT_FB4_MIN_WAVES - bf16_less;
     // instantiations that need more than 80 VGPRs to stay out of scratch (tools/kernel_resources.py): 64-bit gather offsets
-    // (two address registers per load in flight) together with a general store, a 128 / 256-column slice or the index
-    // prefetch; the prefetching walk on 128-column slices; list-driven walks (FB = 8) with 64-bit offsets on 128-column slices,
-    // and adjoint ones with 64-bit offsets or on 128-column slices
-    const bool heavy = VEC == 4 && (LISTS ? (SUM && (!OFF32 || LPR >= 32)) || (!OFF32 && LPR >= 32)
-                                          : !OFF32 ? EPI || LPR >= 32 || PIPE : PIPE && LPR == 32);
+    // (two address registers per load in flight; on the plain walk of 64-column slices it is the index window's staged block
+    // that tips them over); the prefetching walk on 128-column slices; list-driven walks (FB = 8) with 64-bit offsets on
+    // 128-column slices, and adjoint ones with 64-bit offsets or on 128-column slices
+    const bool heavy = VEC == 4 && (LISTS ? (SUM && (!OFF32 || LPR >= 32)) || (!OFF32 && LPR >= 32) : !OFF32 || (PIPE && LPR == 32));
     if (heavy) return H2GCN_OFF64_HEAVY_MIN_WAVES - bf16_less;
     // everything else: 6 (the 128 / 256-column slices have a knob of their own)
     return (LPR >= 32 ? H2GCN_WIDE_MIN_WAVES : kMinWavesPerSimd) - bf16_less;
@@ -1150,6 +1402,20 @@ __global__ __launch_bounds__(kBlock, (min_waves_per_simd<VEC, LPR, EXACT, SUM, O
     if constexpr (SHORT && EXACT && (kWave / LPR == 2 || kWave / LPR == 4)) {
         in_tile_short_rows<TS, TD, VEC, LPR, SUM, OFF32, EPI, FB>(p, lane, rpw, row0, rows_here, rp_lo, rp_hi, (int64_t)lane_off0, src_col_begin, lcol, ecol);
         return;
+    }
+    if constexpr (uses_index_window<LPR, EXACT, PIPE, SHORT, EPI, LISTS>()) {
+        // ---- the plain tile walk of 64-column slices on the index window; selections of more hops than the rings are
+        //      sized for keep the walk below ----
+        __shared__ uint32_t ring[kWavesPerBlock][kRingHops][2 * kRingCap];
+        bool fits = n_sel <= kRingHops;  // ... and a wave whose range of a hop does not fit 32-bit relative indices (long segments inside)
+#pragma unroll
+        for (int s = 0; s < kRingHops; ++s)
+            if (s < n_sel && seg_bound(s * (rpw + 1) + rows_here) - seg_bound(s * (rpw + 1)) > kRingMaxRange) fits = false;
+        if (fits) {
+            window_tile_walk<TS, TD, VEC, LPR, SUM, OFF32, EPI, kMainB>(p, lane, rpw, row0, rows_here, rp, (int64_t)lane_off0, src_col_begin, lcol, ecol,
+                                                                        ring[wave]);
+            return;
+        }
     }
     if constexpr (PIPE && EXACT) {
         // ---- software-pipelined walk over the wave's (row, hop) segments: prefetch the next segment's first
