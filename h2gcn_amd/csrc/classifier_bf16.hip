@@ -7,18 +7,6 @@
 // upcast X, an fp32 dX too, and a bf16 dX is that value's .to(bfloat16).
 #include "classifier_kernels.hip.h"
 
-namespace {
-
-// the layout rule of every bf16 array (as for the bf16 SpMM): 4-byte aligned base, even row stride -- each lane's 8-byte access
-// is then dword-aligned whatever K is
-int check_bf16_array(const char* fn, const char* ptr_name, const void* p, const char* ld_name, int64_t ld) {
-    if ((uintptr_t)p & 3u) return fail(H2GCN_ERR_INVALID_ARGUMENT, "%s: %s must be 4-byte aligned (bf16 rows are read in dwords)", fn, ptr_name);
-    if (ld & 1) return fail(H2GCN_ERR_INVALID_ARGUMENT, "%s: %s = %lld must be even (bf16 rows are read in dwords)", fn, ld_name, (long long)ld);
-    return H2GCN_OK;
-}
-
-}  // namespace
-
 extern "C" {
 
 int h2gcn_dropout_dense_bf16(const uint16_t* X, int64_t ldx, int64_t n_rows, int32_t K, const float* W, int32_t C, const float* bias,

@@ -23,6 +23,15 @@
 namespace {
 
 using h2gcn::fail;
+
+// the layout rule of every bf16 array (as for the bf16 SpMM): 4-byte aligned base, even row stride -- each lane's 8-byte access
+// is then dword-aligned whatever K is
+int check_bf16_array(const char* fn, const char* ptr_name, const void* p, const char* ld_name, int64_t ld) {
+    if ((uintptr_t)p & 3u) return fail(H2GCN_ERR_INVALID_ARGUMENT, "%s: %s must be 4-byte aligned (bf16 rows are read in dwords)", fn, ptr_name);
+    if (ld & 1) return fail(H2GCN_ERR_INVALID_ARGUMENT, "%s: %s = %lld must be even (bf16 rows are read in dwords)", fn, ld_name, (long long)ld);
+    return H2GCN_OK;
+}
+
 using f32x4 = float __attribute__((ext_vector_type(4)));
 typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));
 typedef uint32_t u2u __attribute__((ext_vector_type(2), aligned(4)));   // four bf16: base 4-byte aligned, even strides, k % 4 == 0

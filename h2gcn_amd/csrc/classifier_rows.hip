@@ -8,12 +8,6 @@
 
 namespace {
 
-int check_bf16_array(const char* fn, const char* ptr_name, const void* p, const char* ld_name, int64_t ld) {
-    if ((uintptr_t)p & 3u) return fail(H2GCN_ERR_INVALID_ARGUMENT, "%s: %s must be 4-byte aligned (bf16 rows are read in dwords)", fn, ptr_name);
-    if (ld & 1) return fail(H2GCN_ERR_INVALID_ARGUMENT, "%s: %s = %lld must be even (bf16 rows are read in dwords)", fn, ld_name, (long long)ld);
-    return H2GCN_OK;
-}
-
 // what every row-selected call checks before the device is touched
 int check_rows(const char* fn, const void* X, int64_t n_rows, const void* W, const int32_t* rows, int64_t n_sel) {
     if (n_rows < 0) return fail(H2GCN_ERR_INVALID_ARGUMENT, "%s: n_rows = %lld is negative", fn, (long long)n_rows);

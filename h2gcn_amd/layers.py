@@ -9,12 +9,15 @@ hops are aggregated by ONE fused kernel launch that writes the stacked layout di
 """
 from __future__ import annotations
 
-from typing import Iterable, Optional
-
+import ctypes
+import functools
 import os
+from dataclasses import dataclass, field
+from typing import Iterable, Optional
 
 import torch
 
+from . import _capi
 from .hops import HopPlan, RowSelection
 
 
@@ -289,6 +292,90 @@ class SliceLayer(torch.nn.Module):
         return inputs[:, self.sliceObj]
 
 
+@dataclass(frozen=True)
+class ConcatLayout:
+    """The column layout of the concat buffer ``[r_K | r_0 | r_1 | ... | r_{K-1}]`` of ``rounds = K`` aggregation rounds over
+    ``n_hops = H`` hop matrices on an embedding of width ``w0``: round ``k`` is ``widths[k] = w0 * H**k`` columns wide and starts
+    at column ``offsets[k]``.  The only place that knows the order of the slots."""
+
+    w0: int
+    n_hops: int
+    rounds: int
+    widths: tuple = field(init=False)
+    offsets: tuple = field(init=False)
+    total: int = field(init=False)
+
+    def __post_init__(self):
+        widths = tuple(self.w0 * self.n_hops ** k for k in range(self.rounds + 1))
+        offsets = [0] * (self.rounds + 1)   # r_K first, then r_0 .. r_{K-1}
+        pos = widths[self.rounds]
+        for k in range(self.rounds):
+            offsets[k] = pos
+            pos += widths[k]
+        for name, value in (("widths", widths), ("offsets", tuple(offsets)), ("total", pos)):
+            object.__setattr__(self, name, value)
+
+    def slot(self, t: torch.Tensor, k: int) -> torch.Tensor:
+        """The columns of ``r_k`` in a ``[n, total]`` tensor (a view)."""
+        return t[:, self.offsets[k]:self.offsets[k] + self.widths[k]]
+
+    def hops(self, r_k: torch.Tensor, k: int) -> torch.Tensor:
+        """``r_k [n, widths[k]]`` (``k >= 1``) as the ``[n, H, widths[k-1]]`` output of round ``k``'s hop launch (a view)."""
+        return r_k.unflatten(1, (self.n_hops, self.widths[k - 1]))
+
+    def hop_view(self, t: torch.Tensor, k: int) -> torch.Tensor:
+        """``hops(slot(t, k), k)``: the slot of round ``k >= 1`` as ``[n, H, widths[k-1]]``."""
+        return self.hops(self.slot(t, k), k)
+
+
+#: ``concat_layout(w0, n_hops, rounds)``: the (immutable, hence shared) layout -- a training loop asks for the same one every step
+concat_layout = functools.lru_cache(maxsize=64)(ConcatLayout)
+
+
+def _propagate(layout: ConcatLayout, plan: HopPlan, r0: torch.Tensor, out: Optional[torch.Tensor], reuse: bool,
+               dtype: torch.dtype) -> torch.Tensor:
+    """The forward of the fused propagation (arguments checked by :func:`_check_propagation`): ``r0`` into its slot of ``out`` (or
+    of a fresh buffer), then round ``k`` from slot ``k-1`` into slot ``k`` through the kernel's strides.  ``reuse``: nothing is
+    computed."""
+    n = r0.shape[0]
+    # (out.view: a new tensor object on the caller's storage -- autograd marks IT as the node's output)
+    buf = concat_buffer(n, layout.total, r0.device, dtype) if out is None else out.view(n, layout.total)
+    if not reuse:
+        layout.slot(buf, 0).copy_(r0)
+        for k in range(1, layout.rounds + 1):
+            plan.spmm(layout.slot(buf, k - 1), out=layout.hop_view(buf, k))
+    return buf
+
+
+def _backward_walk(layout: ConcatLayout, grad: torch.Tensor, adjoint, add_slot=None, bf16: bool = False, in_place=None) -> torch.Tensor:
+    """The gradient of ``r_0`` from the gradient ``grad [n, total]`` of a concat buffer (full, or the compact rows of the
+    rows-only path): the rounds in reverse, and THE statement of their order of operations (bf16: of roundings) --
+    :class:`_FusedPropagation`, :class:`_PropagationClassifyRowsFn` and ``partition._ShardedFusedPropagation`` all walk here::
+
+        t       = adjoint(k, g_k)                    accumulated and returned in fp32 (g_K = slot_K(grad), read in place)
+        t      += slot_{k-1}(grad)                   a bf16 slot widened exactly to fp32
+        g_{k-1} = t rounded to bf16 (nearest even)   for k > 1 of a bf16 walk
+        g_{k-1} = t                                  otherwise: fp32 walks, and k = 1 of a bf16 walk (d r_0 stays fp32)
+
+    ``adjoint(k, g, **kw)``: the adjoint of round ``k`` on ``g [n, H, widths[k-1]]``.  ``add_slot(t, slot)``: the second line
+    where ``t`` and the slot differ in their rows (rows-only).  ``in_place(k)``: true where round ``k``
+    may instead be ADDED to ``slot_{k-1}`` inside ``grad`` itself by the adjoint's store (``adjoint(k, g, out=slot,
+    accumulate=True)``; fp32 only): the same sum, one pass and one tensor less."""
+    g_k = layout.slot(grad, layout.rounds)
+    for k in range(layout.rounds, 0, -1):
+        slot = layout.slot(grad, k - 1)
+        if in_place is not None and in_place(k):
+            g_k = adjoint(k, layout.hops(g_k, k), out=slot, accumulate=True)
+            continue
+        t = adjoint(k, layout.hops(g_k, k))
+        if add_slot is None:
+            t += slot
+        else:
+            add_slot(t, slot)
+        g_k = t.to(torch.bfloat16) if bf16 and k > 1 else t
+    return g_k
+
+
 class _FusedPropagation(torch.autograd.Function):
     """K rounds of hop aggregation written straight into the final concat buffer.
 
@@ -303,68 +390,29 @@ class _FusedPropagation(torch.autograd.Function):
 
     ``dtype=torch.bfloat16``: the buffer is bf16.  ``r0`` (fp32) is rounded into its slot (nearest even) and every round is
     the bf16 -> bf16 launch (fp32 accumulation, one rounding at the store) from one slot to the next.  The backward receives
-    the buffer's gradient ``g`` in bf16 and walks the rounds ``k = K .. 1`` with this ORDER OF ROUNDINGS (the specification;
-    ``g_K`` is the slot of ``r_K`` in ``g``)::
-
-        t       = spmm_t(g_k)  accumulated and returned in fp32
-        t      += slot_{k-1}(g) widened exactly to fp32
-        g_{k-1} = t rounded to bf16 (nearest even)   for k > 1
-        d r_0   = t, left in fp32                    for k = 1     (the gradient handed to the embedding layer is fp32)
-
-    i.e. one rounding per round on the way down and none on the last.  ``private_grad`` (the in-place accumulate) applies
-    to fp32 only: a bf16 slot cannot be accumulated into.
+    the buffer's gradient in bf16 and walks the rounds ``k = K .. 1`` in the order of roundings that :func:`_backward_walk`
+    specifies: one rounding per round on the way down and none on the last (the gradient handed to the embedding layer is
+    fp32).  ``private_grad`` (the in-place accumulate) applies to fp32 only: a bf16 slot cannot be accumulated into.
     """
 
     @staticmethod
-    def forward(ctx, r0: torch.Tensor, plan: HopPlan, rounds: int, out: Optional[torch.Tensor] = None, reuse: bool = False,
-                private_grad: bool = False, dtype: Optional[torch.dtype] = None):
-        """``private_grad``: the caller guarantees that the gradient tensor this node's backward receives is a temporary
-        nobody else reads (see :func:`fused_propagation`).  ``out``: a caller-owned ``[N, W]`` contiguous buffer to fill instead of a fresh one.  ``reuse``: ``out`` ALREADY
-        holds the propagation of this very ``r0`` (see :func:`fused_propagation`) -- nothing is computed, the buffer only
-        enters the autograd graph (the backward needs none of the forward's values: the rounds are linear)."""
-        n, w0 = r0.shape
-        H = plan.n_hops
-        dtype = torch.float32 if dtype is None else dtype
-        widths = [w0 * H ** k for k in range(rounds + 1)]
-        total = sum(widths)
-        # column offsets: r_K first, then r_0 .. r_{K-1}
-        off = [0] * (rounds + 1)
-        off[rounds] = 0
-        pos = widths[rounds]
-        for k in range(rounds):
-            off[k] = pos
-            pos += widths[k]
-        if out is None:
-            buf = concat_buffer(n, total, r0.device, dtype)
-        else:
-            if out.shape != (n, total) or out.dtype != dtype or out.device != r0.device or not out.is_contiguous():
-                raise ValueError(f"fused_propagation: out must be a contiguous {str(dtype).replace('torch.', '')} [{n}, {total}] tensor on {r0.device}")
-            buf = out.view(n, total)   # a new tensor object on the caller's storage: autograd marks IT as this node's output
-        if not reuse:
-            buf[:, off[0]:off[0] + w0].copy_(r0)
-            for k in range(1, rounds + 1):
-                src = buf[:, off[k - 1]:off[k - 1] + widths[k - 1]]
-                dst = buf[:, off[k]:off[k] + widths[k]].unflatten(1, (H, widths[k - 1]))
-                plan.spmm(src, out=dst)
-        ctx.plan, ctx.rounds, ctx.widths, ctx.off = plan, rounds, widths, off
+    def forward(ctx, r0: torch.Tensor, plan: HopPlan, layout: ConcatLayout, out: Optional[torch.Tensor], reuse: bool,
+                private_grad: bool, dtype: torch.dtype):
+        """``private_grad`` / ``out`` / ``reuse``: see :func:`fused_propagation` (the backward needs none of the forward's
+        values: the rounds are linear)."""
+        ctx.plan, ctx.layout = plan, layout
         ctx.private_grad = bool(private_grad) and dtype == torch.float32
         ctx.bf16 = dtype == torch.bfloat16
-        return buf
+        return _propagate(layout, plan, r0, out, reuse, dtype)
 
     @staticmethod
     def backward(ctx, grad: torch.Tensor):
-        plan, K, widths, off = ctx.plan, ctx.rounds, ctx.widths, ctx.off
-        H = plan.n_hops
-        g_k = grad[:, off[K]:off[K] + widths[K]]  # d r_K: a view, read in place by the adjoint launch
-        if ctx.bf16:   # the rounding order of the class docstring
+        plan, layout = ctx.plan, ctx.layout
+        if ctx.bf16:   # the adjoint reads bf16 rows in dwords
             if grad.stride(1) != 1 or grad.stride(0) % 2 or grad.data_ptr() % 4:
                 grad = grad.contiguous()
-                g_k = grad[:, off[K]:off[K] + widths[K]]
-            for k in range(K, 0, -1):
-                t = plan.spmm_t(g_k.unflatten(1, (H, widths[k - 1])), out_dtype=torch.float32)
-                t += grad[:, off[k - 1]:off[k - 1] + widths[k - 1]]
-                g_k = t.to(torch.bfloat16) if k > 1 else t
-            return g_k, None, None, None, None, None, None
+            d_r0 = _backward_walk(layout, grad, lambda k, g: plan.spmm_t(g, out_dtype=torch.float32), bf16=True)
+            return d_r0, None, None, None, None, None, None
         # The adjoint of round k is ADDED to the slot of r_{k-1} inside the incoming gradient itself (the library's
         # accumulate flag: the `+=` rides on the adjoint's store) -- but ONLY when the caller has vouched that this tensor is a
         # temporary of its own (`private_grad`: models.H2GCN sets it when the buffer's sole consumer is a layer whose
@@ -373,18 +421,13 @@ class _FusedPropagation(torch.autograd.Function):
         # so the default is a fresh tensor per round plus one `+=` pass.  Also needed: an ordinary dense gradient.
         dense = (ctx.private_grad and grad.is_contiguous() and isinstance(plan, HopPlan)
                  and os.environ.get("H2GCN_BACKWARD_IN_PLACE", "1") != "0")
-        for k in range(K, 0, -1):
-            slot = grad[:, off[k - 1]:off[k - 1] + widths[k - 1]]
+
+        def in_place(k):
             # (not where the plain launch would run in the in-tile short-row mode -- short-throughout operands, where that mode is
             # worth more than the saved pass; list-driven / wave-walk launches lose nothing on the accumulating tile walk)
-            in_place = dense and plan.schedule(widths[k - 1], ld_src=grad.stride(0), adjoint=True)["segment_walk"] != "lane group per segment (short rows)"
-            if in_place:
-                g_k = plan.spmm_t(g_k.unflatten(1, (H, widths[k - 1])), out=slot, accumulate=True)
-            else:
-                g_prev = plan.spmm_t(g_k.unflatten(1, (H, widths[k - 1])))
-                g_prev += slot
-                g_k = g_prev
-        return g_k, None, None, None, None, None, None
+            return dense and plan.schedule(layout.widths[k - 1], ld_src=grad.stride(0), adjoint=True)["segment_walk"] != "lane group per segment (short rows)"
+
+        return _backward_walk(layout, grad, lambda k, g, **kw: plan.spmm_t(g, **kw), in_place=in_place), None, None, None, None, None, None
 
 
 def concat_buffer(n_rows: int, width: int, device, dtype: torch.dtype = torch.float32) -> torch.Tensor:
@@ -415,38 +458,112 @@ def fused_propagation(plan: HopPlan, r0: torch.Tensor, rounds: int, out: Optiona
 
     ``dtype``: ``None`` / ``torch.float32`` (default) or ``torch.bfloat16`` -- the dtype of the buffer; ``r0`` stays float32.
     With bfloat16 every hop launch moves half the bytes (fp32 accumulation, one rounding per slot); the gradient of the
-    buffer is bfloat16 and the gradient returned for ``r0`` float32 (rounding order: :class:`_FusedPropagation`).  ``r0``
+    buffer is bfloat16 and the gradient returned for ``r0`` float32 (rounding order: :func:`_backward_walk`).  ``r0``
     needs an even width (bf16 rows are read in dwords)."""
+    layout, dtype = _check_propagation("fused_propagation", plan, r0, rounds, out, reuse, dtype)
+    if r0.requires_grad and torch.is_grad_enabled():
+        return _FusedPropagation.apply(r0, plan, layout, out, reuse, private_grad, dtype)
+    return _propagate(layout, plan, r0, out, reuse, dtype)
+
+
+def _check_propagation(name: str, plan, r0: torch.Tensor, rounds: int, out: Optional[torch.Tensor], reuse: bool,
+                       dtype: Optional[torch.dtype], rows_only: bool = False):
+    """The argument checks of :func:`fused_propagation` and :func:`fused_propagation_classify_rows` (``name``: the caller, for
+    the messages; ``rows_only``: the latter, whose ``r0`` is a float32 CUDA tensor whatever the buffer's dtype).  Returns the
+    buffer's ``(layout, dtype)``."""
     if rounds < 1:
         raise ValueError("rounds must be >= 1")
     if dtype not in (None, torch.float32, torch.bfloat16):
-        raise ValueError(f"fused_propagation: dtype must be float32 or bfloat16, got {dtype}")
-    if dtype == torch.bfloat16:
-        if r0.dtype != torch.float32:
-            raise ValueError(f"fused_propagation: r0 must be float32 (it is rounded into the bfloat16 buffer), got {r0.dtype}")
-        if r0.dim() == 2 and r0.shape[1] % 2:
-            raise ValueError(f"fused_propagation: a bfloat16 buffer needs an even embedding width, got {r0.shape[1]} "
-                             "(bf16 rows are read in dwords: pad the hidden width to an even number or use float32)")
-    if r0.dim() != 2 or r0.shape[0] != plan.n_cols or plan.n_rows != plan.n_cols:
+        raise ValueError(f"{name}: dtype must be float32 or bfloat16, got {dtype}")
+    dtype = torch.float32 if dtype is None else dtype
+    bf16 = dtype == torch.bfloat16
+    if bf16 and not rows_only and r0.dtype != torch.float32:
+        raise ValueError(f"{name}: r0 must be float32 (it is rounded into the bfloat16 buffer), got {r0.dtype}")
+    square = r0.dim() == 2 and r0.shape[0] == plan.n_cols and plan.n_rows == plan.n_cols
+    if rows_only and not (square and r0.is_cuda and r0.dtype == torch.float32):
+        raise ValueError(f"r0 must be a float32 CUDA tensor [{plan.n_cols}, d] and the hop matrices square")
+    if not square:
         raise ValueError(f"r0 must be [{plan.n_cols}, d] and the hop matrices square")
+    if bf16 and r0.shape[1] % 2:
+        raise ValueError(f"{name}: a bfloat16 buffer needs an even embedding width, got {r0.shape[1]}" + ("" if rows_only else
+                         " (bf16 rows are read in dwords: pad the hidden width to an even number or use float32)"))
     if reuse and out is None:
-        raise ValueError("fused_propagation: reuse=True needs the buffer that holds the propagation (out=)")
-    if r0.requires_grad and torch.is_grad_enabled():
-        return _FusedPropagation.apply(r0, plan, rounds, out, reuse, private_grad, dtype)
-    return _FusedPropagation.forward(_NoCtx(), r0, plan, rounds, out, reuse, False, dtype)
+        raise ValueError(f"{name}: reuse=True needs the buffer that holds the propagation (out=)")
+    layout = concat_layout(r0.shape[1], plan.n_hops, rounds)
+    _check_out(out, r0.shape[0], layout.total, dtype, r0.device)
+    return layout, dtype
 
 
-class _NoCtx:
-    pass
+def _check_out(out: Optional[torch.Tensor], n: int, total: int, dtype: torch.dtype, device) -> None:
+    """``out=`` of a fused propagation, single-GPU or row-partitioned: the whole ``[n, total]`` buffer or nothing."""
+    if out is not None and (out.shape != (n, total) or out.dtype != dtype or out.device != device or not out.is_contiguous()):
+        raise ValueError(f"fused_propagation: out must be a contiguous {str(dtype).replace('torch.', '')} [{n}, {total}] tensor on {device}")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
 # Dropout + output Dense in one pass over the concat buffer (csrc/classifier.hip)
 # ---------------------------------------------------------------------------------------------------------------------
 def _dd_workspace(n: int, k: int, c: int, device) -> torch.Tensor:
-    from . import _capi
     nbytes = int(_capi.lib().h2gcn_dropout_dense_workspace_bytes(n, k, c))
     return torch.empty(nbytes, dtype=torch.uint8, device=device)
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def _classifier_launch(stem: str, x, sel: Optional[RowSelection], rows_out: int, c: int, *args) -> None:
+    """One call of ``<stem>[_rows]_{f32,bf16}``, the symbol picked from ``(x.dtype, sel is None)``.  ``args``: the arguments in
+    front of ``(workspace, workspace_bytes, stream)``, which every symbol takes next (the workspace sized for ``rows_out`` rows);
+    the row-selected symbols end in ``(rows, n_sel)``."""
+    fn = getattr(_capi.lib(), stem + ("" if sel is None else "_rows") + ("_bf16" if x.dtype == torch.bfloat16 else "_f32"))
+    ws = _dd_workspace(rows_out, x.shape[1], c, x.device)
+    with torch.cuda.device(x.device):
+        stream = torch.cuda.current_stream(x.device).cuda_stream
+        _capi.check(fn(*args, _ptr(ws), ws.numel(), ctypes.c_void_p(stream), *(() if sel is None else (_ptr(sel.rows), len(sel)))))
+
+
+def _classifier_forward(x, w, bias, keep_prob, seed, step_dev, sel: Optional[RowSelection] = None) -> torch.Tensor:
+    """``Z = (X .* M / keep) @ W + b`` on the library's kernels: ``[n, C]``, or -- ``sel`` -- the logits ``[len(sel), C]`` of rows
+    ``sel.rows`` of ``x``.  ``x`` float32 or bfloat16, ``w`` contiguous."""
+    n, k = x.shape
+    c, m = w.shape[1], n if sel is None else len(sel)
+    z = torch.empty((m, c), dtype=torch.float32, device=x.device)
+    _classifier_launch("h2gcn_dropout_dense", x, sel, m, c,
+                       _ptr(x), x.stride(0), n, k, _ptr(w), c, _ptr(bias), float(keep_prob), int(seed), _ptr(step_dev),
+                       _ptr(z), z.stride(0))
+    return z
+
+
+def _classifier_backward(x, w, g, keep_prob, seed, step_dev, need_dx: bool, need_dw: bool, sel: Optional[RowSelection] = None):
+    """``(dX in x's dtype, dW [K, C] float32)`` for the contiguous logit gradient ``g`` (either may be None: not computed).
+    ``sel``: ``g`` and ``dX`` are compact, ``[len(sel), .]``."""
+    n, k = x.shape
+    c, m = w.shape[1], n if sel is None else len(sel)
+    bf16 = x.dtype == torch.bfloat16
+    # (a bf16 dX needs an even row stride: an odd K gets one padding column)
+    dx = torch.empty((m, k + (k % 2 if bf16 else 0)), dtype=x.dtype, device=x.device)[:, :k] if need_dx else None
+    dw = torch.empty((k, c), dtype=torch.float32, device=x.device) if need_dw else None
+    if need_dx or need_dw:
+        dx_dtype = (_capi.DTYPE_BF16,) if bf16 else ()   # an argument of the _bf16 symbols only
+        _classifier_launch("h2gcn_dropout_dense_backward", x, sel, m, c,
+                           _ptr(x), x.stride(0), n, k, _ptr(w), c, _ptr(g), g.stride(0), float(keep_prob), int(seed), _ptr(step_dev),
+                           *dx_dtype, _ptr(dx), dx.stride(0) if need_dx else k, _ptr(dw))
+    return dx, dw
+
+
+def _dd_rows_forward(x, w, bias, keep_prob, seed, step_dev, sel: RowSelection) -> torch.Tensor:
+    """The row-selected forward under its earlier name and argument order (tests/test_special_values_gpu.py calls it)."""
+    return _classifier_forward(x, w, bias, keep_prob, seed, step_dev, sel)
+
+
+def _dd_rows_backward(x, w, g, keep_prob, seed, step_dev, sel: RowSelection, need_dx: bool, need_dw: bool):
+    """The row-selected backward under its earlier name and argument order."""
+    return _classifier_backward(x, w, g, keep_prob, seed, step_dev, need_dx, need_dw, sel)
+
+
+def _saved_step(step_dev, device) -> torch.Tensor:
+    return step_dev if step_dev is not None else torch.empty(0, device=device)
 
 
 class _DropoutDenseFn(torch.autograd.Function):
@@ -457,104 +574,24 @@ class _DropoutDenseFn(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, kernel, bias, keep_prob, seed, step_dev):
-        import ctypes as C
-
-        from . import _capi
-        n, k = x.shape
-        c = kernel.shape[1]
         w = kernel.contiguous()
-        z = torch.empty((n, c), dtype=torch.float32, device=x.device)
-        ws = _dd_workspace(n, k, c, x.device)
-        with torch.cuda.device(x.device):
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-            fn = _capi.lib().h2gcn_dropout_dense_bf16 if x.dtype == torch.bfloat16 else _capi.lib().h2gcn_dropout_dense_f32
-            _capi.check(fn(
-                C.c_void_p(x.data_ptr()), x.stride(0), n, k, C.c_void_p(w.data_ptr()), c,
-                C.c_void_p(bias.data_ptr()) if bias is not None else None, float(keep_prob), int(seed),
-                C.c_void_p(step_dev.data_ptr()) if step_dev is not None else None, C.c_void_p(z.data_ptr()), z.stride(0),
-                C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(stream)))
-        ctx.save_for_backward(x, w, step_dev if step_dev is not None else torch.empty(0, device=x.device))
+        ctx.save_for_backward(x, w, _saved_step(step_dev, x.device))
         ctx.keep_prob, ctx.seed, ctx.has_bias, ctx.has_step = float(keep_prob), int(seed), bias is not None, step_dev is not None
-        return z
+        return _classifier_forward(x, w, bias, keep_prob, seed, step_dev)
 
     @staticmethod
     def backward(ctx, g):
-        import ctypes as C
-
-        from . import _capi
         x, w, step = ctx.saved_tensors
-        n, k = x.shape
-        c = w.shape[1]
         g = g.contiguous()
-        need_dx, need_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        bf16 = x.dtype == torch.bfloat16
-        # (a bf16 dX needs an even row stride: an odd K gets one padding column)
-        dx = torch.empty((n, k + (k % 2 if bf16 else 0)), dtype=x.dtype, device=x.device)[:, :k] if need_dx else None
-        dw = torch.empty((k, c), dtype=torch.float32, device=x.device) if need_dw else None
-        if need_dx or need_dw:
-            ws = _dd_workspace(n, k, c, x.device)
-            with torch.cuda.device(x.device):
-                stream = torch.cuda.current_stream(x.device).cuda_stream
-                fn, dx_dtype = ((_capi.lib().h2gcn_dropout_dense_backward_bf16, (_capi.DTYPE_BF16,)) if bf16
-                                else (_capi.lib().h2gcn_dropout_dense_backward_f32, ()))
-                _capi.check(fn(
-                    C.c_void_p(x.data_ptr()), x.stride(0), n, k, C.c_void_p(w.data_ptr()), c, C.c_void_p(g.data_ptr()), g.stride(0),
-                    ctx.keep_prob, ctx.seed, C.c_void_p(step.data_ptr()) if ctx.has_step else None, *dx_dtype,
-                    C.c_void_p(dx.data_ptr()) if need_dx else None, dx.stride(0) if need_dx else k,
-                    C.c_void_p(dw.data_ptr()) if need_dw else None, C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(stream)))
+        dx, dw = _classifier_backward(x, w, g, ctx.keep_prob, ctx.seed, step if ctx.has_step else None,
+                                      ctx.needs_input_grad[0], ctx.needs_input_grad[1])
         db = g.sum(0) if ctx.has_bias and ctx.needs_input_grad[2] else None
         return dx, dw, db, None, None, None
 
 
 def _rows_symbols() -> None:
-    from . import _capi
     if not _capi.has("h2gcn_dropout_dense_rows_f32"):
         raise RuntimeError(f"{_capi.library_path()} predates the row-selected classifier (h2gcn_dropout_dense_rows_f32): rebuild it")
-
-
-def _dd_rows_forward(x, w, bias, keep_prob, seed, step_dev, sel: RowSelection) -> torch.Tensor:
-    """``Z_c [m, C]``: the logits of rows ``sel.rows`` of ``x`` (``h2gcn_dropout_dense_rows_f32 / _bf16``)."""
-    import ctypes as C
-
-    from . import _capi
-    n, k = x.shape
-    c, m = w.shape[1], len(sel)
-    z = torch.empty((m, c), dtype=torch.float32, device=x.device)
-    ws = _dd_workspace(m, k, c, x.device)
-    with torch.cuda.device(x.device):
-        stream = torch.cuda.current_stream(x.device).cuda_stream
-        fn = _capi.lib().h2gcn_dropout_dense_rows_bf16 if x.dtype == torch.bfloat16 else _capi.lib().h2gcn_dropout_dense_rows_f32
-        _capi.check(fn(
-            C.c_void_p(x.data_ptr()), x.stride(0), n, k, C.c_void_p(w.data_ptr()), c,
-            C.c_void_p(bias.data_ptr()) if bias is not None else None, float(keep_prob), int(seed),
-            C.c_void_p(step_dev.data_ptr()) if step_dev is not None else None, C.c_void_p(z.data_ptr()), z.stride(0),
-            C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(stream), C.c_void_p(sel.rows.data_ptr()), m))
-    return z
-
-
-def _dd_rows_backward(x, w, g, keep_prob, seed, step_dev, sel: RowSelection, need_dx: bool, need_dw: bool):
-    """``(dX_c [m, K] in x's dtype, dW [K, C])`` for the compact logit gradient ``g [m, C]`` (either may be None)."""
-    import ctypes as C
-
-    from . import _capi
-    n, k = x.shape
-    c, m = w.shape[1], len(sel)
-    bf16 = x.dtype == torch.bfloat16
-    dx = torch.empty((m, k + (k % 2 if bf16 else 0)), dtype=x.dtype, device=x.device)[:, :k] if need_dx else None
-    dw = torch.empty((k, c), dtype=torch.float32, device=x.device) if need_dw else None
-    if need_dx or need_dw:
-        ws = _dd_workspace(m, k, c, x.device)
-        with torch.cuda.device(x.device):
-            stream = torch.cuda.current_stream(x.device).cuda_stream
-            fn, dx_dtype = ((_capi.lib().h2gcn_dropout_dense_backward_rows_bf16, (_capi.DTYPE_BF16,)) if bf16
-                            else (_capi.lib().h2gcn_dropout_dense_backward_rows_f32, ()))
-            _capi.check(fn(
-                C.c_void_p(x.data_ptr()), x.stride(0), n, k, C.c_void_p(w.data_ptr()), c, C.c_void_p(g.data_ptr()), g.stride(0),
-                float(keep_prob), int(seed), C.c_void_p(step_dev.data_ptr()) if step_dev is not None else None, *dx_dtype,
-                C.c_void_p(dx.data_ptr()) if need_dx else None, dx.stride(0) if need_dx else k,
-                C.c_void_p(dw.data_ptr()) if need_dw else None, C.c_void_p(ws.data_ptr()), ws.numel(), C.c_void_p(stream),
-                C.c_void_p(sel.rows.data_ptr()), m))
-    return dx, dw
 
 
 class _DropoutDenseRowsFn(torch.autograd.Function):
@@ -565,15 +602,15 @@ class _DropoutDenseRowsFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, kernel, bias, keep_prob, seed, step_dev, sel):
         w = kernel.contiguous()
-        ctx.save_for_backward(x, w, step_dev if step_dev is not None else torch.empty(0, device=x.device))
+        ctx.save_for_backward(x, w, _saved_step(step_dev, x.device))
         ctx.keep_prob, ctx.seed, ctx.has_bias, ctx.has_step, ctx.sel = float(keep_prob), int(seed), bias is not None, step_dev is not None, sel
-        return _dd_rows_forward(x, w, bias, keep_prob, seed, step_dev, sel)
+        return _classifier_forward(x, w, bias, keep_prob, seed, step_dev, sel)
 
     @staticmethod
     def backward(ctx, g):
         x, w, step = ctx.saved_tensors
         g = g.contiguous()
-        _, dw = _dd_rows_backward(x, w, g, ctx.keep_prob, ctx.seed, step if ctx.has_step else None, ctx.sel, False, ctx.needs_input_grad[1])
+        _, dw = _classifier_backward(x, w, g, ctx.keep_prob, ctx.seed, step if ctx.has_step else None, False, ctx.needs_input_grad[1], ctx.sel)
         db = g.sum(0) if ctx.has_bias and ctx.needs_input_grad[2] else None
         return None, dw, db, None, None, None, None
 
@@ -590,39 +627,35 @@ class _PropagationClassifyRowsFn(torch.autograd.Function):
                           t[rows] += g_c[:, slot_{K-1}]                           (rows are unique: deterministic)
         rounds K-1 .. 1:  t = plan.spmm_t(g_k);  t[rows] += g_c[:, slot_{k-1}]
 
-    bfloat16 keeps :class:`_FusedPropagation`'s order of roundings: ``t`` is accumulated in fp32, the slot addend is widened
-    exactly, one rounding to bfloat16 per round for ``k > 1``, the last round stays fp32."""
+    -- :func:`_backward_walk` over the compact gradient, with these two as its adjoint and its slot addition; bfloat16 rounds
+    where that walk says."""
 
     @staticmethod
-    def forward(ctx, r0, kernel, bias, plan, sel, rounds, out, reuse, dtype, keep_prob, seed, step_dev):
-        prop = _NoCtx()
-        buf = _FusedPropagation.forward(prop, r0, plan, rounds, out, reuse, False, dtype)
+    def forward(ctx, r0, kernel, bias, plan, sel, layout, out, reuse, dtype, keep_prob, seed, step_dev):
+        buf = _propagate(layout, plan, r0, out, reuse, dtype)
         w = kernel.contiguous()
-        z = _dd_rows_forward(buf, w, bias, keep_prob, seed, step_dev, sel)
-        ctx.save_for_backward(buf, w, step_dev if step_dev is not None else torch.empty(0, device=buf.device))
-        ctx.plan, ctx.sel, ctx.rounds, ctx.widths, ctx.off = plan, sel, rounds, prop.widths, prop.off
+        z = _classifier_forward(buf, w, bias, keep_prob, seed, step_dev, sel)
+        ctx.save_for_backward(buf, w, _saved_step(step_dev, buf.device))
+        ctx.plan, ctx.sel, ctx.layout = plan, sel, layout
         ctx.keep_prob, ctx.seed, ctx.has_bias, ctx.has_step = float(keep_prob), int(seed), bias is not None, step_dev is not None
         return z
 
     @staticmethod
     def backward(ctx, g):
         buf, w, step = ctx.saved_tensors
-        plan, sel, K, widths, off = ctx.plan, ctx.sel, ctx.rounds, ctx.widths, ctx.off
-        H = plan.n_hops
+        plan, sel, layout = ctx.plan, ctx.sel, ctx.layout
         g = g.contiguous()
         need_r0 = ctx.needs_input_grad[0]
-        g_c, dw = _dd_rows_backward(buf, w, g, ctx.keep_prob, ctx.seed, step if ctx.has_step else None, sel, need_r0, ctx.needs_input_grad[1])
+        g_c, dw = _classifier_backward(buf, w, g, ctx.keep_prob, ctx.seed, step if ctx.has_step else None, need_r0, ctx.needs_input_grad[1], sel)
         db = g.sum(0) if ctx.has_bias and ctx.needs_input_grad[2] else None
         d_r0 = None
         if need_r0:
             bf16 = buf.dtype == torch.bfloat16
-            g_k, p = g_c[:, off[K]:off[K] + widths[K]], sel.plan    # round K gathers through A_k[rows]^T, the others through A_k^T
-            for k in range(K, 0, -1):
-                t = p.spmm_t(g_k.unflatten(1, (H, widths[k - 1])), out_dtype=torch.float32)
-                slot = g_c[:, off[k - 1]:off[k - 1] + widths[k - 1]]
-                t.index_add_(0, sel.rows_long, slot.float() if bf16 else slot)
-                g_k, p = (t.to(torch.bfloat16) if bf16 and k > 1 else t), plan
-            d_r0 = g_k
+            d_r0 = _backward_walk(
+                layout, g_c, bf16=bf16,
+                # round K gathers through A_k[rows]^T, the others through A_k^T
+                adjoint=lambda k, g_k: (sel.plan if k == layout.rounds else plan).spmm_t(g_k, out_dtype=torch.float32),
+                add_slot=lambda t, slot: t.index_add_(0, sel.rows_long, slot.float() if bf16 else slot))
         return d_r0, dw, db, None, None, None, None, None, None, None, None, None
 
 
@@ -648,29 +681,24 @@ def fused_propagation_classify_rows(plan: HopPlan, sel: RowSelection, r0: torch.
         raise ValueError(f"fused_propagation_classify_rows: dense_layer must be a DropoutDense, got {type(dense_layer).__name__}")
     if dense_layer.kernel.shape[1] > 64:
         raise ValueError(f"fused_propagation_classify_rows: the classifier kernels cover units <= 64, got {dense_layer.kernel.shape[1]}")
-    if rounds < 1:
-        raise ValueError("rounds must be >= 1")
-    if dtype not in (None, torch.float32, torch.bfloat16):
-        raise ValueError(f"fused_propagation_classify_rows: dtype must be float32 or bfloat16, got {dtype}")
-    if r0.dim() != 2 or r0.shape[0] != plan.n_cols or plan.n_rows != plan.n_cols or not r0.is_cuda or r0.dtype != torch.float32:
-        raise ValueError(f"r0 must be a float32 CUDA tensor [{plan.n_cols}, d] and the hop matrices square")
-    if dtype == torch.bfloat16 and r0.shape[1] % 2:
-        raise ValueError(f"fused_propagation_classify_rows: a bfloat16 buffer needs an even embedding width, got {r0.shape[1]}")
-    if reuse and out is None:
-        raise ValueError("fused_propagation_classify_rows: reuse=True needs the buffer that holds the propagation (out=)")
+    layout, dtype = _check_propagation("fused_propagation_classify_rows", plan, r0, rounds, out, reuse, dtype, rows_only=True)
     _rows_symbols()
     keep_prob, step = dense_layer._draw_step()
-    args = (plan, sel, rounds, out, reuse, dtype, keep_prob, dense_layer.seed, step)
     if torch.is_grad_enabled() and (r0.requires_grad or dense_layer.kernel.requires_grad):
         if not sel.plan.has_transpose and r0.requires_grad:
             raise ValueError("fused_propagation_classify_rows: sel was built without its transpose (select_rows(build_transpose=True))")
-        return _PropagationClassifyRowsFn.apply(r0, dense_layer.kernel, dense_layer.bias, *args)
-    return _PropagationClassifyRowsFn.forward(_NoCtxSave(), r0, dense_layer.kernel, dense_layer.bias, *args)
+        return _PropagationClassifyRowsFn.apply(r0, dense_layer.kernel, dense_layer.bias, plan, sel, layout, out, reuse, dtype,
+                                                keep_prob, dense_layer.seed, step)
+    buf = _propagate(layout, plan, r0, out, reuse, dtype)
+    return _classifier_forward(buf, dense_layer.kernel.contiguous(), dense_layer.bias, keep_prob, dense_layer.seed, step, sel)
 
 
-class _NoCtxSave(_NoCtx):
-    def save_for_backward(self, *tensors) -> None:
-        pass
+def _fused_classifier_covers(x: torch.Tensor, units: int) -> bool:
+    """The layout rule of the classifier kernels: a 2-D float32 or bfloat16 CUDA tensor with unit column stride, at most 64
+    units; bfloat16 rows are read in dwords (even row stride, 4-byte aligned base)."""
+    return (x.is_cuda and x.dim() == 2 and x.dtype in (torch.float32, torch.bfloat16) and units <= 64
+            and (x.shape[1] <= 1 or x.stride(1) == 1) and x.stride(0) >= x.shape[1]
+            and (x.dtype != torch.bfloat16 or (x.stride(0) % 2 == 0 and x.data_ptr() % 4 == 0)))
 
 
 class DropoutDense(torch.nn.Module):
@@ -722,34 +750,22 @@ class DropoutDense(torch.nn.Module):
         (``torch.no_grad()``); with gradients enabled ``kernel`` and ``bias`` get theirs, ``x`` must not require one."""
         if rows is not None:
             return self._forward_rows(x, rows)
-        training = self.training and self.drop_prob > 0.0
-        fused_ok = (x.is_cuda and x.dim() == 2 and x.dtype in (torch.float32, torch.bfloat16) and self.kernel.shape[1] <= 64
-                    and (x.shape[1] <= 1 or x.stride(1) == 1) and x.stride(0) >= x.shape[1])
-        if fused_ok and x.dtype == torch.bfloat16:
-            from . import _capi
-            if not _capi.has("h2gcn_dropout_dense_bf16"):
-                raise RuntimeError(f"{_capi.library_path()} predates the bf16 classifier (h2gcn_dropout_dense_bf16): rebuild it")
-            fused_ok = x.stride(0) % 2 == 0 and x.data_ptr() % 4 == 0
-        if not fused_ok:
+        if not _fused_classifier_covers(x, self.kernel.shape[1]):
             if x.dtype == torch.bfloat16:
                 x = x.to(self.kernel.dtype)
-            if training:
+            if self.training and self.drop_prob > 0.0:
                 x = torch.nn.functional.dropout(x, self.drop_prob, True)
             y = x @ self.kernel
             return y if self.bias is None else y + self.bias
-        step = None
-        if training:
-            self._step += 1                      # stream-ordered: a captured graph bumps it on every replay
-            step = self._step.clone()            # the value this forward (and its backward) uses
-        return _DropoutDenseFn.apply(x, self.kernel, self.bias, 1.0 - self.drop_prob if training else 1.0, self.seed, step)
+        if x.dtype == torch.bfloat16 and not _capi.has("h2gcn_dropout_dense_bf16"):
+            raise RuntimeError(f"{_capi.library_path()} predates the bf16 classifier (h2gcn_dropout_dense_bf16): rebuild it")
+        keep_prob, step = self._draw_step()
+        return _DropoutDenseFn.apply(x, self.kernel, self.bias, keep_prob, self.seed, step)
 
     def _forward_rows(self, x: torch.Tensor, sel: RowSelection) -> torch.Tensor:
         if not isinstance(sel, RowSelection):
             raise TypeError(f"rows must be a RowSelection (HopPlan.select_rows), got {type(sel).__name__}")
-        ok = (x.is_cuda and x.dim() == 2 and x.dtype in (torch.float32, torch.bfloat16) and self.kernel.shape[1] <= 64
-              and (x.shape[1] <= 1 or x.stride(1) == 1) and x.stride(0) >= x.shape[1]
-              and (x.dtype != torch.bfloat16 or (x.stride(0) % 2 == 0 and x.data_ptr() % 4 == 0)))
-        if not ok:   # no stock path here: it would draw another mask
+        if not _fused_classifier_covers(x, self.kernel.shape[1]):   # no stock path here: it would draw another mask
             raise ValueError("DropoutDense(x, rows=...) runs on the row-selected classifier kernels only: x must be a 2-D float32 or "
                              "bfloat16 CUDA tensor with unit column stride (bfloat16: even row stride) and units <= 64")
         if x.shape[0] != sel.n_rows_full or sel.rows.device != x.device:

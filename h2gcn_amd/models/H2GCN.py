@@ -782,6 +782,7 @@ class H2GCN(torch.nn.Module):
                 # rows of the same buffer, one exchange per round)
                 _, end, K, tags = self.fused
                 sharded_hops = hasattr(adjhops, "fused_propagation")
+                layout = L.concat_layout(inputs.shape[1], adjhops.n_hops, K)
                 propagate = adjhops.fused_propagation if sharded_hops else functools.partial(
                     L.fused_propagation, adjhops, private_grad=self._buffer_grad_is_private(end), **({"dtype": torch.bfloat16} if bf16 else {}))
                 if rows is not None:   # propagation + final classifier on the selected rows, one autograd node
@@ -791,9 +792,7 @@ class H2GCN(torch.nn.Module):
                 if self.reuse_propagation and inputs.is_cuda:
                     # (row-partitioned runs: every rank takes the same branch -- the decision depends only on the call
                     # sequence, which is the same on all ranks)
-                    H_ = adjhops.n_hops
-                    width = inputs.shape[1] * sum(H_ ** k for k in range(K + 1))
-                    buf = self._propagation_buffer(inputs.shape[0], width, inputs.device)
+                    buf = self._propagation_buffer(inputs.shape[0], layout.total, inputs.device)
                     plan_ = getattr(adjhops, "plan", adjhops)
                     # the parameters in front of the propagation enter through their autograd version counters (every in-place
                     # torch update bumps them; KerasAdam's raw-pointer kernel bumps them explicitly), so an ordinary torch
@@ -814,12 +813,8 @@ class H2GCN(torch.nn.Module):
                 if rows is not None:
                     return inputs          # the compact logits [m, units]: the classifier was the last layer
                 skip_until = end
-                w0 = tagged[tags[0]].shape[1]
-                H = adjhops.n_hops
-                pos = w0 * H ** K
                 for k in range(1, K):  # expose r_1 .. r_{K-1} under their tags as views of the buffer
-                    pos += w0 * H ** (k - 1)
-                    tagged[tags[k]] = inputs[:, pos:pos + w0 * H ** k]
+                    tagged[tags[k]] = layout.slot(inputs, k)
                 continue
             if ind < skip_until:
                 continue

@@ -26,6 +26,8 @@ from typing import Optional, Tuple
 import torch
 import torch.distributed as dist
 
+from .layers import _backward_walk, _check_out, concat_buffer, concat_layout
+
 
 def init_rccl_process_group(device: torch.device, timeout_s: Optional[float] = None) -> None:
     """``torch.distributed`` over RCCL with a HIGH-PRIORITY communication stream: the exchange kernels must be
@@ -811,38 +813,27 @@ class _ShardedFusedPropagation(torch.autograd.Function):
     def forward(ctx, r0, hops_obj, rounds, out=None, reuse=False):
         """``out`` / ``reuse``: as in :func:`h2gcn_amd.layers.fused_propagation` -- a caller-owned buffer to fill, or (``reuse``)
         one that already holds the propagation of this ``r0``: no exchange and no SpMM then, on any rank."""
-        plan = hops_obj.plan
-        n_local, w0 = r0.shape
-        H = plan.n_hops
-        widths = [w0 * H ** k for k in range(rounds + 1)]
-        off = [0] * (rounds + 1)
-        pos = widths[rounds]
-        for k in range(rounds):
-            off[k] = pos
-            pos += widths[k]
-        from .layers import concat_buffer
-        total = sum(widths)
-        if out is None:
-            buf = concat_buffer(n_local, total, r0.device)
-        else:
-            if out.shape != (n_local, total) or out.dtype != torch.float32 or out.device != r0.device or not out.is_contiguous():
-                raise ValueError(f"fused_propagation: out must be a contiguous float32 [{n_local}, {total}] tensor on {r0.device}")
-            buf = out.view(n_local, total)
+        ctx.hops_obj, ctx.layout = hops_obj, concat_layout(r0.shape[1], hops_obj.plan.n_hops, rounds)
+        return _ShardedFusedPropagation.propagate(ctx.layout, hops_obj, r0, out, reuse)
+
+    @staticmethod
+    def propagate(layout, hops_obj, r0, out, reuse):
+        """The forward itself (no autograd state): what :meth:`ShardedHops.fused_propagation` runs when no gradient is wanted."""
+        n_local = r0.shape[0]
+        _check_out(out, n_local, layout.total, torch.float32, r0.device)
+        buf = concat_buffer(n_local, layout.total, r0.device) if out is None else out.view(n_local, layout.total)
         if not reuse:
-            buf[:, off[0]:off[0] + w0].copy_(r0)
-            layers = [hops_obj.pipeline(widths[k - 1]) for k in range(1, rounds + 1)]
-            if _cross_round_ok(layers, widths, H):
-                _ShardedFusedPropagation._cross_round(buf, layers, widths, off, H)
+            layout.slot(buf, 0).copy_(r0)
+            layers = [hops_obj.pipeline(layout.widths[k - 1]) for k in range(1, layout.rounds + 1)]
+            if _cross_round_ok(layers, layout.widths, layout.n_hops):
+                _ShardedFusedPropagation._cross_round(buf, layers, layout)
             else:
-                for k in range(1, rounds + 1):
-                    src = buf[:, off[k - 1]:off[k - 1] + widths[k - 1]]
-                    dst = buf[:, off[k]:off[k] + widths[k]].unflatten(1, (H, widths[k - 1]))
-                    layers[k - 1](src, out=dst)
-        ctx.hops_obj, ctx.rounds, ctx.widths, ctx.off = hops_obj, rounds, widths, off
+                for k in range(1, layout.rounds + 1):
+                    layers[k - 1](layout.slot(buf, k - 1), out=layout.hop_view(buf, k))
         return buf
 
     @staticmethod
-    def _cross_round(buf, layers, widths, off, H):
+    def _cross_round(buf, layers, layout):
         """The rounds with the exchange of round k+1 started as soon as its columns exist: round k is launched per (feature
         chunk, hop) -- the hop matrices gather independently, so splitting the fused launch by hop costs only launch overhead
         -- and the moment the launch (c, h) is enqueued, the chunk of ``r_k`` it writes (= chunk ``h * C_k + c`` of round
@@ -851,35 +842,28 @@ class _ShardedFusedPropagation(torch.autograd.Function):
         hence the same bits as the round-by-round schedule."""
         rounds = len(layers)
         first = layers[0]
-        src0 = buf[:, off[0]:off[0] + widths[0]]
+        src0 = layout.slot(buf, 0)
         for c in range(first.C):
             first.start_chunk(c, src0[:, first.offsets[c]:first.offsets[c] + first.widths[c]])
         for k in range(1, rounds + 1):
             cur = layers[k - 1]
             nxt = layers[k] if k < rounds else None
-            dst = buf[:, off[k]:off[k] + widths[k]].unflatten(1, (H, widths[k - 1]))
+            dst = layout.hop_view(buf, k)
             for c in range(cur.C):
                 src = cur.wait_chunk(c)
                 cols = slice(cur.offsets[c], cur.offsets[c] + cur.widths[c])
                 if nxt is None:
                     cur._spmm(src, dst[:, :, cols], None)          # last round: nothing waits for it, keep the fused launch
                     continue
-                for h in range(H):
+                for h in range(layout.n_hops):
                     cur._spmm(src, dst[:, h:h + 1, cols], [h])
                     nxt.start_chunk(h * cur.C + c, dst[:, h, cols])
 
     @staticmethod
     def backward(ctx, grad):
-        hops_obj, K, widths, off = ctx.hops_obj, ctx.rounds, ctx.widths, ctx.off
-        plan = hops_obj.plan
-        H = plan.n_hops
-        g_k = grad[:, off[K]:off[K] + widths[K]]
-        for k in range(K, 0, -1):
-            layer = hops_obj.pipeline(widths[k - 1])
-            g_prev = _adjoint_reduce_scatter(layer, g_k.unflatten(1, (H, widths[k - 1])))
-            g_prev = g_prev + grad[:, off[k - 1]:off[k - 1] + widths[k - 1]]
-            g_k = g_prev
-        return g_k, None, None, None, None
+        hops_obj, layout = ctx.hops_obj, ctx.layout
+        d_r0 = _backward_walk(layout, grad, lambda k, g_k: _adjoint_reduce_scatter(hops_obj.pipeline(layout.widths[k - 1]), g_k))
+        return d_r0, None, None, None, None
 
 
 class ShardedHops:
@@ -1035,10 +1019,7 @@ class ShardedHops:
             raise ValueError("fused_propagation: reuse=True needs the buffer that holds the propagation (out=)")
         if r0_local.requires_grad and torch.is_grad_enabled():
             return _ShardedFusedPropagation.apply(r0_local, self, rounds, out, reuse)
-
-        class _Ctx:
-            pass
-        return _ShardedFusedPropagation.forward(_Ctx(), r0_local, self, rounds, out, reuse)
+        return _ShardedFusedPropagation.propagate(concat_layout(r0_local.shape[1], self.n_hops, rounds), self, r0_local, out, reuse)
 
 
 def slice_csr_rows(rowptr: torch.Tensor, colidx: torch.Tensor, vals: torch.Tensor, r0: int, r1: int):
