@@ -470,6 +470,57 @@ class HopPlan:
         _capi.check(st)
         return out
 
+    def _segment_tensors(self, name: str, tensors, sel) -> list:
+        """``tensors`` as a list of one contiguous float32 ``[nnz_k]`` tensor on the plan's device per selected hop."""
+        _require(not isinstance(tensors, torch.Tensor) and tensors is not None, f"{name} must be a sequence of {len(sel)} tensors (one per selected hop)")
+        tensors = list(tensors)
+        _require(len(tensors) == len(sel), f"{name} must list {len(sel)} tensors (one per selected hop), got {len(tensors)}")
+        for s, k in enumerate(sel):
+            t, nnz = tensors[s], self.colidx[k].numel()
+            _require(isinstance(t, torch.Tensor), f"{name}[{s}] must be a tensor, got {type(t).__name__}")
+            _require(t.dtype != torch.bfloat16, f"{name}[{s}] is bfloat16: the row softmax is fp32 only (pass .float())")
+            _require(t.dtype == torch.float32, f"{name}[{s}] must be float32 (the row softmax is fp32 only), got {t.dtype}")
+            _require(t.device == self.device, f"{name}[{s}] on {t.device}, plan on {self.device}")
+            _require(tuple(t.shape) == (nnz,), f"{name}[{s}] must have shape [{nnz}] (one value per stored entry of hop {k}), got {tuple(t.shape)}")
+            _require(t.is_contiguous(), f"{name}[{s}] must be contiguous")
+        return tensors
+
+    def _row_softmax_launch(self, symbol: str, hops, inputs: dict, out) -> list:
+        sel = list(range(self.n_hops)) if hops is None else sorted({int(h) for h in hops})
+        mask = self._mask(hops)
+        tables = [self._segment_tensors(name, ts, sel) for name, ts in inputs.items()]
+        if out is not None:
+            out = self._segment_tensors("out", out, sel)
+        if not _capi.has(symbol):
+            raise RuntimeError(f"{_capi.library_path()} predates the row softmax (h2gcn_row_softmax_hops_f32 / _backward_hops_f32): rebuild it")
+        if out is None:
+            out = [torch.empty(self.colidx[k].numel(), dtype=torch.float32, device=self.device) for k in sel]
+        arr_t = C.c_void_p * len(sel)
+        ptrs = [arr_t(*[t.data_ptr() if t.numel() else None for t in ts]) for ts in tables + [out]]
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            st = getattr(_capi.lib(), symbol)(self._handle, mask, *ptrs, C.c_void_p(stream))
+        _capi.check(st)
+        return out
+
+    def row_softmax(self, scores: Sequence[torch.Tensor], hops=None, out: Optional[Sequence[torch.Tensor]] = None) -> list:
+        """Softmax over every (row, hop) segment of the pattern: ``alpha[s][e] = exp(scores[s][e] - m) / S`` with ``m`` / ``S`` the
+        maximum / the sum of exponentials over the entries of ``e``'s row in selected hop ``s`` -> one contiguous float32
+        ``[nnz_k]`` tensor per selected hop, in the entry order of ``colidx[k]`` (``h2gcn_row_softmax_hops_f32``: one launch for
+        all selected hops, one softmax per hop and row -- not a joint one across hops).
+
+        ``scores``: a sequence of ``H_sel`` contiguous float32 CUDA tensors ``[nnz_k]``.  ``out``: the tensors to overwrite; it
+        may be the ``scores`` tensors themselves.  The bits are a function of each segment's own scores (``include/h2gcn_hip.h``);
+        non-finite scores behave as in ``torch.softmax`` on the segment."""
+        return self._row_softmax_launch("h2gcn_row_softmax_hops_f32", hops, {"scores": scores}, out)
+
+    def row_softmax_backward(self, alpha: Sequence[torch.Tensor], grad: Sequence[torch.Tensor], hops=None,
+                             out: Optional[Sequence[torch.Tensor]] = None) -> list:
+        """The backward of :meth:`row_softmax`: ``dscores[s][e] = alpha[s][e] * (grad[s][e] - D)`` with ``D`` the sum of
+        ``alpha * grad`` over the entries of ``e``'s row in hop ``s`` (``h2gcn_row_softmax_backward_hops_f32``, one launch).
+        ``alpha`` (the forward's result) and ``grad`` as ``scores`` above; ``out`` may be the ``grad`` tensors themselves."""
+        return self._row_softmax_launch("h2gcn_row_softmax_backward_hops_f32", hops, {"alpha": alpha, "grad": grad}, out)
+
     def __del__(self):
         h = getattr(self, "_handle", None)
         if h is not None and h.value:

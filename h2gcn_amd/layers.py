@@ -127,6 +127,52 @@ def hop_spmm(adjhops: HopPlan, inputs: torch.Tensor, hops: Optional[Iterable[int
     return adjhops.spmm(inputs, hops=sel)
 
 
+class _HopSoftmax(torch.autograd.Function):
+    """The row softmax over the hop pattern: forward -- ONE launch over the selected hops (``HopPlan.row_softmax``), ``alpha``
+    saved; backward -- ONE launch over the selected hops (``HopPlan.row_softmax_backward``) on the contiguous incoming gradients
+    (a hop nobody differentiated through enters as zeros), ``None`` for a hop whose scores do not require a gradient."""
+
+    @staticmethod
+    def forward(ctx, plan: HopPlan, hops, *scores):
+        alpha = plan.row_softmax(scores, hops=hops)
+        ctx.plan, ctx.hops = plan, hops
+        ctx.save_for_backward(*alpha)
+        return tuple(alpha)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        alpha = ctx.saved_tensors
+        if not any(ctx.needs_input_grad[2:]):
+            return (None, None) + (None,) * len(alpha)
+        grads = [torch.zeros_like(a) if g is None else g.contiguous() for g, a in zip(grads, alpha)]
+        dscores = ctx.plan.row_softmax_backward(alpha, grads, hops=ctx.hops)
+        return (None, None, *[d if need else None for d, need in zip(dscores, ctx.needs_input_grad[2:])])
+
+
+def hop_softmax(adjhops: HopPlan, scores, hops: Optional[Iterable[int]] = None) -> tuple:
+    """Attention coefficients over the hop pattern: per selected hop ``s`` and row ``i`` the softmax of ``scores[s]`` over the
+    stored entries of row ``i`` -- ``alpha[s][e] = exp(scores[s][e] - max) / sum`` -- as a tuple of ``H_sel`` float32 ``[nnz_k]``
+    tensors in the entry order of ``colidx[k]``, differentiable wrt ``scores`` (what ``hop_spmm(plan, x, values=list(alpha))``
+    takes).  One softmax per hop and row; there is no joint softmax across hops.
+
+    ``scores``: a sequence of ``H_sel`` contiguous float32 ``[nnz_k]`` tensors on the plan's device (bfloat16 scores are refused:
+    the kernels are fp32 only).  ``hops``: the hop indices the scores belong to, default all.  Forward and backward are one
+    launch each (:meth:`HopPlan.row_softmax` / :meth:`HopPlan.row_softmax_backward`); their bits are a function of each
+    segment's own contents.  Row-partitioned operands (``ShardedHops``) are not covered."""
+    if hasattr(adjhops, "aggregate"):
+        raise ValueError("hop_softmax is not supported on row-partitioned operands (ShardedHops): pass a single-GPU HopPlan")
+    if not isinstance(adjhops, HopPlan):
+        raise TypeError(f"adjhops must be a HopPlan, got {type(adjhops).__name__}")
+    sel = None if hops is None else tuple(sorted(set(int(h) for h in hops)))
+    if isinstance(scores, torch.Tensor) or scores is None:
+        raise ValueError(f"scores must be a sequence of {adjhops.n_selected(sel)} tensors (one per selected hop)")
+    scores = tuple(scores)
+    if any(isinstance(t, torch.Tensor) and t.requires_grad for t in scores) and torch.is_grad_enabled():
+        # (the argument checks of the launch run first either way: HopPlan.row_softmax refuses before any device work)
+        return _HopSoftmax.apply(adjhops, sel, *scores)
+    return tuple(adjhops.row_softmax(scores, hops=sel))
+
+
 class GCNLayer(torch.nn.Module):
     """``GCNLayer(hops=None)(adjhops, inputs) -> [N, H_sel, d]`` (reference ``_layers.py:54-81``).
 

@@ -410,6 +410,63 @@ int h2gcn_sddmm_hops_bf16(const h2gcn_plan_t* plan, uint32_t hop_mask, const uin
                           const uint16_t* X_dev, int64_t ldx, int32_t d, float* const* dvals_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Row softmax over the hop pattern and its backward (an additive extension of ABI 5: look the symbols up before calling a
+ * build that may predate it) -- what turns per-entry scores into the attention coefficients that h2gcn_plan_set_values /
+ * h2gcn_spmm_hops_* consume and h2gcn_sddmm_hops_* differentiates.  For every selected hop k (s = its rank among the selected
+ * hops) and every row i the SEGMENT is the entries e of [rowptr_k[i], rowptr_k[i+1]), j = 0 .. n-1 in stored order:
+ *
+ *     forward    alpha[s][e]   = exp(scores[s][e] - m) / S          m = max_j score_j,  S = sum_j exp(score_j - m)
+ *     backward   dscores[s][e] = alpha[s][e] * (dalpha[s][e] - D)   D = sum_j alpha_j * dalpha_j
+ *
+ * fp32 only; one softmax per (row, hop) segment (no joint softmax across hops).
+ *
+ *   scores_dev / alpha_dev / dalpha_dev / dscores_dev   HOST arrays of H_sel device pointers; entry s holds nnz_k floats in the
+ *              entry order of colidx_dev[k].  Outputs are OVERWRITTEN.  An entry may be NULL only when its hop has no nonzeros.
+ *   Aliasing:  alpha_dev[s] == scores_dev[s] and dscores_dev[s] == dalpha_dev[s] are allowed (a lane writes only entries it has
+ *              read, after every read of the segment's sums); any other overlap between an output and any input or other
+ *              output is undefined.
+ *
+ * Only the plan's forward rowptr arrays are read -- neither columns, values nor transposes -- so the calls work on plans
+ * created without H2GCN_PLAN_BUILD_TRANSPOSE, on shard plans and on row-selected sub-plans.  Empty segments write nothing.
+ * All offsets are 64-bit.  No atomics: two launches give the same bits.
+ *
+ * Arithmetic: ONE order per segment, a function of the segment's own contents (its n values in order) and of nothing else.
+ *   t_j = score_j - m                           one fp32 subtraction
+ *   e_j = exp2(t_j * 0x1.715476p+0f)            one fp32 multiplication by log2(e) rounded to fp32, then the hardware 2^x
+ *                                               (v_exp_f32, 1 ulp) -- the ONE device exponential of every path
+ *   256 partials P[l], l = j mod 256, each starting at +0 and accumulated sequentially in ascending j:
+ *       forward   P[l] = P[l] + e_j             backward   P[l] = fma(alpha_j, dalpha_j, P[l])
+ *   W_w, w = 0..3: the xor butterfly over lane distances 1, 2, 4, 8, 16, 32 of P[64w .. 64w+63]
+ *       (v1[l] = P[l] + P[l^1], v2[l] = v1[l] + v1[l^2], ... W_w = v32[l] + v32[l^32])
+ *   segment total S (forward) or D (backward) = (W_0 + W_1) + (W_2 + W_3)
+ *   alpha_j  = e_j * (1 / S)                    1 / S ONE correctly rounded fp32 division per segment, then one multiplication
+ *   dscore_j = alpha_j * (dalpha_j - D)         one subtraction, one multiplication
+ * A partial that received no entry is +0 and adding +0 changes no bit here (every e_j >= +0; an fma onto +0 never gives -0), so
+ * the bits never depend on which mapping served the segment (16-lane group, one wave in registers, one wave in passes, 4-wave
+ * workgroup), on long_row_threshold, rows_per_wave, variant, slice_cols, the hop selection, the row the segment sits in or the
+ * alignment of its first entry.
+ * Error bounds (u = 2^-24, T = max_j |score_j - m|, every e_j a normal number):
+ *   |alpha_j - exact| <= (6T + n + 6) * u * exact   and   |dscore_j - exact(alpha, dalpha)| <= alpha_j * gamma_{n+2} *
+ *   (|dalpha_j| + sum_i |alpha_i dalpha_i|) + 2^-149,  gamma_k = k*u / (1 - k*u).
+ * Non-finite scores follow softmax on the segment as IEEE arithmetic gives it: a segment that contains a NaN or a +inf is NaN
+ * throughout (the maximum carries NaN explicitly: v_max_f32 would drop it), a segment made only of -inf is NaN throughout, and
+ * -inf next to finite scores gives exactly +0.  Other segments are not affected.
+ *
+ * hipGraph capture: the condition of the forward launch of the same hop selection, as for h2gcn_sddmm_hops_*: segments with
+ * >= long_row_threshold entries are served from the plan's forward long-segment list of the selection, built by the FIRST
+ * launch of that selection (of any of these kernels; the all-hops list at plan creation).  A launch that would have to build
+ * it while its stream is being captured returns H2GCN_ERR_INVALID_ARGUMENT with the same advice (run the launch once eagerly).
+ *
+ * Validation, all before the device is touched, each H2GCN_ERR_INVALID_ARGUMENT with a message naming the argument: a NULL
+ * plan ("plan is NULL"), a hop mask outside the plan, a NULL table when the selection has nonzeros, a NULL entry of a selected
+ * hop that has nonzeros.
+ */
+int h2gcn_row_softmax_hops_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* const* scores_dev,
+                               float* const* alpha_dev, void* stream);
+int h2gcn_row_softmax_backward_hops_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* const* alpha_dev,
+                                        const float* const* dalpha_dev, float* const* dscores_dev, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Operand construction on the device: exact-k-hop neighbourhood rings and their normalisation -- the step that
  * FEEDS the aggregation.  Stands in for TransformSPAdj.nhoodSplit (reference h2gcn/datasets/_dataset.py:138-158:
  * `mt <- bin(mt @ (A + I))`, ring_k = mt_k - mt_{k-1}, a host SpGEMM in scipy) and TransformSPAdj.normalize
