@@ -25,11 +25,11 @@ constexpr unsigned kMirrorRange = 4u;         // a column id outside [0, n)
 hipError_t mirror_pass(int64_t n, int64_t nnz, const int64_t* rowptr, const int32_t* colidx, const float* vals,
                        uint32_t* partner, float* t_vals, MirrorStatus* status, hipStream_t stream);
 
-// What the SDDMM launch (sddmm.hip) needs of a plan: the forward arrays of the selected hops, packed in ascending hop order, and
-// the tunables that map rows to waves.  sddmm_plan_view touches no device; sddmm_long_list returns the forward long-segment list
-// of the selection (row << 4 | s per entry), building and caching it on the selection's first launch exactly as the forward
-// launch does -- including the refusal to build it while `stream` is being captured.
-struct SddmmPlanView {
+// What the pattern kernels (pattern_walk.hip.h: sddmm.hip, row_softmax.hip) need of a plan: the forward arrays of the selected
+// hops, packed in ascending hop order, and the tunables that map rows to waves.  pattern_view touches no device; pattern_long_list
+// returns the forward long-segment list of the selection (row << 4 | s per entry), building and caching it on the selection's first
+// launch exactly as the forward launch does -- including the refusal to build it while `stream` is being captured.
+struct PatternView {
     int n_sel;
     int64_t n_rows, n_cols;
     const int64_t* rowptr[H2GCN_MAX_HOPS];
@@ -39,8 +39,8 @@ struct SddmmPlanView {
     int rows_per_wave;
     uint32_t mask;
 };
-int sddmm_plan_view(const h2gcn_plan* plan, uint32_t hop_mask, SddmmPlanView* out);
-int sddmm_long_list(const h2gcn_plan* plan, uint32_t mask, hipStream_t stream, const int64_t** list_dev, int* n_long);
+int pattern_view(const h2gcn_plan* plan, uint32_t hop_mask, PatternView* out);
+int pattern_long_list(const h2gcn_plan* plan, uint32_t mask, hipStream_t stream, const int64_t** list_dev, int* n_long);
 
 }  // namespace h2gcn
 

@@ -1215,10 +1215,10 @@ int spmm_hops(bool adjoint, const h2gcn_plan_t* plan, uint32_t hop_mask, Dense s
 }
 }  // namespace
 
-// The plan as the SDDMM launch of sddmm.hip sees it (capi_internal.h; C++ linkage: called across translation units).
+// The plan as the pattern kernels see it (capi_internal.h; C++ linkage: called across translation units).
 extern "C++" {
 namespace h2gcn {
-int sddmm_plan_view(const h2gcn_plan* plan, uint32_t hop_mask, SddmmPlanView* out) {
+int pattern_view(const h2gcn_plan* plan, uint32_t hop_mask, PatternView* out) {
     if (!plan) return fail(H2GCN_ERR_INVALID_ARGUMENT, "plan is NULL");
     memset(out, 0, sizeof(*out));
     const int st = resolve_mask(plan, hop_mask, &out->mask);
@@ -1240,7 +1240,7 @@ int sddmm_plan_view(const h2gcn_plan* plan, uint32_t hop_mask, SddmmPlanView* ou
     return H2GCN_OK;
 }
 
-int sddmm_long_list(const h2gcn_plan* plan, uint32_t mask, hipStream_t stream, const int64_t** list_dev, int* n_long) {
+int pattern_long_list(const h2gcn_plan* plan, uint32_t mask, hipStream_t stream, const int64_t** list_dev, int* n_long) {
     const int st = check_device(plan);
     if (st != H2GCN_OK) return st;
     CaptureScope capture_scope(stream);

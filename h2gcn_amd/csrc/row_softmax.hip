@@ -8,8 +8,7 @@
 // kernel is compiled differently because of it.
 //
 // Mapping (gfx950, wave64; a streaming kernel: no atomics, no scratch, a few bytes of LDS on the long path only):
-//   * the block -> row-tile map of sddmm.hip (every XCD gets a contiguous row range); a wave owns rows_per_wave consecutive rows
-//     and takes its row pointers from one wave-wide load;
+//   * the pattern walk of pattern_walk.hip.h: a wave owns rows_per_wave consecutive rows;
 //   * per hop the wave walks its rows FOUR at a time (a step), lane group gi (16 lanes) standing for row i0 + gi:
 //       - all four segments <= 16 entries: one 16-lane group per segment, one load and one store instruction for the four
 //         (consecutive rows of one hop are consecutive in memory, so the load is contiguous up to the masked lanes);
@@ -33,57 +32,27 @@
 #include <cmath>
 #include <cstring>
 
-#include "h2gcn_hip.h"
-#include "capi_internal.h"
+#include "pattern_walk.hip.h"
 
 namespace h2gcn {
 namespace row_softmax {
 
-constexpr int kWave = 64;
-constexpr int kWavesPerBlock = 4;
-constexpr int kBlock = kWave * kWavesPerBlock;
-constexpr int kNumXcd = 8;
+using namespace pattern;
 constexpr int kGroup = 16;       // lanes of a lane group: the longest segment it serves
 constexpr int kPartials = 256;   // partial sums of a segment: entry j belongs to P[j mod 256]
 
 struct Params {
-    const int64_t* rowptr[H2GCN_MAX_HOPS];   // the selected hops, packed
-    const float* a[H2GCN_MAX_HOPS];          // forward: scores; backward: alpha
+    Geom geom;
+    const float* a[H2GCN_MAX_HOPS];          // forward: scores; backward: alpha   (the selected hops, packed as geom.rowptr)
     const float* g[H2GCN_MAX_HOPS];          // backward: dalpha
     float* out[H2GCN_MAX_HOPS];              // forward: alpha; backward: dscores
-    int n_sel;
-    int64_t n_rows;
-    const int64_t* long_list;   // row << 4 | s per long segment
-    int n_long;
-    int long_threshold;
-    int rows_per_wave;
-    int64_t n_tiles, tiles_per_xcd;
 };
 
-struct Add {
-    static __device__ __forceinline__ float op(float a, float b) { return a + b; }
-};
 struct Max {   // (drops NaN like v_max_f32: the callers carry NaN in a flag of their own)
     static __device__ __forceinline__ float op(float a, float b) { return fmaxf(a, b); }
 };
 
-template <int CTRL>
-__device__ __forceinline__ float dpp(float v) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false));
-}
-
-// xor butterfly over lane distances 1, 2, 4, 8 of a 16-lane group: afterwards its 16 lanes hold the same bits (the partner of
-// the distance-4 / distance-8 step is reached with row_half_mirror / row_ror:8, whose source lanes hold the partner's value).
-// All 64 lanes must be active.
-template <typename Op>
-__device__ __forceinline__ float bfly16(float v) {
-    v = Op::op(v, dpp<0xB1>(v));    // quad_perm [1,0,3,2]: lane ^ 1
-    v = Op::op(v, dpp<0x4E>(v));    // quad_perm [2,3,0,1]: lane ^ 2
-    v = Op::op(v, dpp<0x141>(v));   // row_half_mirror: lane ^ 4 up to a permutation of equals
-    v = Op::op(v, dpp<0x128>(v));   // row_ror:8: lane ^ 8
-    return v;
-}
-// ... and on over distances 16 and 32: the 64 lanes of the wave
+// the 16-lane xor butterfly, and on over distances 16 and 32: the 64 lanes of the wave
 template <typename Op>
 __device__ __forceinline__ float bfly64(float v) {
     v = bfly16<Op>(v);
@@ -97,17 +66,6 @@ __device__ __forceinline__ float exp_t(float t) { return __builtin_amdgcn_exp2f(
 
 __device__ __forceinline__ float quiet_nan() { return __int_as_float(0x7fc00000); }
 __device__ __forceinline__ float neg_inf() { return __int_as_float((int)0xff800000u); }
-
-__device__ __forceinline__ int64_t readlane64(int64_t v, int src) {
-    const uint32_t lo = __builtin_amdgcn_readlane((int)(uint32_t)v, src);
-    const uint32_t hi = __builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), src);
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-__device__ __forceinline__ int64_t bpermute64(int64_t v, int src) {
-    const uint32_t lo = __builtin_amdgcn_ds_bpermute(src << 2, (int)(uint32_t)v);
-    const uint32_t hi = __builtin_amdgcn_ds_bpermute(src << 2, (int)(uint32_t)((uint64_t)v >> 32));
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
 
 // ---- a segment of at most 16 entries on the lane's own 16-lane group: x / y are entry q = lane & 15 (padding where !ok)
 template <bool BWD>
@@ -290,12 +248,12 @@ struct Step {
 
 template <bool BWD>
 __device__ __forceinline__ void step_begin(const Params& p, int t, int quads, int64_t row0, int64_t rp, int lane, Step& st) {
-    const int rpw = p.rows_per_wave;
+    const int rpw = p.geom.rows_per_wave;
     const int s = t / quads, i = 4 * (t - s * quads) + (lane >> 4);
-    const int src = s * (rpw + 1) + (i < rpw ? i : rpw - 1);
+    const int src = rp_lane(p.geom, s, i < rpw ? i : rpw - 1);
     const int64_t beg = bpermute64(rp, src);
     int64_t n = bpermute64(rp, src + 1) - beg;
-    if (i >= rpw || row0 + i >= p.n_rows || n >= p.long_threshold) n = 0;   // (long segments: workgroups of their own)
+    if (i >= rpw || row0 + i >= p.geom.n_rows || n >= p.geom.long_threshold) n = 0;   // (long segments: workgroups of their own)
     st.s = s;
     st.beg = beg;
     st.n = (int)(n < 0x7fffffff ? n : 0x7fffffff);
@@ -375,31 +333,18 @@ __global__ __launch_bounds__(kBlock) void row_softmax_hops_kernel(const Params p
     __shared__ float lds[8];   // long segments: wave maxima [0..3], wave totals [4..7]
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    if ((int)blockIdx.x < p.n_long) {
+    int64_t row, beg, end;
+    int s;
+    if (long_segment(p.geom, blockIdx.x, &row, &s, &beg, &end)) {
         // ---- a long segment: 64-entry chunks over the 4 waves ----
-        const int64_t e = p.long_list[blockIdx.x];
-        const int64_t row = e >> 4;
-        const int s = (int)(e & 15);
-        const int64_t beg = p.rowptr[s][row], end = p.rowptr[s][row + 1];
         if (end <= beg) return;   // (the same for the whole block)
         loop_segment<BWD, kWavesPerBlock>(p.a[s] + beg, BWD ? p.g[s] + beg : nullptr, p.out[s] + beg, end - beg, lane, wave, lds);
         return;
     }
-    // ---- regular path: XCD-aware tile map, each wave walks rows_per_wave consecutive rows ----
-    const int64_t tb = (int64_t)blockIdx.x - p.n_long;
-    const int64_t tile = (tb % kNumXcd) * p.tiles_per_xcd + tb / kNumXcd;
-    if (tile >= p.n_tiles) return;
-    const int rpw = p.rows_per_wave;
-    const int64_t row0 = (tile * kWavesPerBlock + wave) * rpw;
-    if (row0 >= p.n_rows) return;
-    // the wave's row pointers: lane s * (rpw + 1) + i holds rowptr_s[row0 + i]  ((rpw + 1) * n_sel <= 64: plan invariant)
-    int64_t rp = 0;
-    if (lane < (rpw + 1) * p.n_sel) {
-        const int s = lane / (rpw + 1), i = lane - s * (rpw + 1);
-        const int64_t r = row0 + i < p.n_rows ? row0 + i : p.n_rows;
-        rp = p.rowptr[s][r];
-    }
-    const int quads = (rpw + 3) >> 2, n_steps = p.n_sel * quads;
+    // ---- the tile walk: each wave walks rows_per_wave consecutive rows, four at a time ----
+    int64_t row0, rp;
+    if (!wave_rows(p.geom, blockIdx.x, wave, lane, &row0, &rp)) return;
+    const int quads = (p.geom.rows_per_wave + 3) >> 2, n_steps = p.geom.n_sel * quads;
     Step cur;
     step_begin<BWD>(p, 0, quads, row0, rp, lane, cur);
     for (int t = 0; t < n_steps; ++t) {
@@ -416,43 +361,23 @@ int launch(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* const* a, c
            const char* g_name, float* const* out, const char* out_name, void* stream_v) {
     try {
         // every check below comes before the device is touched
-        SddmmPlanView v;
-        int st = sddmm_plan_view(plan, hop_mask, &v);
+        PatternView v;
+        int st = pattern_view(plan, hop_mask, &v);
         if (st != H2GCN_OK) return st;
-        int64_t nnz_sel = 0;
-        for (int s = 0; s < v.n_sel; ++s) nnz_sel += v.nnz[s];
-        if (nnz_sel > 0) {
-            if (!a) return fail(H2GCN_ERR_INVALID_ARGUMENT, "%s is NULL", a_name);
-            if (BWD && !g) return fail(H2GCN_ERR_INVALID_ARGUMENT, "%s is NULL", g_name);
-            if (!out) return fail(H2GCN_ERR_INVALID_ARGUMENT, "%s is NULL", out_name);
-            for (int s = 0; s < v.n_sel; ++s) {
-                if (v.nnz[s] <= 0) continue;
-                const char* which = !a[s] ? a_name : (BWD && !g[s]) ? g_name : !out[s] ? out_name : nullptr;
-                if (which)
-                    return fail(H2GCN_ERR_INVALID_ARGUMENT, "%s[%d] is NULL (selected hop %d of the launch has %lld nonzeros)", which, s, s,
-                                (long long)v.nnz[s]);
-            }
-        }
-        if (nnz_sel == 0 || v.n_rows == 0) return H2GCN_OK;
+        if ((st = check_hop_arrays(v, a_name, a)) != H2GCN_OK) return st;
+        if (BWD && (st = check_hop_arrays(v, g_name, g)) != H2GCN_OK) return st;
+        if ((st = check_hop_arrays(v, out_name, out)) != H2GCN_OK) return st;
         hipStream_t stream = (hipStream_t)stream_v;
         Params p;
         memset(&p, 0, sizeof(p));
-        if ((st = sddmm_long_list(plan, v.mask, stream, &p.long_list, &p.n_long)) != H2GCN_OK) return st;
+        int64_t n_blocks;
+        if ((st = launch_geometry(plan, v, stream, &p.geom, &n_blocks)) != H2GCN_OK) return st;
+        if (n_blocks == 0) return H2GCN_OK;
         for (int s = 0; s < v.n_sel; ++s) {
-            p.rowptr[s] = v.rowptr[s];
             p.a[s] = a[s];
             p.g[s] = BWD ? g[s] : nullptr;
             p.out[s] = out[s];
         }
-        p.n_sel = v.n_sel;
-        p.n_rows = v.n_rows;
-        p.long_threshold = v.long_threshold;
-        p.rows_per_wave = v.rows_per_wave;
-        const int64_t rows_per_tile = (int64_t)p.rows_per_wave * kWavesPerBlock;
-        p.n_tiles = (p.n_rows + rows_per_tile - 1) / rows_per_tile;
-        p.tiles_per_xcd = (p.n_tiles + kNumXcd - 1) / kNumXcd;
-        const int64_t n_blocks = (int64_t)p.n_long + p.tiles_per_xcd * kNumXcd;
-        if (n_blocks > 0x7fffffffLL) return fail(H2GCN_ERR_INVALID_ARGUMENT, "grid too large (%lld blocks)", (long long)n_blocks);
         hipLaunchKernelGGL((row_softmax_hops_kernel<BWD>), dim3((unsigned)n_blocks), dim3(kBlock), 0, stream, p);
         H2GCN_HIP_TRY(hipGetLastError());
         return H2GCN_OK;

@@ -10,9 +10,8 @@
 // Mapping (gfx950, wave64; gather-bound like the forward launch, no MFMA, no LDS memory, no atomics):
 //   * ONE lane geometry: 16 lanes x 4 columns cover a 64-column block of a feature row, so the 4 lane groups of a wave
 //     gather 4 neighbour rows of X per load instruction (16 bytes per lane fp32, 8 bytes bf16);
-//   * a wave walks the (row, hop) segments of its row tile (the forward's block -> row-tile map: every XCD gets a contiguous
-//     row range; the wave's row pointers come from one wave-wide load).  Per segment it keeps the dY row in registers -- lane
-//     (group, quad q) holds columns 4q..4q+3 of up to four 64-column blocks, replicated over the groups;
+//   * a wave walks the (row, hop) segments of its row tile (the pattern walk of pattern_walk.hip.h).  Per segment it keeps the
+//     dY row in registers -- lane (group, quad q) holds columns 4q..4q+3 of up to four 64-column blocks, replicated over the groups;
 //   * column ids are fetched 64 at a time -- lane (group gi, quad q) loads entry 4q + gi of the chunk, so the 64 lanes read
 //     the chunk's 256 bytes once -- and handed to the group's lanes with ds_bpermute; in round r group gi serves entry
 //     4r + gi: a chunk of n entries takes ceil(n / 4) rounds, whatever n;
@@ -21,8 +20,8 @@
 //   * the 16 quads of a block are summed by an xor butterfly in DPP (one row of 16 lanes), the lane with q == r keeps the
 //     entry's result, and after the last round the 64 results of the chunk leave with ONE store instruction into the chunk's
 //     256 bytes of dV;
-//   * segments with >= long_row_threshold nonzeros belong to workgroups of their own (the plan's forward long-segment list):
-//     the 4 waves take 64-entry chunks in turn.  Every result belongs to one entry, so nothing is summed across waves.
+//   * segments with >= long_row_threshold nonzeros belong to workgroups of their own: the 4 waves take 64-entry chunks in turn.
+//     Every result belongs to one entry, so nothing is summed across waves.
 //
 // Arithmetic (documented in include/h2gcn_hip.h): one order per element, a function of d alone -- see dot_block / walk_chunk.
 #include <hip/hip_runtime.h>
@@ -32,16 +31,12 @@
 #include <cstring>
 #include <type_traits>
 
-#include "h2gcn_hip.h"
-#include "capi_internal.h"
+#include "pattern_walk.hip.h"
 
 namespace h2gcn {
 namespace sddmm {
 
-constexpr int kWave = 64;
-constexpr int kWavesPerBlock = 4;
-constexpr int kBlock = kWave * kWavesPerBlock;
-constexpr int kNumXcd = 8;
+using namespace pattern;
 constexpr int kBlockCols = 64;   // columns one lane group covers per load: 16 lanes x 4
 constexpr int kMaxBlocks = 4;    // 64-column blocks of the dY row a lane keeps in registers (one column pass: 256 columns)
 
@@ -50,21 +45,14 @@ struct bf16 {
 };
 
 struct Params {
-    const int64_t* rowptr[H2GCN_MAX_HOPS];   // the selected hops, packed
-    const int32_t* colidx[H2GCN_MAX_HOPS];
+    Geom geom;
+    const int32_t* colidx[H2GCN_MAX_HOPS];   // the selected hops, packed as geom.rowptr
     float* dvals[H2GCN_MAX_HOPS];
-    int n_sel;
     int d;
-    int64_t n_rows;
     const void* g;   // dY, [n_rows, n_sel, d] through ldg_row / ldg_hop (elements)
     int64_t ldg_row, ldg_hop;
     const void* x;   // X, [n_cols, d] through ldx
     int64_t ldx;
-    const int64_t* long_list;   // row << 4 | s per long segment
-    int n_long;
-    int long_threshold;
-    int rows_per_wave;
-    int64_t n_tiles, tiles_per_xcd;
 };
 
 typedef float float4u __attribute__((ext_vector_type(4), aligned(4)));     // 16-byte loads need only dword alignment on gfx950
@@ -101,25 +89,14 @@ __device__ __forceinline__ Quad load_quad(const bf16* row, int c0, int d) {
     return r;
 }
 
-template <int CTRL>
-__device__ __forceinline__ float dpp_add(float v) {
-    const int o = __builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xf, 0xf, false);
-    return v + __int_as_float(o);
-}
-
 // The total of one 64-column block: the quad's value t = g0*x0, then fma(g1, x1, t), fma(g2, x2, t), fma(g3, x3, t), and the 16
-// quads summed by the xor butterfly over lane distances 1, 2, 4, 8 (afterwards all 16 lanes hold the same bits; the partner of
-// the distance-4 / distance-8 step is reached with row_half_mirror / row_ror:8, whose source lanes hold the partner's value).
+// quads summed by the xor butterfly over lane distances 1, 2, 4, 8 (afterwards all 16 lanes hold the same bits).
 __device__ __forceinline__ float dot_block(const Quad& g, const Quad& x) {
     float t = g.v[0] * x.v[0];
     t = __builtin_fmaf(g.v[1], x.v[1], t);
     t = __builtin_fmaf(g.v[2], x.v[2], t);
     t = __builtin_fmaf(g.v[3], x.v[3], t);
-    t = dpp_add<0xB1>(t);    // quad_perm [1,0,3,2]: lane ^ 1
-    t = dpp_add<0x4E>(t);    // quad_perm [2,3,0,1]: lane ^ 2
-    t = dpp_add<0x141>(t);   // row_half_mirror: the neighbouring group of four lanes (lane ^ 4 up to a permutation of equals)
-    t = dpp_add<0x128>(t);   // row_ror:8: lane ^ 8
-    return t;
+    return bfly16<Add>(t);
 }
 
 // One batch of U rounds of a chunk: group gi serves entry 4r + gi in round r.  FULL: every round of the batch exists.
@@ -171,12 +148,6 @@ __device__ __forceinline__ void walk_chunk(const Params& p, const TS* grow, cons
     if (my_n < count) out[my_n] = res;
 }
 
-__device__ __forceinline__ int64_t readlane64(int64_t v, int src) {
-    const uint32_t lo = __builtin_amdgcn_readlane((int)(uint32_t)v, src);
-    const uint32_t hi = __builtin_amdgcn_readlane((int)(uint32_t)((uint64_t)v >> 32), src);
-    return (int64_t)(((uint64_t)hi << 32) | lo);
-}
-
 template <typename TS, int NB>
 __global__ __launch_bounds__(kBlock) void sddmm_hops_kernel(const Params p) {
     // rounds per batch: 8 load instructions in flight (fp32: 8 KiB per wave), 16 for bf16 (8 KiB again), at most 8 rounds
@@ -185,12 +156,10 @@ __global__ __launch_bounds__(kBlock) void sddmm_hops_kernel(const Params p) {
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const TS* g = reinterpret_cast<const TS*>(p.g);
-    if ((int)blockIdx.x < p.n_long) {
+    int64_t row, beg, end;
+    int s;
+    if (long_segment(p.geom, blockIdx.x, &row, &s, &beg, &end)) {
         // ---- a long segment: 64-entry chunks over the 4 waves ----
-        const int64_t e = p.long_list[blockIdx.x];
-        const int64_t row = e >> 4;
-        const int s = (int)(e & 15);
-        const int64_t beg = p.rowptr[s][row], end = p.rowptr[s][row + 1];
         const TS* grow = g + row * p.ldg_row + (int64_t)s * p.ldg_hop;
         for (int64_t c = beg + (int64_t)wave * kWave; c < end; c += kBlock) {
             const int count = (int)(end - c < kWave ? end - c : kWave);
@@ -198,25 +167,14 @@ __global__ __launch_bounds__(kBlock) void sddmm_hops_kernel(const Params p) {
         }
         return;
     }
-    // ---- regular path: XCD-aware tile map, each wave walks rows_per_wave consecutive rows ----
-    const int64_t tb = (int64_t)blockIdx.x - p.n_long;
-    const int64_t tile = (tb % kNumXcd) * p.tiles_per_xcd + tb / kNumXcd;
-    if (tile >= p.n_tiles) return;
-    const int rpw = p.rows_per_wave;
-    const int64_t row0 = (tile * kWavesPerBlock + wave) * rpw;
-    if (row0 >= p.n_rows) return;
-    // the wave's row pointers: lane s * (rpw + 1) + i holds rowptr_s[row0 + i]  ((rpw + 1) * n_sel <= 64: plan invariant)
-    int64_t rp = 0;
-    if (lane < (rpw + 1) * p.n_sel) {
-        const int s = lane / (rpw + 1), i = lane - s * (rpw + 1);
-        const int64_t r = row0 + i < p.n_rows ? row0 + i : p.n_rows;
-        rp = p.rowptr[s][r];
-    }
-    for (int i = 0; i < rpw && row0 + i < p.n_rows; ++i) {
-        for (int s = 0; s < p.n_sel; ++s) {
-            const int64_t beg = readlane64(rp, s * (rpw + 1) + i), end = readlane64(rp, s * (rpw + 1) + i + 1);
+    // ---- the tile walk: each wave walks rows_per_wave consecutive rows ----
+    int64_t row0, rp;
+    if (!wave_rows(p.geom, blockIdx.x, wave, lane, &row0, &rp)) return;
+    for (int i = 0; i < p.geom.rows_per_wave && row0 + i < p.geom.n_rows; ++i) {
+        for (s = 0; s < p.geom.n_sel; ++s) {
+            segment(p.geom, rp, s, i, &beg, &end);
             const int64_t len = end - beg;
-            if (len <= 0 || len >= p.long_threshold) continue;
+            if (len <= 0 || len >= p.geom.long_threshold) continue;
             const TS* grow = g + (row0 + i) * p.ldg_row + (int64_t)s * p.ldg_hop;
             for (int64_t c = beg; c < end; c += kWave) {
                 const int count = (int)(end - c < kWave ? end - c : kWave);
@@ -243,8 +201,8 @@ int sddmm_hops(const h2gcn_plan_t* plan, uint32_t hop_mask, const void* dY, int6
     constexpr bool kBf16 = std::is_same<TS, bf16>::value;
     try {
         // every check below comes before the device is touched
-        SddmmPlanView v;
-        int st = sddmm_plan_view(plan, hop_mask, &v);
+        PatternView v;
+        int st = pattern_view(plan, hop_mask, &v);
         if (st != H2GCN_OK) return st;
         if (d < 1) return fail(H2GCN_ERR_INVALID_ARGUMENT, "d = %d", d);
         if (ldx < d) return fail(H2GCN_ERR_INVALID_ARGUMENT, "ldx = %lld < d = %d", (long long)ldx, d);
@@ -255,42 +213,25 @@ int sddmm_hops(const h2gcn_plan_t* plan, uint32_t hop_mask, const void* dY, int6
             if ((st = check_bf16_layout("dY", dY, ldg_row, ldg_hop, d)) != H2GCN_OK) return st;
             if ((st = check_bf16_layout("X", X, ldx, 0, d)) != H2GCN_OK) return st;
         }
-        int64_t nnz_sel = 0;
-        for (int s = 0; s < v.n_sel; ++s) nnz_sel += v.nnz[s];
-        if (nnz_sel > 0) {
-            if (!dY) return fail(H2GCN_ERR_INVALID_ARGUMENT, "dY is NULL");
-            if (!X) return fail(H2GCN_ERR_INVALID_ARGUMENT, "X is NULL");
-            if (!dvals) return fail(H2GCN_ERR_INVALID_ARGUMENT, "dvals is NULL");
-            for (int s = 0; s < v.n_sel; ++s)
-                if (v.nnz[s] > 0 && !dvals[s])
-                    return fail(H2GCN_ERR_INVALID_ARGUMENT, "dvals[%d] is NULL (selected hop %d of the launch has %lld nonzeros)", s, s,
-                                (long long)v.nnz[s]);
-        }
-        if (nnz_sel == 0 || v.n_rows == 0) return H2GCN_OK;
+        if (selected_nnz(v) > 0 && !dY) return fail(H2GCN_ERR_INVALID_ARGUMENT, "dY is NULL");
+        if (selected_nnz(v) > 0 && !X) return fail(H2GCN_ERR_INVALID_ARGUMENT, "X is NULL");
+        if ((st = check_hop_arrays(v, "dvals", dvals)) != H2GCN_OK) return st;
         hipStream_t stream = (hipStream_t)stream_v;
         Params p;
         memset(&p, 0, sizeof(p));
-        if ((st = sddmm_long_list(plan, v.mask, stream, &p.long_list, &p.n_long)) != H2GCN_OK) return st;
+        int64_t n_blocks;
+        if ((st = launch_geometry(plan, v, stream, &p.geom, &n_blocks)) != H2GCN_OK) return st;
+        if (n_blocks == 0) return H2GCN_OK;
         for (int s = 0; s < v.n_sel; ++s) {
-            p.rowptr[s] = v.rowptr[s];
             p.colidx[s] = v.colidx[s];
             p.dvals[s] = dvals[s];
         }
-        p.n_sel = v.n_sel;
         p.d = d;
-        p.n_rows = v.n_rows;
         p.g = dY;
         p.ldg_row = ldg_row;
         p.ldg_hop = ldg_hop;
         p.x = X;
         p.ldx = ldx;
-        p.long_threshold = v.long_threshold;
-        p.rows_per_wave = v.rows_per_wave;
-        const int64_t rows_per_tile = (int64_t)p.rows_per_wave * kWavesPerBlock;
-        p.n_tiles = (p.n_rows + rows_per_tile - 1) / rows_per_tile;
-        p.tiles_per_xcd = (p.n_tiles + kNumXcd - 1) / kNumXcd;
-        const int64_t n_blocks = (int64_t)p.n_long + p.tiles_per_xcd * kNumXcd;
-        if (n_blocks > 0x7fffffffLL) return fail(H2GCN_ERR_INVALID_ARGUMENT, "grid too large (%lld blocks)", (long long)n_blocks);
         const dim3 grid((unsigned)n_blocks), block(kBlock);
         // blocks of the dY row a lane keeps: the narrowest geometry that covers d in one column pass, four blocks beyond 256
         // columns (the bits are the same for all three: the order of summation is a function of d alone)

@@ -273,7 +273,7 @@ class HopPlan:
         seg, nnz, listed = (C.c_int64 * (3 * h_sel))(), (C.c_int64 * (3 * h_sel))(), C.c_int64()
         ld = int(ld_src) if ld_src is not None else (h_sel * d if adjoint else d)
         _capi.check(L.h2gcn_plan_segment_classes(self._handle, self._mask(hops), 1 if adjoint else 0, ld, int(d), seg, nnz, C.byref(listed)))
-        sel = list(range(self.n_hops)) if hops is None else sorted({int(h) for h in hops})
+        sel = self._selected(hops)
         short_walk = ("lane group per segment (binned list)" if listed.value > 0 else
                       "lane group per segment (rounds of consecutive short rows)" if listed.value < 0 else "wave per segment")
         per_hop = [dict(hop=sel[s], segments=dict(short=seg[3 * s], medium=seg[3 * s + 1], long=seg[3 * s + 2]),
@@ -290,6 +290,10 @@ class HopPlan:
             mask |= 1 << int(h)
         _require(mask != 0, "empty hop selection")
         return mask
+
+    def _selected(self, hops) -> list:
+        """The selected hop indices in ascending order: slot ``s`` of a launch is hop ``_selected(hops)[s]``."""
+        return list(range(self.n_hops)) if hops is None else sorted({int(h) for h in hops})
 
     def n_selected(self, hops) -> int:
         return self.n_hops if hops is None else bin(self._mask(hops)).count("1")
@@ -442,18 +446,8 @@ class HopPlan:
             grad = grad.contiguous()  # e.g. an expanded (stride-0) gradient coming out of a reduction
         if x.stride(1) != 1 or x.stride(0) < d:
             x = x.contiguous()
-        sel = list(range(self.n_hops)) if hops is None else sorted({int(h) for h in hops})
-        mask = self._mask(hops)
-        if out is None:
-            out = [torch.empty(self.colidx[k].numel(), dtype=torch.float32, device=self.device) for k in sel]
-        else:
-            out = list(out)
-            _require(len(out) == h_sel, f"out must list {h_sel} tensors (one per selected hop), got {len(out)}")
-            for s, k in enumerate(sel):
-                nnz = self.colidx[k].numel()
-                _require(isinstance(out[s], torch.Tensor) and out[s].dtype == torch.float32 and out[s].device == self.device
-                         and tuple(out[s].shape) == (nnz,) and out[s].is_contiguous(),
-                         f"out[{s}] must be a contiguous float32 [{nnz}] tensor on the plan's device (hop {k})")
+        mask, sel = self._mask(hops), self._selected(hops)
+        out = self._segment_outputs("values gradient", out, sel)
         ld_row, ld_hop = (grad.stride(0) if self.n_rows > 1 else h_sel * d), (grad.stride(1) if h_sel > 1 else d)
         ldx = x.stride(0) if self.n_cols > 1 else d
         if bf16:
@@ -461,42 +455,47 @@ class HopPlan:
             _bf16_layout("x", x, d, (ldx,))
         _require(_capi.has("h2gcn_sddmm_hops_f32"), f"{_capi.library_path()} predates the values gradient (h2gcn_sddmm_hops_*)")
         L = _capi.lib()
-        ptrs = (C.c_void_p * h_sel)(*[t.data_ptr() if t.numel() else None for t in out])
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
             fn = L.h2gcn_sddmm_hops_bf16 if bf16 else L.h2gcn_sddmm_hops_f32
             st = fn(self._handle, mask, C.c_void_p(grad.data_ptr()), ld_row, ld_hop, C.c_void_p(x.data_ptr()), ldx, d,
-                    ptrs, C.c_void_p(stream))
+                    *self._segment_ptrs(out), C.c_void_p(stream))
         _capi.check(st)
         return out
 
-    def _segment_tensors(self, name: str, tensors, sel) -> list:
-        """``tensors`` as a list of one contiguous float32 ``[nnz_k]`` tensor on the plan's device per selected hop."""
+    def _segment_tensors(self, op: str, name: str, tensors, sel) -> list:
+        """``tensors`` as a list of one contiguous float32 ``[nnz_k]`` tensor per selected hop; ``op`` names the operation."""
         _require(not isinstance(tensors, torch.Tensor) and tensors is not None, f"{name} must be a sequence of {len(sel)} tensors (one per selected hop)")
         tensors = list(tensors)
         _require(len(tensors) == len(sel), f"{name} must list {len(sel)} tensors (one per selected hop), got {len(tensors)}")
         for s, k in enumerate(sel):
             t, nnz = tensors[s], self.colidx[k].numel()
             _require(isinstance(t, torch.Tensor), f"{name}[{s}] must be a tensor, got {type(t).__name__}")
-            _require(t.dtype != torch.bfloat16, f"{name}[{s}] is bfloat16: the row softmax is fp32 only (pass .float())")
-            _require(t.dtype == torch.float32, f"{name}[{s}] must be float32 (the row softmax is fp32 only), got {t.dtype}")
+            _require(t.dtype == torch.float32, f"{name}[{s}] must be float32 (the {op} is fp32 only), got {t.dtype}")
             _require(t.device == self.device, f"{name}[{s}] on {t.device}, plan on {self.device}")
             _require(tuple(t.shape) == (nnz,), f"{name}[{s}] must have shape [{nnz}] (one value per stored entry of hop {k}), got {tuple(t.shape)}")
             _require(t.is_contiguous(), f"{name}[{s}] must be contiguous")
         return tensors
 
-    def _row_softmax_launch(self, symbol: str, hops, inputs: dict, out) -> list:
-        sel = list(range(self.n_hops)) if hops is None else sorted({int(h) for h in hops})
-        mask = self._mask(hops)
-        tables = [self._segment_tensors(name, ts, sel) for name, ts in inputs.items()]
+    def _segment_outputs(self, op: str, out, sel) -> list:
+        """The caller's ``out`` list, checked, or new tensors."""
         if out is not None:
-            out = self._segment_tensors("out", out, sel)
+            return self._segment_tensors(op, "out", out, sel)
+        return [torch.empty(self.colidx[k].numel(), dtype=torch.float32, device=self.device) for k in sel]
+
+    @staticmethod
+    def _segment_ptrs(*tables) -> list:
+        """Per table the C ABI's array of one device pointer per selected hop (NULL for a hop without entries)."""
+        arr_t = C.c_void_p * len(tables[0])
+        return [arr_t(*[t.data_ptr() if t.numel() else None for t in ts]) for ts in tables]
+
+    def _row_softmax_launch(self, symbol: str, hops, inputs: dict, out) -> list:
+        mask, sel = self._mask(hops), self._selected(hops)
+        tables = [self._segment_tensors("row softmax", name, ts, sel) for name, ts in inputs.items()]
+        out = self._segment_outputs("row softmax", out, sel)
         if not _capi.has(symbol):
             raise RuntimeError(f"{_capi.library_path()} predates the row softmax (h2gcn_row_softmax_hops_f32 / _backward_hops_f32): rebuild it")
-        if out is None:
-            out = [torch.empty(self.colidx[k].numel(), dtype=torch.float32, device=self.device) for k in sel]
-        arr_t = C.c_void_p * len(sel)
-        ptrs = [arr_t(*[t.data_ptr() if t.numel() else None for t in ts]) for ts in tables + [out]]
+        ptrs = self._segment_ptrs(*tables, out)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
             st = getattr(_capi.lib(), symbol)(self._handle, mask, *ptrs, C.c_void_p(stream))

@@ -5,19 +5,18 @@ next to what a caller had before the kernels existed: the torch composite over a
     backward   D = index_add(alpha * g);  ds = alpha * (g - D[row])
 (the row index -- repeat_interleave, 8 B per nonzero -- is built once, outside the timed region).
 usage: python tools/row_softmax_kernels.py [--shapes arxiv,products] [--reps R] [--rounds Q]
-Everything runs in ONE process after 3 warm-up launches of every configuration; each launch sits between its own pair of device
-events; a figure is the median of R launches (default 12); Q rounds (default 2), the configurations taking turns inside a round
-(the spread between the rounds of one configuration is the noise).  "of 8 TB/s": the byte model of the launch,
+The measuring loop is tools/_launch_timing.py: a figure is the median of R launches (default 12); Q rounds (default 2), whose
+spread is the noise.  "of 8 TB/s": the byte model of the launch,
     forward    sum_k nnz_k * 8  + (n_rows + 1) * 8 * H          backward   sum_k nnz_k * 12 + (n_rows + 1) * 8 * H,
 over the time, as a fraction of 8e12 B/s (the composite is rated on the same bytes: what the result needs, not what it moves)."""
 import argparse
-import statistics
 import sys
 from pathlib import Path
 
 import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+from _launch_timing import print_bandwidth, round_medians, warm_up
 from h2gcn_amd import HopPlan, synth
 
 ap = argparse.ArgumentParser()
@@ -26,7 +25,6 @@ ap.add_argument("--reps", type=int, default=12)
 ap.add_argument("--rounds", type=int, default=2)
 a = ap.parse_args()
 dev = torch.device("cuda:0")
-PEAK = 8.0e12
 
 
 def composite_forward(rows, n, scores, out):
@@ -43,15 +41,6 @@ def composite_backward(rows, n, alpha, grad, out):
         dot = torch.zeros(n, device=dev).index_add_(0, r, alpha[s] * grad[s])
         torch.mul(alpha[s], grad[s] - dot[r], out=out[s])
     return out
-
-
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
 
 
 for shape in a.shapes.split(","):
@@ -77,27 +66,17 @@ for shape in a.shapes.split(","):
     seg = plan.segment_classes(128)["per_hop"]
     print(f"== {shape}: n = {n}, nonzeros per hop {nnz}, segments per hop (short <= 16 / medium / long): "
           + ", ".join(f"{h['segments']['short']} / {h['segments']['medium']} / {h['segments']['long']}" for h in seg))
-    for fn, _ in configs.values():
-        for _ in range(3):
-            fn()
-    torch.cuda.synchronize()
+    fns = {k: fn for k, (fn, _) in configs.items()}
+    warm_up(fns)
     # same quantities: the composite's exp and order of summation are torch's, so compare with a tolerance
     print(f"   max |kernel - composite|: forward {max(float((p - q).abs().max()) for p, q in zip(alpha, alpha_c)):.3e}, "
           f"backward {max(float((p - q).abs().max()) for p, q in zip(ds, ds_c)):.3e}")
-    med = {k: [] for k in configs}
-    for rnd in range(a.rounds):
-        ts = {k: [] for k in configs}
-        for _ in range(a.reps):
-            for k, (fn, _) in configs.items():        # the configurations take turns
-                ts[k].append(timed(fn))
-        for k in configs:
-            med[k].append(statistics.median(ts[k]))
+    med = round_medians(fns, a.reps, a.rounds)
     for k, (_, per_nnz) in configs.items():
         nbytes = sum(z * per_nnz for z in nnz) + (n + 1) * 8 * H
-        line = "  ".join(f"round {r}: {t:9.4f} ms  {nbytes / (t * 1e-3) / PEAK:6.3f} of 8 TB/s" for r, t in enumerate(med[k]))
-        print(f"   {k:26s} {line}")
+        print_bandwidth(k, 26, med[k], nbytes)
     for d in ("forward", "backward"):
         r = [p / q for p, q in zip(med[f"torch composite {d}"], med[f"row_softmax {d}"])]
         print(f"   torch composite / row_softmax {d}: " + "  ".join(f"{v:.2f}" for v in r))
-    del plan, csr, scores, grad, rows, alpha, ds, alpha_c, ds_c, configs
+    del plan, csr, scores, grad, rows, alpha, ds, alpha_c, ds_c, configs, fns
     torch.cuda.empty_cache()

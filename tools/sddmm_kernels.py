@@ -3,19 +3,18 @@ of the same plan and width (HopPlan.spmm), on the synthetic operands of h2gcn_am
 --composite-max-nnz nonzeros per hop -- next to what a caller had before the kernel existed: the chunked torch composite
 (grad[row_of_entry, s] * x[col]).sum(-1), chunks of 2^20 entries.
 usage: python tools/sddmm_kernels.py [--shapes arxiv,products] [--d 128] [--reps R] [--rounds Q] [--composite-max-nnz N]
-Everything runs in ONE process after 3 warm-up launches of every configuration; each launch sits between its own pair of device
-events; a figure is the median of R launches (default 12); Q rounds (default 2), the configurations taking turns inside a round
-(the spread between the rounds of one configuration is the noise).  "of 8 TB/s": the algorithmic bytes of the launch,
+The measuring loop is tools/_launch_timing.py: a figure is the median of R launches (default 12); Q rounds (default 2), whose
+spread is the noise.  "of 8 TB/s": the algorithmic bytes of the launch,
     sum_k nnz_k * (4 + 4 + d*s) + n_rows * H * d*s + (n_rows + 1) * 8 * H        (s = bytes per element of grad / x),
 over the time, as a fraction of 8e12 B/s -- the same count for the forward launch, which moves nearly the same bytes."""
 import argparse
-import statistics
 import sys
 from pathlib import Path
 
 import torch
 
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+from _launch_timing import print_bandwidth, round_medians, warm_up
 from h2gcn_amd import HopPlan, synth
 
 ap = argparse.ArgumentParser()
@@ -26,7 +25,6 @@ ap.add_argument("--rounds", type=int, default=2)
 ap.add_argument("--composite-max-nnz", type=int, default=2_000_000)
 a = ap.parse_args()
 dev = torch.device("cuda:0")
-PEAK = 8.0e12
 CHUNK = 1 << 20
 
 
@@ -37,15 +35,6 @@ def composite(rows, cols, grad, x, out):
             r, c = rows[s][lo:lo + CHUNK], cols[s][lo:lo + CHUNK]
             out[s][lo:lo + CHUNK] = (grad[r, s, :] * x[c, :]).sum(-1)
     return out
-
-
-def timed(fn):
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1)
 
 
 for shape in a.shapes.split(","):
@@ -71,31 +60,21 @@ for shape in a.shapes.split(","):
         dv_c = [torch.empty(z, device=dev) for z in nnz]
         configs["torch composite f32"] = (lambda: composite(rows, cols, g32, x32, dv_c), 4)
     print(f"== {shape}: n = {n}, nonzeros per hop {nnz}, d = {d}, schedule of the forward launch: {plan.schedule(d)}")
-    for fn, _ in configs.values():
-        for _ in range(3):
-            fn()
-    torch.cuda.synchronize()
+    fns = {k: fn for k, (fn, _) in configs.items()}
+    warm_up(fns)
     if with_composite:      # same quantity: the composite's order of summation is torch's, so compare with a tolerance
         plan.sddmm(g32, x32, out=dv)
         err = max(float((p - q).abs().max()) for p, q in zip(dv, dv_c))
         print(f"   max |kernel - composite| = {err:.3e}")
-    med = {k: [] for k in configs}
-    for rnd in range(a.rounds):
-        ts = {k: [] for k in configs}
-        for _ in range(a.reps):
-            for k, (fn, _) in configs.items():        # the configurations take turns
-                ts[k].append(timed(fn))
-        for k in configs:
-            med[k].append(statistics.median(ts[k]))
+    med = round_medians(fns, a.reps, a.rounds)
     for k, (_, s) in configs.items():
         nbytes = sum(z * (4 + 4 + d * s) for z in nnz) + n * H * d * s + (n + 1) * 8 * H
-        line = "  ".join(f"round {r}: {t:9.4f} ms  {nbytes / (t * 1e-3) / PEAK:6.3f} of 8 TB/s" for r, t in enumerate(med[k]))
-        print(f"   {k:22s} {line}")
+        print_bandwidth(k, 22, med[k], nbytes)
     for name in ops:
         r = [p / q for p, q in zip(med[f"sddmm {name}"], med[f"spmm  {name}"])]
         print(f"   sddmm / spmm {name}: " + "  ".join(f"{v:.3f}" for v in r))
     if with_composite:
         r = [p / q for p, q in zip(med["torch composite f32"], med["sddmm f32"])]
         print("   torch composite / sddmm f32: " + "  ".join(f"{v:.2f}" for v in r))
-    del plan, csr, ops, configs, x32, g32, dv, y
+    del plan, csr, ops, configs, fns, x32, g32, dv, y
     torch.cuda.empty_cache()
