@@ -40,7 +40,16 @@ struct PatternView {
     uint32_t mask;
 };
 int pattern_view(const h2gcn_plan* plan, uint32_t hop_mask, PatternView* out);
-int pattern_long_list(const h2gcn_plan* plan, uint32_t mask, hipStream_t stream, const int64_t** list_dev, int* n_long);
+int pattern_long_list(const h2gcn_plan* plan, uint32_t mask, hipStream_t stream, const int64_t** list_dev, int* n_long,
+                      bool adjoint = false);
+
+// The adjoint view of a hop selection, for the column side of edge_scores.hip: `out` describes A_k^T (n_rows = the plan's n_cols,
+// rowptr / colidx = t_rowptr / t_colidx -- the forward arrays of a symmetric plan) and perm[s][e'] is the forward entry behind
+// transposed entry e' (a symmetric plan's partner).  Touches no device.  H2GCN_ERR_NO_TRANSPOSE on a plan without transposed
+// operands, H2GCN_ERR_INVALID_ARGUMENT on one created without H2GCN_PLAN_KEEP_PERMUTATION.  The long-segment list that goes with
+// it is pattern_long_list(..., adjoint = true): one entry per ROW that is long in any selected hop (no `<< 4 | s`), the list the
+// adjoint launch of the selection uses.
+int adjoint_view(const h2gcn_plan* plan, uint32_t hop_mask, PatternView* out, const uint32_t** perm);
 
 }  // namespace h2gcn
 

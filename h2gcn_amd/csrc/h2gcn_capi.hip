@@ -1240,11 +1240,32 @@ int pattern_view(const h2gcn_plan* plan, uint32_t hop_mask, PatternView* out) {
     return H2GCN_OK;
 }
 
-int pattern_long_list(const h2gcn_plan* plan, uint32_t mask, hipStream_t stream, const int64_t** list_dev, int* n_long) {
+int pattern_long_list(const h2gcn_plan* plan, uint32_t mask, hipStream_t stream, const int64_t** list_dev, int* n_long, bool adjoint) {
     const int st = check_device(plan);
     if (st != H2GCN_OK) return st;
     CaptureScope capture_scope(stream);
-    return get_long_list(plan, false, mask, list_dev, n_long);
+    return get_long_list(plan, adjoint, mask, list_dev, n_long);
+}
+
+int adjoint_view(const h2gcn_plan* plan, uint32_t hop_mask, PatternView* out, const uint32_t** perm) {
+    int st = pattern_view(plan, hop_mask, out);
+    if (st != H2GCN_OK) return st;
+    if (!plan->has_transpose) return fail(H2GCN_ERR_NO_TRANSPOSE, "plan was created without H2GCN_PLAN_BUILD_TRANSPOSE");
+    out->n_rows = plan->n_cols;
+    out->n_cols = plan->n_rows;
+    int s = 0;
+    for (int k = 0; k < plan->n_hops; ++k) {
+        if (!(out->mask & (1u << k))) continue;
+        const HopOperand& op = plan->adj[k];
+        if (op.nnz > 0 && !op.perm)
+            return fail(H2GCN_ERR_INVALID_ARGUMENT, "plan has transposed operands but was created without H2GCN_PLAN_KEEP_PERMUTATION");
+        out->rowptr[s] = op.rowptr;
+        out->colidx[s] = op.colidx;
+        out->nnz[s] = op.nnz;
+        perm[s] = op.perm;
+        ++s;
+    }
+    return H2GCN_OK;
 }
 }  // namespace h2gcn
 }  // extern "C++"

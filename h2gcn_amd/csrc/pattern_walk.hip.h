@@ -108,10 +108,13 @@ int check_hop_arrays(const PatternView& v, const char* name, T* const* ptrs) {
 }
 
 // Fills `g` and the grid size (0: nothing to launch).  The first step that touches the device (the long list): checks come before.
-inline int launch_geometry(const h2gcn_plan* plan, const PatternView& v, hipStream_t stream, Geom* g, int64_t* n_blocks) {
+// `adjoint`: v is an adjoint_view and the list is the adjoint's -- one entry per row that is long in any selected hop, bare (no
+// `<< 4 | s`): long_segment does not read it.
+inline int launch_geometry(const h2gcn_plan* plan, const PatternView& v, hipStream_t stream, Geom* g, int64_t* n_blocks,
+                           bool adjoint = false) {
     *n_blocks = 0;
     if (selected_nnz(v) == 0 || v.n_rows == 0) return H2GCN_OK;
-    const int st = pattern_long_list(plan, v.mask, stream, &g->long_list, &g->n_long);
+    const int st = pattern_long_list(plan, v.mask, stream, &g->long_list, &g->n_long, adjoint);
     if (st != H2GCN_OK) return st;
     for (int s = 0; s < v.n_sel; ++s) g->rowptr[s] = v.rowptr[s];
     g->n_sel = v.n_sel;

@@ -520,6 +520,83 @@ class HopPlan:
         ``alpha`` (the forward's result) and ``grad`` as ``scores`` above; ``out`` may be the ``grad`` tensors themselves."""
         return self._row_softmax_launch("h2gcn_row_softmax_backward_hops_f32", hops, {"alpha": alpha, "grad": grad}, out)
 
+    def _node_operand(self, name: str, t, n: int, h_sel: int):
+        """``t`` as the C ABI takes a per-node operand of the edge scores: float32 ``[n, h_sel]`` with unit column stride (a row
+        stride passes through; 1-D when ``h_sel == 1``) -> ``(tensor, row stride in elements)``."""
+        _require(isinstance(t, torch.Tensor), f"{name} must be a tensor, got {type(t).__name__}")
+        _require(t.dtype == torch.float32, f"{name} must be float32 (the edge scores are fp32 only), got {t.dtype}")
+        _require(t.device == self.device, f"{name} on {t.device}, plan on {self.device}")
+        if t.dim() == 1 and h_sel == 1:
+            t = t.unsqueeze(1)
+        _require(t.dim() == 2 and tuple(t.shape) == (n, h_sel),
+                 f"{name} must have shape [{n}, {h_sel}] (one column per selected hop{'; or [' + str(n) + ']' if h_sel == 1 else ''}), got {tuple(t.shape)}")
+        if (h_sel > 1 and t.stride(1) != 1) or (n > 1 and t.stride(0) < h_sel):
+            t = t.contiguous()
+        return t, (t.stride(0) if n > 1 else h_sel)
+
+    @staticmethod
+    def _edge_scores_symbols() -> None:
+        if not _capi.has("h2gcn_edge_scores_hops_f32"):
+            raise RuntimeError(f"{_capi.library_path()} predates the edge scores (h2gcn_edge_scores_hops_f32 / _backward_hops_f32): rebuild it")
+
+    def edge_scores(self, l: torch.Tensor, r: torch.Tensor, negative_slope: float = 0.2, hops=None,
+                    out: Optional[Sequence[torch.Tensor]] = None) -> list:
+        """Additive (GAT-style) attention scores on the pattern: ``score[s][e] = leaky_relu(l[i, s] + r[j, s], negative_slope)`` for
+        every stored entry ``e = (i, j)`` of selected hop ``s`` -> one contiguous float32 ``[nnz_k]`` tensor per selected hop, in
+        the entry order of ``colidx[k]`` (``h2gcn_edge_scores_hops_f32``: one launch, no row-of-entry index) -- what
+        :meth:`row_softmax` takes.  The bits are those of ``torch.nn.functional.leaky_relu(l[row, s] + r[col, s], slope)``.
+
+        ``l`` ``[n_rows, H_sel]`` and ``r`` ``[n_cols, H_sel]``: float32 on the plan's device (1-D when ``H_sel == 1``); a row
+        stride passes through (column slices of a wider tensor), a non-unit column stride is made contiguous.  ``out``: a list of
+        ``H_sel`` contiguous float32 ``[nnz_k]`` tensors to overwrite.  Only the forward pattern is read: no transposed operand
+        is needed."""
+        mask, sel = self._mask(hops), self._selected(hops)
+        l, ldl = self._node_operand("l", l, self.n_rows, len(sel))
+        r, ldr = self._node_operand("r", r, self.n_cols, len(sel))
+        out = self._segment_outputs("edge scores", out, sel)
+        self._edge_scores_symbols()
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            st = _capi.lib().h2gcn_edge_scores_hops_f32(self._handle, mask, C.c_void_p(l.data_ptr()), ldl, C.c_void_p(r.data_ptr()), ldr,
+                                                        float(negative_slope), *self._segment_ptrs(out), C.c_void_p(stream))
+        _capi.check(st)
+        return out
+
+    def edge_scores_backward(self, l: torch.Tensor, r: torch.Tensor, grad: Sequence[torch.Tensor], negative_slope: float = 0.2,
+                             hops=None, need_dl: bool = True, need_dr: bool = True) -> tuple:
+        """The backward of :meth:`edge_scores` -> ``(dl, dr)``: with ``t[e] = grad[s][e]`` where ``l[i, s] + r[j, s] > 0`` and
+        ``grad[s][e] * negative_slope`` elsewhere, ``dl[i, s]`` is the sum of ``t`` over row ``i`` and ``dr[j, s]`` the sum over
+        column ``j`` of selected hop ``s`` (``h2gcn_edge_scores_backward_hops_f32``).  No atomics: one fixed summation order per
+        row / column (``include/h2gcn_hip.h``), so the bits are reproducible and do not depend on the plan's tunables.  Every
+        element is written; a row / column without entries gets ``+0``.
+
+        ``l``, ``r`` as in :meth:`edge_scores`; ``grad``: ``H_sel`` contiguous float32 ``[nnz_k]`` tensors.  ``need_dl`` /
+        ``need_dr``: compute only that side (``None`` for the other; both ``False`` is refused).  ``dr`` walks the plan's
+        transposed operands through their permutation: the plan must have been built with ``build_transpose=True,
+        keep_permutation=True`` (``symmetric_pattern=True`` serves it on the forward arrays); ``dl`` needs neither."""
+        mask, sel = self._mask(hops), self._selected(hops)
+        h_sel = len(sel)
+        _require(need_dl or need_dr, "need_dl and need_dr are both False: nothing to compute")
+        shapes = (l.shape if isinstance(l, torch.Tensor) else None, r.shape if isinstance(r, torch.Tensor) else None)
+        l, ldl = self._node_operand("l", l, self.n_rows, h_sel)
+        r, ldr = self._node_operand("r", r, self.n_cols, h_sel)
+        grad = self._segment_tensors("edge scores", "grad", grad, sel)
+        _require(not need_dr or (self.has_transpose and self.keep_permutation),
+                 "the gradient wrt r sums over the COLUMNS of the hop matrices: it walks the plan's transposed operands through their "
+                 "permutation.  Build the plan with HopPlan(..., build_transpose=True, keep_permutation=True)"
+                 + ("" if self.has_transpose else " (this plan has no transposed operands)"))
+        self._edge_scores_symbols()
+        dl = torch.empty((self.n_rows, h_sel), dtype=torch.float32, device=self.device) if need_dl else None
+        dr = torch.empty((self.n_cols, h_sel), dtype=torch.float32, device=self.device) if need_dr else None
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            st = _capi.lib().h2gcn_edge_scores_backward_hops_f32(
+                self._handle, mask, C.c_void_p(l.data_ptr()), ldl, C.c_void_p(r.data_ptr()), ldr, float(negative_slope),
+                *self._segment_ptrs(grad), C.c_void_p(dl.data_ptr()) if need_dl else None, h_sel,
+                C.c_void_p(dr.data_ptr()) if need_dr else None, h_sel, C.c_void_p(stream))
+        _capi.check(st)
+        return (dl.view(shapes[0]) if need_dl else None, dr.view(shapes[1]) if need_dr else None)
+
     def __del__(self):
         h = getattr(self, "_handle", None)
         if h is not None and h.value:

@@ -173,6 +173,114 @@ def hop_softmax(adjhops: HopPlan, scores, hops: Optional[Iterable[int]] = None) 
     return tuple(adjhops.row_softmax(scores, hops=sel))
 
 
+class _HopEdgeScores(torch.autograd.Function):
+    """The additive edge scores on the hop pattern: forward -- ONE launch over the selected hops (``HopPlan.edge_scores``), ``l``
+    and ``r`` saved (the backward recomputes ``pre``); backward -- ONE call (``HopPlan.edge_scores_backward``) on the contiguous
+    incoming gradients (a hop nobody differentiated through enters as zeros), for the sides whose input requires a gradient."""
+
+    @staticmethod
+    def forward(ctx, plan: HopPlan, hops, negative_slope: float, l: torch.Tensor, r: torch.Tensor):
+        scores = plan.edge_scores(l, r, negative_slope, hops=hops)
+        ctx.plan, ctx.hops, ctx.negative_slope = plan, hops, negative_slope
+        ctx.save_for_backward(l, r)
+        return tuple(scores)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        need_dl, need_dr = ctx.needs_input_grad[3:5]
+        if not (need_dl or need_dr):
+            return None, None, None, None, None
+        l, r = ctx.saved_tensors
+        plan = ctx.plan
+        grads = [torch.zeros(plan.colidx[k].numel(), dtype=torch.float32, device=plan.device) if g is None else g.contiguous()
+                 for g, k in zip(grads, plan._selected(ctx.hops))]
+        dl, dr = plan.edge_scores_backward(l, r, grads, ctx.negative_slope, hops=ctx.hops, need_dl=need_dl, need_dr=need_dr)
+        return None, None, None, dl, dr
+
+
+def hop_edge_scores(adjhops: HopPlan, l: torch.Tensor, r: torch.Tensor, negative_slope: float = 0.2,
+                    hops: Optional[Iterable[int]] = None) -> tuple:
+    """Additive (GAT-style) attention scores over the hop pattern: ``scores[s][e] = leaky_relu(l[i, s] + r[j, s], negative_slope)``
+    for every stored entry ``e = (i, j)`` of selected hop ``s``, as a tuple of ``H_sel`` float32 ``[nnz_k]`` tensors in the entry
+    order of ``colidx[k]`` (what :func:`hop_softmax` takes), differentiable wrt ``l`` and ``r``.  There is no row-of-entry index,
+    no gather and no ``index_add``: forward and backward are one call each (:meth:`HopPlan.edge_scores` /
+    :meth:`HopPlan.edge_scores_backward`), and the backward is free of atomics -- its bits are reproducible.
+
+    ``l`` ``[n_rows, H_sel]``, ``r`` ``[n_cols, H_sel]``: float32 on the plan's device (1-D when one hop is selected; bfloat16 is
+    refused: the kernels are fp32 only).  The backward computes only the sides whose input requires a gradient.  A gradient for
+    ``r`` sums over the columns of the hop matrices: the plan must have been built with ``build_transpose=True,
+    keep_permutation=True`` (what ``hop_spmm(..., values=...)`` asks of a differentiable input already).  Row-partitioned
+    operands (``ShardedHops``) are not covered."""
+    if hasattr(adjhops, "aggregate"):
+        raise ValueError("hop_edge_scores is not supported on row-partitioned operands (ShardedHops): pass a single-GPU HopPlan")
+    if not isinstance(adjhops, HopPlan):
+        raise TypeError(f"adjhops must be a HopPlan, got {type(adjhops).__name__}")
+    sel = None if hops is None else tuple(sorted(set(int(h) for h in hops)))
+    grads = [isinstance(t, torch.Tensor) and t.requires_grad and torch.is_grad_enabled() for t in (l, r)]
+    if grads[1] and not (adjhops.has_transpose and adjhops.keep_permutation):
+        raise ValueError("hop_edge_scores with an r that requires a gradient: that gradient sums over the columns of the hop matrices, "
+                         "on the plan's transposed operands through their permutation.  Build the plan with "
+                         "HopPlan(..., build_transpose=True, keep_permutation=True)")
+    if any(grads):
+        # (the argument checks of the launch run first either way: HopPlan.edge_scores refuses before any device work)
+        return _HopEdgeScores.apply(adjhops, sel, float(negative_slope), l, r)
+    return tuple(adjhops.edge_scores(l, r, negative_slope, hops=sel))
+
+
+class HopAttention(torch.nn.Module):
+    """``HopAttention(in_dim, hops=None, n_hops=2, negative_slope=0.2)(adjhops, inputs) -> [N, H_sel, d]``: the attention
+    counterpart of :class:`GCNLayer` -- per selected hop ``s`` the rows of ``inputs`` are aggregated with coefficients
+
+        ``alpha_s[i, j] = softmax_j( leaky_relu(inputs[i] . a_l[s] + inputs[j] . a_r[s]) )``   over the stored entries of row ``i``
+
+    (single-head GAT attention over the 1-hop / 2-hop rings, one softmax per hop and row).  The chain is ``l = inputs @ a_l.T``,
+    ``r = inputs @ a_r.T`` -> :func:`hop_edge_scores` -> :func:`hop_softmax` -> ``hop_spmm(adjhops, inputs, hops, values=alpha)``,
+    every link one launch forward and one call backward, none of them atomic: two identical training steps give identical bits.
+
+    ``a_l``, ``a_r``: parameters ``[H_sel, in_dim]``, Glorot-uniform.  ``hops``: the hop indices to attend over (``H_sel`` of
+    them); ``None`` takes all ``n_hops`` hops of the plan.  Like ``hop_spmm(..., values=...)`` the layer INSTALLS the coefficients
+    in the plan (``set_values``): the plan keeps pointing at them, and the stored values it was built with are not used.  It
+    needs a square plan built with ``build_transpose=True, keep_permutation=True`` to be trained.  Row-partitioned operands
+    (``ShardedHops``) are not covered."""
+
+    SIGNATURE = ["adjhops", "inputs"]
+
+    def __init__(self, in_dim: int, hops=None, n_hops: int = 2, negative_slope: float = 0.2):
+        super().__init__()
+        self.hops = None if hops is None else tuple(sorted(set(int(h) for h in hops)))
+        self.in_dim = int(in_dim)
+        self.negative_slope = float(negative_slope)
+        h_sel = int(n_hops) if self.hops is None else len(self.hops)
+        if h_sel < 1 or self.in_dim < 1:
+            raise ValueError(f"HopAttention needs at least one hop and one input column, got {h_sel} hops and in_dim = {in_dim}")
+        self.a_l = torch.nn.Parameter(torch.empty(h_sel, self.in_dim))
+        self.a_r = torch.nn.Parameter(torch.empty(h_sel, self.in_dim))
+        torch.nn.init.xavier_uniform_(self.a_l)
+        torch.nn.init.xavier_uniform_(self.a_r)
+
+    def forward(self, adjhops: HopPlan, inputs: torch.Tensor) -> torch.Tensor:
+        if hasattr(adjhops, "aggregate"):
+            raise ValueError("HopAttention is not supported on row-partitioned operands (ShardedHops): pass a single-GPU HopPlan")
+        if not isinstance(adjhops, HopPlan):
+            raise TypeError(f"adjhops must be a HopPlan, got {type(adjhops).__name__}")
+        h_sel = self.a_l.shape[0]
+        if adjhops.n_selected(self.hops) != h_sel:
+            raise ValueError(f"HopAttention holds attention vectors for {h_sel} hops, the plan has {adjhops.n_hops}: pass hops= or n_hops=")
+        if adjhops.n_rows != adjhops.n_cols:
+            raise ValueError(f"HopAttention needs a square plan (the same nodes attend and are attended to), got {adjhops.n_rows} x {adjhops.n_cols}")
+        if inputs.dim() != 2 or inputs.shape[1] != self.in_dim:
+            raise ValueError(f"inputs must be [{adjhops.n_cols}, {self.in_dim}], got {tuple(inputs.shape)}")
+        l, r = inputs @ self.a_l.t(), inputs @ self.a_r.t()
+        alpha = hop_softmax(adjhops, hop_edge_scores(adjhops, l, r, self.negative_slope, self.hops), self.hops)
+        values = [None] * adjhops.n_hops     # hop_spmm takes one entry per hop of the plan
+        for s, k in enumerate(adjhops._selected(self.hops)):
+            values[k] = alpha[s]
+        return hop_spmm(adjhops, inputs, self.hops, values=values)
+
+    def extra_repr(self) -> str:
+        return f"in_dim={self.in_dim}, hops={None if self.hops is None else list(self.hops)}, negative_slope={self.negative_slope}"
+
+
 class GCNLayer(torch.nn.Module):
     """``GCNLayer(hops=None)(adjhops, inputs) -> [N, H_sel, d]`` (reference ``_layers.py:54-81``).
 

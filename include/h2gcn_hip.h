@@ -467,6 +467,72 @@ int h2gcn_row_softmax_backward_hops_f32(const h2gcn_plan_t* plan, uint32_t hop_m
                                         const float* const* dalpha_dev, float* const* dscores_dev, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Additive (GAT-style) edge scores on the hop pattern and their backward (an additive extension of ABI 5: look the symbols up
+ * before calling a build that may predate it) -- what PRODUCES the per-entry scores that h2gcn_row_softmax_hops_f32 turns into
+ * attention coefficients, and what takes their gradient back to the nodes.  For every selected hop k (s = its rank among the
+ * selected hops) and every stored entry e = (i, j) of A_k:
+ *
+ *     forward    pre[e]      = l[i*ldl + s] + r[j*ldr + s]                one fp32 addition
+ *                score[s][e] = pre > 0 ? pre : pre * negative_slope       one fp32 multiplication on the negative branch
+ *     backward   t[e]        = pre > 0 ? g[s][e] : g[s][e] * negative_slope     pre recomputed as above; a NaN pre takes the
+ *                                                                               slope branch (as torch's leaky_relu does)
+ *                dl[i*lddl + s] = sum of t[e] over row i of A_k           in stored order
+ *                dr[j*lddr + s] = sum of t[e] over column j of A_k        = over row j of A_k^T, in A_k^T's stored order
+ *
+ * fp32 only.  No row-of-entry index exists anywhere: the kernels walk the CSR pattern.
+ *
+ *   l_dev      [n_rows, H_sel], row stride ldl >= H_sel (elements), column stride 1
+ *   r_dev      [n_cols, H_sel], row stride ldr >= H_sel.  n_rows != n_cols is allowed (shard plans, row-selected sub-plans)
+ *   scores_dev / dscores_dev   HOST arrays of H_sel device pointers; entry s holds nnz_k floats in the entry order of
+ *              colidx_dev[k].  An entry may be NULL only when its hop has no nonzeros.
+ *   dl_dev     [n_rows, H_sel] through lddl >= H_sel;  dr_dev [n_cols, H_sel] through lddr >= H_sel.  Either may be NULL: that
+ *              side is not computed (both NULL is an error).
+ * Outputs are OVERWRITTEN.  dl / dr are written for every row / column of every selected hop; an empty segment writes +0 (a
+ * per-node output has no "write nothing").  Outputs must not overlap any input or each other.
+ *
+ * The ROW side (scores, dl) reads only the plan's forward rowptr / colidx -- neither values nor transposes -- so it works on
+ * plans created without H2GCN_PLAN_BUILD_TRANSPOSE.  The COLUMN side (dr) walks the plan's adjoint operand A_k^T through its
+ * permutation: for transposed entry e' of row j, i = t_colidx[e'], g = dscores[s][perm[e']], pre = l[i] + r[j]; nothing of size
+ * nnz is materialised.  It needs H2GCN_PLAN_BUILD_TRANSPOSE and H2GCN_PLAN_KEEP_PERMUTATION (what h2gcn_plan_set_values
+ * requires already); a H2GCN_PLAN_SYMMETRIC_PATTERN plan with the permutation kept serves it on the forward arrays.  Without
+ * transposed operands the call returns H2GCN_ERR_NO_TRANSPOSE, without the permutation H2GCN_ERR_INVALID_ARGUMENT with a message
+ * that names H2GCN_PLAN_KEEP_PERMUTATION -- both before the device is touched and before the row side runs.
+ * All offsets are 64-bit.  No atomics: two launches give the same bits.
+ *
+ * Arithmetic of dl / dr: ONE order per segment (a row of A_k, or a row of A_k^T), a function of the segment's own terms t_m,
+ * m = 0 .. n-1 in stored order, and of nothing else -- the row softmax's tree:
+ *   256 partials P[q], q = m mod 256, each starting at +0 and accumulated sequentially in ascending m:  P[q] = P[q] + t_m
+ *   W_w, w = 0..3: the xor butterfly over lane distances 1, 2, 4, 8, 16, 32 of P[64w .. 64w+63]
+ *       (v1[q] = P[q] + P[q^1], v2[q] = v1[q] + v1[q^2], ... W_w = v32[q] + v32[q^32])
+ *   total = (W_0 + W_1) + (W_2 + W_3)
+ * A partial that starts at +0 and is only added to is never -0 (+0 + -0 = +0), and neither is any sum of values that are not
+ * -0; so a partial, a wave total or a pair total that received no entry is +0 and adding it changes no bit.  The bits of dl /
+ * dr therefore never depend on which mapping served the segment (16-lane group, one wave, 4-wave workgroup), on
+ * long_row_threshold, rows_per_wave, variant, slice_cols or the hop selection, and the column side of a symmetric plan equals
+ * that of a plan with built transposes.
+ * Error bound: every term is exact or one rounding (g * slope), and any order of an n-term fp32 sum satisfies
+ *   |dl - exact| <= gamma_{n+1} * sum_m |t_m| + (n + 1) * 2^-149,   gamma_k = k*u / (1 - k*u), u = 2^-24
+ * (exact: real arithmetic on the fp32 inputs with the branch taken from the fp32 pre), and the same for dr.
+ * Non-finite inputs follow IEEE arithmetic entry by entry: a NaN or an inf - inf in pre gives a NaN score there and t = g * slope;
+ * only the dl / dr elements whose segment contains a non-finite t are non-finite, every other element keeps its bits.
+ *
+ * hipGraph capture: the condition of the forward launch of the same hop selection, as for h2gcn_sddmm_hops_*: segments with
+ * >= long_row_threshold entries are served from the plan's long-segment list of the selection -- the forward launch's list for
+ * scores and dl, the adjoint launch's for dr -- built by the FIRST launch of that selection (of any kernel that uses it; the
+ * all-hops lists at plan creation).  A launch that would have to build one while its stream is being captured returns
+ * H2GCN_ERR_INVALID_ARGUMENT with the same advice (run the launch once eagerly first).
+ *
+ * Validation, all before the device is touched, each H2GCN_ERR_INVALID_ARGUMENT with a message naming the argument: a NULL
+ * plan ("plan is NULL"), a hop mask outside the plan, ldl / ldr / lddl / lddr smaller than H_sel, a NULL l / r when the selection
+ * has nonzeros, a NULL table or a NULL entry of a selected hop that has nonzeros, dl and dr both NULL.
+ */
+int h2gcn_edge_scores_hops_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* l_dev, int64_t ldl,
+                               const float* r_dev, int64_t ldr, float negative_slope, float* const* scores_dev, void* stream);
+int h2gcn_edge_scores_backward_hops_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* l_dev, int64_t ldl,
+                                        const float* r_dev, int64_t ldr, float negative_slope, const float* const* dscores_dev,
+                                        float* dl_dev, int64_t lddl, float* dr_dev, int64_t lddr, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Operand construction on the device: exact-k-hop neighbourhood rings and their normalisation -- the step that
  * FEEDS the aggregation.  Stands in for TransformSPAdj.nhoodSplit (reference h2gcn/datasets/_dataset.py:138-158:
  * `mt <- bin(mt @ (A + I))`, ring_k = mt_k - mt_{k-1}, a host SpGEMM in scipy) and TransformSPAdj.normalize
