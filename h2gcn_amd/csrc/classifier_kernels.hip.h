@@ -732,11 +732,13 @@ int with_nt_mask(int nt, int mask, F&& f) {
 }
 
 // ---- launch code of the entry points (arguments already validated for the element types by the callers) -------------------
-// ROWS: n_rows is the length of the row list `rows` (device, ascending, unique, every entry a row of X); Y / G / dX are compact
+// ROWS: n_rows is the length of the row list `rows` (device, ascending, unique, every entry a row of X); Y / G / dX are compact;
+// x_rows is the row count of X itself, which picks the kernel family (small_operand) -- the one the full-matrix call on that X
+// takes, whatever the length of the list: Z_c and dX_c have the bits of the full call's rows only if both run the same kernels
 template <typename TX, bool ROWS = false>
 int dropout_dense_forward(const TX* X, int64_t ldx, int64_t n_rows, int32_t K, const float* W, int32_t C, const float* bias,
                           float keep_prob, uint64_t seed, const int64_t* step_dev, float* Y, int64_t ldy, void* workspace,
-                          size_t workspace_bytes, void* stream_v, const int32_t* rows = nullptr) {
+                          size_t workspace_bytes, void* stream_v, const int32_t* rows = nullptr, int64_t x_rows = -1) {
     int st = check_common(X, ldx, n_rows, K, W, C, keep_prob);
     if (st != H2GCN_OK) return st;
     if (n_rows == 0) return H2GCN_OK;
@@ -745,7 +747,7 @@ int dropout_dense_forward(const TX* X, int64_t ldx, int64_t n_rows, int32_t K, c
     if (!workspace || workspace_bytes < s.total || ((uintptr_t)workspace & 15u))
         return fail(H2GCN_ERR_INVALID_ARGUMENT, "dropout_dense: workspace of %zu bytes (16-byte aligned) needed, got %zu", s.total, workspace_bytes);
     hipStream_t stream = (hipStream_t)stream_v;
-    if (small_operand(n_rows, K, C)) {   // latency-bound operand: one plain kernel, no packing
+    if (small_operand(ROWS ? x_rows : n_rows, K, C)) {   // latency-bound operand: one plain kernel, no packing
         const int64_t rows_per_block = (int64_t)(kThreads / 64) * kSmallRowsPerWave;
         const unsigned blocks = (unsigned)((n_rows + rows_per_block - 1) / rows_per_block);
         const size_t lds = small_lds_bytes(K, C);
@@ -778,7 +780,7 @@ int dropout_dense_forward(const TX* X, int64_t ldx, int64_t n_rows, int32_t K, c
 template <typename TX, typename TD, bool ROWS = false>
 int dropout_dense_backward(const TX* X, int64_t ldx, int64_t n_rows, int32_t K, const float* W, int32_t C, const float* G, int64_t ldg,
                            float keep_prob, uint64_t seed, const int64_t* step_dev, TD* dX, int64_t lddx, float* dW, void* workspace,
-                           size_t workspace_bytes, void* stream_v, const int32_t* rows = nullptr) {
+                           size_t workspace_bytes, void* stream_v, const int32_t* rows = nullptr, int64_t x_rows = -1) {
     int st = check_common(X, ldx, n_rows, K, W, C, keep_prob);
     if (st != H2GCN_OK) return st;
     if (!G && n_rows > 0) return fail(H2GCN_ERR_INVALID_ARGUMENT, "dropout_dense_backward: G is NULL");
@@ -794,7 +796,7 @@ int dropout_dense_backward(const TX* X, int64_t ldx, int64_t n_rows, int32_t K, 
         if (dW) H2GCN_HIP_TRY(hipMemsetAsync(dW, 0, (size_t)K * C * 4, stream));
         return H2GCN_OK;
     }
-    if (dX && small_operand(n_rows, K, C)) {   // latency-bound operand (see small_fwd_kernel); dW below, on the matrix cores
+    if (dX && small_operand(ROWS ? x_rows : n_rows, K, C)) {   // latency-bound operand (see small_fwd_kernel); dW below, on the matrix cores
         const int64_t total = n_rows * ((K + 3) / 4);
         const unsigned blocks = (unsigned)std::min<int64_t>((total + kThreads - 1) / kThreads, 2 * (int64_t)cu_count());   // W^T is staged once per workgroup
         const size_t lds = small_lds_bytes(K, C);

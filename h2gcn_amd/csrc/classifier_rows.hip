@@ -32,7 +32,7 @@ int h2gcn_dropout_dense_rows_f32(const float* X, int64_t ldx, int64_t n_rows, in
     if (st != H2GCN_OK) return st;
     if (!Z && n_sel > 0) return fail(H2GCN_ERR_INVALID_ARGUMENT, "%s: Z_dev is NULL", fn);
     return dropout_dense_forward<float, true>(X, ldx, n_sel, K, W, C, bias, keep_prob, seed, step_dev, Z, ldz, workspace, workspace_bytes, stream_v,
-                                              rows);
+                                              rows, n_rows);
 }
 
 int h2gcn_dropout_dense_rows_bf16(const uint16_t* X, int64_t ldx, int64_t n_rows, int32_t K, const float* W, int32_t C, const float* bias,
@@ -44,7 +44,7 @@ int h2gcn_dropout_dense_rows_bf16(const uint16_t* X, int64_t ldx, int64_t n_rows
     if (!Z && n_sel > 0) return fail(H2GCN_ERR_INVALID_ARGUMENT, "%s: Z_dev is NULL", fn);
     if ((st = check_bf16_array(fn, "X_dev", X, "ldx", ldx)) != H2GCN_OK) return st;
     return dropout_dense_forward<bf16, true>(reinterpret_cast<const bf16*>(X), ldx, n_sel, K, W, C, bias, keep_prob, seed, step_dev, Z, ldz, workspace,
-                                             workspace_bytes, stream_v, rows);
+                                             workspace_bytes, stream_v, rows, n_rows);
 }
 
 int h2gcn_dropout_dense_backward_rows_f32(const float* X, int64_t ldx, int64_t n_rows, int32_t K, const float* W, int32_t C, const float* G,
@@ -56,7 +56,7 @@ int h2gcn_dropout_dense_backward_rows_f32(const float* X, int64_t ldx, int64_t n
     if (st != H2GCN_OK) return st;
     if (!G && n_sel > 0) return fail(H2GCN_ERR_INVALID_ARGUMENT, "%s: G_dev is NULL", fn);
     return dropout_dense_backward<float, float, true>(X, ldx, n_sel, K, W, C, G, ldg, keep_prob, seed, step_dev, dX, lddx, dW, workspace,
-                                                      workspace_bytes, stream_v, rows);
+                                                      workspace_bytes, stream_v, rows, n_rows);
 }
 
 int h2gcn_dropout_dense_backward_rows_bf16(const uint16_t* X, int64_t ldx, int64_t n_rows, int32_t K, const float* W, int32_t C, const float* G,
@@ -74,10 +74,10 @@ int h2gcn_dropout_dense_backward_rows_bf16(const uint16_t* X, int64_t ldx, int64
     if (dx_dtype == H2GCN_DTYPE_BF16) {
         if (dX && (st = check_bf16_array(fn, "dX_dev", dX, "lddx", lddx)) != H2GCN_OK) return st;
         return dropout_dense_backward<bf16, bf16, true>(Xb, ldx, n_sel, K, W, C, G, ldg, keep_prob, seed, step_dev, static_cast<bf16*>(dX), lddx, dW,
-                                                        workspace, workspace_bytes, stream_v, rows);
+                                                        workspace, workspace_bytes, stream_v, rows, n_rows);
     }
     return dropout_dense_backward<bf16, float, true>(Xb, ldx, n_sel, K, W, C, G, ldg, keep_prob, seed, step_dev, static_cast<float*>(dX), lddx, dW,
-                                                     workspace, workspace_bytes, stream_v, rows);
+                                                     workspace, workspace_bytes, stream_v, rows, n_rows);
 }
 
 }  // extern "C"

@@ -689,7 +689,9 @@ int h2gcn_dropout_dense_backward_bf16(const uint16_t* X_dev, int64_t ldx, int64_
  *   dX_c   bit-identical to rows rows_dev[] of the full call's dX when that call gets G_c scattered into a zero [n_rows, C] G
  *   dW     deterministic (fixed-order reduction over the list); equal to the full call's dW on the scattered G up to the
  *          summation tree over rows, not bit for bit
- * The small-operand rule (h2gcn_dropout_dense_small_rows) applies to n_sel, and the workspace is
+ * The small-operand rule (h2gcn_dropout_dense_small_rows) applies to n_rows, the row count of X -- a row-selected call runs the
+ * kernels the full call on the same X runs, however short the list is: the two kernel families sum in different orders, and the
+ * bit identities above hold between calls of one family only.  The workspace is
  * h2gcn_dropout_dense_workspace_bytes(n_sel, K, C).  Arguments are validated before the device is touched -- a negative
  * n_sel or n_rows, n_sel > n_rows, a NULL rows_dev with n_sel > 0, a NULL operand and the layout rules of the full calls give
  * H2GCN_ERR_INVALID_ARGUMENT with a message that names the argument.  hipGraph capture: no condition (nothing is allocated,

@@ -26,7 +26,7 @@ SEED, STEP = 0x1234_5678_9ABC, 41
 @pytest.fixture(autouse=True, params=["matrix-core kernels", "small-operand kernels where they apply"])
 def _kernel_family(request):
     """Every test runs with the small-operand kernels switched off (h2gcn_dropout_dense_small_rows(0)) and with the shipped
-    rule, which the row-selected calls apply to n_sel."""
+    rule, which the row-selected calls apply to n_rows, as the full calls they are compared with do."""
     from h2gcn_amd import _capi
     L = _capi.lib()
     old = L.h2gcn_dropout_dense_small_rows(0 if request.param.startswith("matrix") else 12288)

@@ -242,3 +242,100 @@ def test_bench_checksum_constants_come_from_the_oracle():
     ck, nnz = fs.oracle_checksum("arxiv", block_rows=60_000)       # three row blocks: the sum does not depend on the blocking
     assert ck == bench.N1_CHECKSUMS[("arxiv", 128)]
     assert nnz == [1203951, 1205200]
+
+
+def test_kept_fraction_at_every_keep_value_and_step_of_the_sweep():
+    """Kept fraction of a [300, 130] mask (N = 39 000 elements) within 5 binomial standard deviations of the field threshold
+    over the field range, thr / 2^bits -- at thresholds next to both ends of both field widths and at steps whose high word is
+    set (measured: at most 2.6 sigma)."""
+    import classifier_driver as cd
+
+    n, k = 300, 130
+    for keep in cd.KEEPS + (0.5, 0.9):
+        thr16 = int(float(np.float32(keep)) * 65536.0)
+        p = (thr16 // 256) / 256 if thr16 % 256 == 0 else thr16 / 65536
+        sigma = np.sqrt(p * (1 - p) / (n * k))
+        for step in cd.STEPS:
+            got = oc.keep_mask(n, k, keep, cd.SEED, step).mean()
+            assert abs(got - p) <= 5 * sigma, (keep, step, (got - p) / sigma)
+
+
+_U32 = 0xFFFFFFFF
+
+
+def _scalar_keep(row, col, k, keep_prob, seed, step):
+    """keep(row, col) in Python integers, written from the description in include/h2gcn_hip.h (not from oracle.classifier)."""
+    def mix(h):
+        h ^= h >> 16
+        h = h * 0x7FEB352D & _U32
+        h ^= h >> 15
+        h = h * 0x846CA68B & _U32
+        return h ^ h >> 16
+
+    key0 = mix(seed & _U32 ^ mix((step & _U32) + 0x9E3779B9 & _U32))
+    key1 = mix(seed >> 32 & _U32 ^ step >> 32 & _U32 ^ key0 ^ 0x85EBCA6B)
+    gid = (row * ((k + 3) // 4) + col // 4) & (2 ** 64 - 1)
+    lo, hi = gid & _U32, gid >> 32
+    h = lo ^ (hi << 16 & _U32 | hi >> 16) ^ key0
+    h ^= h >> 16
+    h = h * 0x7FEB352D & _U32
+    h ^= key1
+    h ^= h >> 15
+    h = h * 0x846CA68B & _U32
+    w0 = h ^ h >> 16
+    t = int(float(np.float32(keep_prob)) * 65536.0)          # T = floor(keep_prob * 65536), keep_prob an fp32
+    if t % 256 == 0:
+        return (w0 >> 8 * (col % 4) & 0xFF) < t // 256
+    w1 = mix(w0 ^ 0x85EBCA6B)
+    return (w0 & 0xFFFF, w0 >> 16, w1 & 0xFFFF, w1 >> 16)[col % 4] < t
+
+
+def test_mask_generator_against_a_scalar_restatement_of_the_header():
+    """oracle.classifier.keep_mask (numpy, what the GPU suites hold the device to) == the generator of include/h2gcn_hip.h
+    spelled out with Python integers, element by element: both field widths, every key of the sweep's ends, widths with a
+    partial last group, and rows whose group ids need more than 32 bits (which no device test can afford to reach)."""
+    import classifier_driver as cd
+
+    k = 130                                                   # 33 groups per row, the last one partial
+    row0s = (0, 5, 2 ** 32 // 33 - 1, 2 ** 32 // 33 + 7, 2 ** 33 + 12345, (2 ** 48 + 9) // 33, 2 ** 57)
+    cols = (0, 1, 2, 3, 4, 63, 64, 127, 128, 129)
+    keys = [(cd.SEED, cd.STEP), (0, 0), (2 ** 64 - 1, 2 ** 63 - 1), (0x1234 << 32, (7 << 40) + 3), (0x9ABC, 2 ** 32 + 41)]
+    n_checked = n_far = 0
+    for keep in (0.5, 0.9, 1 / 256, 65534 / 65536, 0.999, 255 / 256):
+        for seed, step in keys:
+            for row0 in row0s:
+                m = oc.keep_mask(3, k, keep, seed, step, row0=row0)
+                for r in range(3):
+                    for col in cols:
+                        assert bool(m[r, col]) == _scalar_keep(row0 + r, col, k, keep, seed, step), (keep, seed, step, row0 + r, col)
+                        n_checked += 1
+                        n_far += (row0 + r) * 33 >= 2 ** 32
+    assert n_checked >= 5000 and n_far >= 2000
+    # the two high words matter in the scalar form as well
+    a = [_scalar_keep(r, c, k, 0.5, cd.SEED, 41) for r in range(40) for c in range(k)]
+    assert a != [_scalar_keep(r, c, k, 0.5, cd.SEED, 2 ** 32 + 41) for r in range(40) for c in range(k)]
+    assert a != [_scalar_keep(r, c, k, 0.5, cd.SEED ^ 1 << 40, 41) for r in range(40) for c in range(k)]
+
+
+def test_sweep_driver_reference_is_the_oracle():
+    """tests/classifier_driver.reference (one mask, every product once, any row subset) == oracle.classifier.dropout_dense /
+    dropout_dense_grad: exactly for the full matrix, and for a row subset the oracle on G scattered into a zero matrix."""
+    import classifier_driver as cd
+
+    for keep, bias in ((0.5, True), (0.9, False), (1.0, True)):
+        inp = cd.make_inputs(57, 13, 5, data_seed=3)
+        b = inp.b if bias else None
+        ref = cd.reference(inp.x32, inp.w, b, inp.g, keep, cd.SEED, cd.STEP)
+        assert np.array_equal(ref.z, oc.dropout_dense(inp.x32, inp.w, b, keep, cd.SEED, cd.STEP))
+        dx, dw, _ = oc.dropout_dense_grad(inp.x32, inp.w, inp.g, keep, cd.SEED, cd.STEP)
+        assert np.array_equal(ref.dx, dx) and np.array_equal(ref.dw(slice(0, 57))[0], dw)
+        assert np.array_equal(ref.mask, oc.keep_mask(57, 13, keep, cd.SEED, cd.STEP))
+        rows = cd.selection(57, 19, np.random.default_rng(0))
+        g0 = np.zeros_like(inp.g)
+        g0[rows] = inp.g[rows]
+        dx0, dw0, _ = oc.dropout_dense_grad(inp.x32, inp.w, g0, keep, cd.SEED, cd.STEP)
+        assert np.array_equal(ref.dx[rows], dx0[rows]) and np.allclose(ref.dw(rows)[0], dw0, rtol=0, atol=1e-13)
+    # the bf16 helpers: round to nearest even, ties included, and the exact widening
+    v = np.array([1.0, 1.0 + 2.0 ** -8, 1.0 + 3 * 2.0 ** -8, -0.3, 1e-30], np.float32)
+    assert list(cd.bf16_bits(v)[:3]) == [0x3F80, 0x3F80, 0x3F82]
+    assert np.array_equal(cd.bf16_widen(cd.bf16_bits(v))[:3], np.array([1.0, 1.0, 1.0 + 2.0 ** -6], np.float32))
