@@ -545,7 +545,11 @@ int h2gcn_edge_scores_backward_hops_f32(const h2gcn_plan_t* plan, uint32_t hop_m
  *                     SUB = ring_1 .. ring_{k-1}, sub_diag = 1
  *   merged group "0,1" of --adj_nhood (getTensors, :560-572):  no F, ADD = {ring_1}, add_diag = 1
  *
- * All patterns are n x n CSR (int64 rowptr, int32 colidx ascending, no values); outputs have ascending columns.
+ * All patterns are n x n CSR (int64 rowptr, int32 colidx, no values), every column in [0, n); outputs have strictly
+ * ascending columns.  What a row of each operand may hold: SUB_q and F rows must be strictly ascending (rows with more
+ * than 131072 columns to choose from binary-search the SUB rows, and a repeated frontier node would count its A-row twice
+ * towards the row's candidate count); ADD_p and A rows are taken as they are -- any order, repeated columns allowed -- since
+ * candidates are only ever united.  A SUB column that is no candidate is ignored.  Nothing of this is checked.
  * Two passes: h2gcn_ring_count writes out_rowptr[0..n] (row pointers of the result) and returns the number of
  * nonzeros (it synchronises the stream -- the caller has to allocate out_colidx); h2gcn_ring_fill, called with the
  * SAME inputs, writes the columns.  `scratch` is h2gcn_ring_scratch_bytes(n) bytes of device memory.
