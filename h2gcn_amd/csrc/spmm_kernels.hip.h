@@ -725,6 +725,11 @@ __device__ __forceinline__ void store_out(const P& p, TD* row, int col0, int eco
 // hops are short; the partials run on across the hops exactly as the wave walk's accumulators do.
 // The arithmetic is the canonical tree of the header comment (a group keeps P[j mod 4] in registers, combined as
 // (P0 + P1) + (P2 + P3)), so which class served a segment can never be seen in the result.
+// Valid ranges (launch() in h2gcn_capi.hip keeps to them, overrides included): spw = p.short_per_wave in 4, 8 ... 64 -- lane e
+// parks entry e, so spw <= kWave, and the host makes it a multiple of 4 >= G, so that only a wave's LAST round can be partial;
+// NS = 1 forward, NS = n_sel <= kShortSumHops in SUM mode (rows of s_seg); every listed segment holds at most
+// min(kShortMax, LPR) nonzeros (6 bits of s_seg, one index fetch per lane group).  A workgroup index past the last list
+// workgroup -- the padding of the chunk-major order, the tail of the last group of 8 -- finds left <= 0 and returns.
 template <typename TS, typename TD, int VEC, int LPR, bool SUM, bool OFF32, bool EPI, int PD>
 __device__ __forceinline__ void short_list_blocks(const LaunchParams& p, int64_t sblock, int lane, int wave, int64_t lane_off0,
                                                   int64_t src_col_begin, int lcol, int ecol,
@@ -838,6 +843,9 @@ __device__ __forceinline__ void short_list_blocks(const LaunchParams& p, int64_t
 // Forward: an entry is a (row, hop) segment of the hop the workgroup's list belongs to; SUM: a row that is neither listed
 // as short nor owned by the long path, all selected hops' segments accumulated into one output row.  Lane j*NS + s fetches
 // the row pointers of entry j, hop s; the walk itself is accumulate_segment, i.e. the tile walk's arithmetic.
+// Valid ranges: mpw = p.med_per_wave >= 1 and NS = SUM ? n_sel : 1 with mpw * NS <= kWave (one lane per row-pointer pair):
+// launch() gives 1 ... 8 forward, 1 ... min(4, kWave / n_sel) in SUM mode, where lists exist for n_sel <= kShortSumHops only.
+// Segment lengths are anything below long_row_threshold (64-neighbour chunks); tested in tests/test_spmm_classes_sweep_gpu.py.
 template <typename TS, typename TD, int VEC, int LPR, bool SUM, bool OFF32, bool EPI, int MAXB>
 __device__ __forceinline__ void medium_list_blocks(const LaunchParams& p, int64_t mblock, int lane, int wave, int64_t lane_off0,
                                                    int64_t src_col_begin, int lcol, int ecol) {
