@@ -47,6 +47,7 @@ EXPORTED_SYMBOLS = (
     "h2gcn_plan_info",
     "h2gcn_plan_set_values",
     "h2gcn_plan_transpose_sharing",
+    "h2gcn_plan_row_constant",
     "h2gcn_plan_device_bytes",
     "h2gcn_spmm_hops_f32",
     "h2gcn_spmm_hops_T_f32",
@@ -200,6 +201,9 @@ def lib() -> C.CDLL:
         L.h2gcn_plan_transpose_sharing.argtypes = [C.c_void_p, C.c_int]
         L.h2gcn_plan_device_bytes.restype = C.c_size_t
         L.h2gcn_plan_device_bytes.argtypes = [C.c_void_p]
+    if hasattr(L, "h2gcn_plan_row_constant"):   # (row-constant hops, added within ABI 5; absent from parent builds loaded for A/B runs)
+        L.h2gcn_plan_row_constant.restype = C.c_int
+        L.h2gcn_plan_row_constant.argtypes = [C.c_void_p, C.c_int]
     L.h2gcn_spmm_workspace_bytes.restype = C.c_size_t
     L.h2gcn_spmm_workspace_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_int32]
     L.h2gcn_spmm_hops_opts_f32.restype = C.c_int

@@ -102,6 +102,12 @@ struct h2gcn_plan {
     // forward arrays (borrowed: never in `owned`); 2 -- its vals too
     std::vector<int> sharing;
     size_t transpose_bytes = 0;   // device bytes behind `owned`
+    // row-constant forward operands (every stored value of a row of A_k carries the same bits; established by row_values_kernel
+    // at creation, cleared for good by h2gcn_plan_set_values): the row's value per row, max(n_rows, 1) floats -- what the ROWVAL
+    // kernels read instead of the value stream.  An array may outlive the state (a set_values call inside a stream capture
+    // cannot free it); device_bytes counts what is allocated.
+    std::vector<DeviceBuf> rowval;
+    std::vector<char> row_const;
     // long-segment lists are specific to a hop selection; built on first use, then cached
     mutable std::mutex mu;
     mutable std::map<uint64_t, LongList> long_cache;  // key = mask | (adjoint << 32)
@@ -120,6 +126,24 @@ __global__ void check_colidx_kernel(const int32_t* __restrict__ colidx, int64_t 
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nnz; i += (int64_t)gridDim.x * blockDim.x) {
         const int32_t c = colidx[i];
         bad |= (c < 0) | ((int64_t)c >= n_cols);
+    }
+    if (bad) atomicOr(flag, 1);
+}
+
+// one-time detection of plan_create, per hop: rowval[r] = the bits of row r's first stored value (0 for an empty row), and the
+// flag is raised when any stored value differs IN ITS BITS from its row's first one (+0.0 next to -0.0 differs, two NaNs with
+// one payload do not).  A wave per row, rows taken grid-stride; one read of vals.  rowptr has passed check_rowptr.
+__global__ void row_values_kernel(const int64_t* __restrict__ rowptr, const float* __restrict__ vals, int64_t n_rows,
+                                  float* __restrict__ rowval, int* flag) {
+    const int lane = threadIdx.x & (kWave - 1);
+    const int64_t n_waves = ((int64_t)gridDim.x * blockDim.x) / kWave;
+    const uint32_t* v = reinterpret_cast<const uint32_t*>(vals);
+    int bad = 0;
+    for (int64_t r = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / kWave; r < n_rows; r += n_waves) {
+        const int64_t b = rowptr[r], e = rowptr[r + 1];
+        const uint32_t first = b < e ? v[b] : 0u;
+        for (int64_t i = b + lane; i < e; i += kWave) bad |= v[i] != first;
+        if (lane == 0) reinterpret_cast<uint32_t*>(rowval)[r] = first;
     }
     if (bad) atomicOr(flag, 1);
 }
@@ -582,12 +606,22 @@ int launch(LaunchParams& p, const h2gcn_plan* plan, uint32_t mask, LaunchShape& 
     if (n_blocks <= 0) return H2GCN_OK;
     if (n_blocks > 0x7fffffffLL) return fail(H2GCN_ERR_INVALID_ARGUMENT, "grid too large (%lld blocks)", (long long)n_blocks);
     const dim3 grid((unsigned)n_blocks);
-    if (!src_bf16 && adjoint) launch_spmm<true, float, float>(p, sc, grid, stream);
-    else if (!src_bf16) launch_spmm<false, float, float>(p, sc, grid, stream);
-    else if (out_bf16 && adjoint) launch_spmm<true, bf16, bf16>(p, sc, grid, stream);
-    else if (out_bf16) launch_spmm<false, bf16, bf16>(p, sc, grid, stream);
-    else if (adjoint) launch_spmm<true, bf16, float>(p, sc, grid, stream);
-    else launch_spmm<false, bf16, float>(p, sc, grid, stream);
+    // forward launches that walk on the index window (plain walk of 64-column slices, plain store, fp32 output, at most
+    // kRingHops hops) leave the value stream unread when EVERY selected hop is row-constant: the ROWVAL instantiations
+    Schedule rv = sc;
+    rv.rowval = !adjoint && !out_bf16 && sc.exact && sc.slice == 64 && !sc.scalar128 && !sc.pipe && !sc.shortrow && !sc.lists &&
+                !sc.gen && p.n_sel <= kRingHops;
+    for (int k = 0, s = 0; rv.rowval && k < plan->n_hops; ++k) {
+        if (!(mask & (1u << k))) continue;
+        if (plan->row_const[(size_t)k] && plan->rowval[(size_t)k].p) p.rowval[s++] = (const float*)plan->rowval[(size_t)k].p;
+        else rv.rowval = false;
+    }
+    if (!src_bf16 && adjoint) launch_spmm<true, float, float>(p, rv, grid, stream);
+    else if (!src_bf16) launch_spmm<false, float, float>(p, rv, grid, stream);
+    else if (out_bf16 && adjoint) launch_spmm<true, bf16, bf16>(p, rv, grid, stream);
+    else if (out_bf16) launch_spmm<false, bf16, bf16>(p, rv, grid, stream);
+    else if (adjoint) launch_spmm<true, bf16, float>(p, rv, grid, stream);
+    else launch_spmm<false, bf16, float>(p, rv, grid, stream);
     H2GCN_HIP_TRY(hipGetLastError());
     return H2GCN_OK;
 }
@@ -766,6 +800,8 @@ int h2gcn_plan_create(int n_hops, int64_t n_rows, int64_t n_cols, const int64_t*
         DeviceBuf flag;
         H2GCN_HIP_TRY(hipMalloc(&flag.p, sizeof(int)));
         H2GCN_HIP_TRY(hipMemsetAsync(flag.p, 0, sizeof(int), stream));
+        plan->rowval.resize(n_hops);
+        plan->row_const.assign(n_hops, 0);
 
         std::vector<std::vector<int64_t>> h_rowptr(n_hops);
         for (int k = 0; k < n_hops; ++k) {
@@ -874,6 +910,34 @@ int h2gcn_plan_create(int n_hops, int64_t n_rows, int64_t n_cols, const int64_t*
             }
             plan->has_transpose = true;
         }
+        // row-constant detection (validates nothing, so H2GCN_PLAN_SKIP_VALIDATION does not skip it): one read of vals per hop,
+        // flag k raised when hop k is not row-constant.  It comes AFTER the transposed operands so that those sit where they sat
+        // before the row values existed (allocated in front of them, the row values moved the arrays of A_k^T, and the adjoint of
+        // the DRAM-resident shape -- the same kernel -- ran 0.3 % slower: profiles/r18_row_values_ab_parent_vs_this.txt).
+        {
+            DeviceBuf rc_flag;
+            H2GCN_HIP_TRY(hipMalloc(&rc_flag.p, (size_t)n_hops * sizeof(int)));
+            H2GCN_HIP_TRY(hipMemsetAsync(rc_flag.p, 0, (size_t)n_hops * sizeof(int), stream));
+            for (int k = 0; k < n_hops; ++k) {
+                const HopOperand& op = plan->fwd[k];
+                H2GCN_HIP_TRY(hipMalloc(&plan->rowval[k].p, (size_t)std::max<int64_t>(n_rows, 1) * sizeof(float)));
+                if (n_rows == 0) continue;
+                const unsigned blocks = (unsigned)std::min<int64_t>((n_rows + h2gcn::kWavesPerBlock - 1) / h2gcn::kWavesPerBlock, 8192);
+                hipLaunchKernelGGL(h2gcn::row_values_kernel, dim3(blocks), dim3(h2gcn::kBlock), 0, stream, op.rowptr, op.vals, n_rows,
+                                   (float*)plan->rowval[k].p, (int*)rc_flag.p + k);
+                H2GCN_HIP_TRY(hipGetLastError());
+            }
+            std::vector<int> h_rc((size_t)n_hops, 0);
+            H2GCN_HIP_TRY(hipMemcpyAsync(h_rc.data(), rc_flag.p, h_rc.size() * sizeof(int), hipMemcpyDeviceToHost, stream));
+            H2GCN_HIP_TRY(hipStreamSynchronize(stream));
+            for (int k = 0; k < n_hops; ++k) {
+                plan->row_const[k] = h_rc[k] ? 0 : 1;
+                if (!plan->row_const[k]) {
+                    (void)hipFree(plan->rowval[k].p);
+                    plan->rowval[k].p = nullptr;
+                }
+            }
+        }
         // build the long-segment lists of the common selection (all hops) now, so that launches with the default
         // hop mask never allocate -- they can be issued inside a hipGraph capture without a warm-up
         {
@@ -924,6 +988,18 @@ int h2gcn_plan_set_values(h2gcn_plan_t* plan, int hop, const float* vals_dev, vo
         H2GCN_HIP_TRY(hipGetLastError());
     }
     f.vals = vals_dev;
+    // the new values are whatever the caller writes: the hop is on the value stream from here on (no re-detection).  Its row
+    // values go with the first such call -- unless the stream is being captured, where nothing can be freed: then they stay
+    // allocated (and counted) until the plan is destroyed.  Later calls find nothing to do.
+    plan->row_const[(size_t)hop] = 0;
+    if (plan->rowval[(size_t)hop].p) {
+        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+        if (hipStreamIsCapturing((hipStream_t)stream_v, &cs) != hipSuccess) (void)hipGetLastError();
+        else if (cs == hipStreamCaptureStatusNone) {
+            (void)hipFree(plan->rowval[(size_t)hop].p);
+            plan->rowval[(size_t)hop].p = nullptr;
+        }
+    }
     return H2GCN_OK;
 }
 
@@ -945,10 +1021,18 @@ int h2gcn_plan_transpose_sharing(const h2gcn_plan_t* plan, int hop) {
     return plan->sharing[(size_t)hop];
 }
 
+int h2gcn_plan_row_constant(const h2gcn_plan_t* plan, int hop) {
+    if (!plan) return fail(H2GCN_ERR_INVALID_ARGUMENT, "plan is NULL");
+    if (hop < 0 || hop >= plan->n_hops) return fail(H2GCN_ERR_INVALID_ARGUMENT, "hop %d outside 0..%d", hop, plan->n_hops - 1);
+    return plan->row_const[(size_t)hop] ? 1 : 0;
+}
+
 size_t h2gcn_plan_device_bytes(const h2gcn_plan_t* plan) {
     if (!plan) return 0;
     std::lock_guard<std::mutex> lock(plan->mu);
     size_t bytes = plan->transpose_bytes;
+    for (const DeviceBuf& rv : plan->rowval)
+        if (rv.p) bytes += (size_t)std::max<int64_t>(plan->n_rows, 1) * sizeof(float);
     for (const auto& kv : plan->long_cache) bytes += (size_t)kv.second.n * sizeof(int64_t);
     for (const auto& kv : plan->class_cache)
         if (kv.second.built) bytes += (size_t)(kv.second.n_short + kv.second.n_med) * sizeof(int32_t);

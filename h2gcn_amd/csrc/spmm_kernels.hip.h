@@ -151,6 +151,9 @@ struct LaunchParams {
     int64_t med_end[H2GCN_MAX_HOPS];
     int64_t med_groups;
     int med_per_wave;
+    // ROWVAL kernels (forward launches whose selected hops are all row-constant, see h2gcn_plan_row_constant): the one value
+    // every stored entry of row r of selected hop s carries, rowval[s][r] (0 for an empty row); hop[s].vals is not read
+    const float* rowval[H2GCN_MAX_HOPS];
 };
 
 template <int VEC>
@@ -342,9 +345,13 @@ struct GatherAddr {
 // The cross-lane reads of (c, v) always run with the full wave active (ds_bpermute returns 0 for a source
 // lane that is masked off); only the gather itself is predicated, by `take` (false on lanes whose slot is
 // padding -- they must not touch src: 0 * Inf would poison the row).
-template <typename TS, int VEC, int LPR, int U, bool PREDICATED, bool OFF32, int PHASE = 0, int NP>
+// EP (exact padding, the ROWVAL kernels): a padding slot multiplies by -0.0 instead of +0.0.  fma(-0.0, +0.0, p) is p for
+// EVERY p, while fma(+0.0, +0.0, p) turns a partial that has underflowed to -0.0 into +0.0 -- a step the canonical tree does
+// not have.  (The kernels on the value stream keep +0.0, and with it that one deviation in the sign of a zero: they are the
+// code they were.)
+template <typename TS, int VEC, int LPR, int U, bool PREDICATED, bool OFF32, int PHASE = 0, int NP, bool EP = false>
 __device__ __forceinline__ void gather_batch(int c, float v, int t, int g, const GatherAddr<OFF32>& addr, bool take,
-                                             float (&acc)[NP][VEC]) {
+                                             float (&acc)[NP][VEC], std::integral_constant<bool, EP> = {}) {
     constexpr int G = kWave / LPR;
     typename LoadT<TS, VEC>::type x[U];
     float w[U];
@@ -365,7 +372,7 @@ __device__ __forceinline__ void gather_batch(int c, float v, int t, int g, const
             if (take) {
                 x[u] = load_vec<TS, VEC>(p);
             } else {
-                w[u] = 0.f;
+                w[u] = EP ? -0.f : 0.f;
                 x[u] = zero_load<TS, VEC>();
             }
         } else {
@@ -389,13 +396,21 @@ __device__ __forceinline__ void load_chunk(const int32_t* __restrict__ colidx, c
     }
 }
 
+// ... of a row-constant hop (ROWVAL kernels): the column id only; every neighbour carries the row's value `w`
+__device__ __forceinline__ void load_chunk_ids(const int32_t* __restrict__ colidx, float w, int64_t base, int64_t seg_end, int lane,
+                                               int& c, float& v) {
+    c = 0;
+    v = w;
+    if (base + lane < seg_end) c = __builtin_nontemporal_load(colidx + base + lane);
+}
+
 // All gathers + multiply-adds of one chunk of n (<= 64) neighbours held lane-wise in (c, v).
 // MAXB: deepest load batch (8 in the bandwidth kernels; 4 where register pressure matters more than the last few
 // percent on long segments -- the fallback walk of the short-row kernels).  The batch depth only re-times loads: the
 // accumulation order, hence the bits, do not depend on it.
-template <typename TS, int VEC, int LPR, bool MASKED, bool OFF32, int MAXB = H2GCN_MAIN_MAXB, int NP>
+template <typename TS, int VEC, int LPR, bool MASKED, bool OFF32, int MAXB = H2GCN_MAIN_MAXB, int NP, bool EP = false>
 __device__ __forceinline__ void process_chunk(int c, float v, int n, int g, const GatherAddr<OFF32>& addr,
-                                              bool lane_active, float (&acc)[NP][VEC]) {
+                                              bool lane_active, float (&acc)[NP][VEC], std::integral_constant<bool, EP> ep = {}) {
     constexpr int G = kWave / LPR;
     const int full = n / G;  // steps in which every lane group has a neighbour
     int t = 0;               // batches of 8 / 4 start at t % 4 == 0: partial phase 0
@@ -416,18 +431,18 @@ __device__ __forceinline__ void process_chunk(int c, float v, int n, int g, cons
         if (t + 1 <= full) {
             gather_batch<TS, VEC, LPR, 1, MASKED, OFF32, 2 % NP>(c, v, t, g, addr, lane_active, acc);
             if constexpr (G > 1)
-                if (rem > 0) gather_batch<TS, VEC, LPR, 1, true, OFF32, 3 % NP>(c, v, full, g, addr, lane_active && g < rem, acc);
+                if (rem > 0) gather_batch<TS, VEC, LPR, 1, true, OFF32, 3 % NP>(c, v, full, g, addr, lane_active && g < rem, acc, ep);
         } else {
             if constexpr (G > 1)
-                if (rem > 0) gather_batch<TS, VEC, LPR, 1, true, OFF32, 2 % NP>(c, v, full, g, addr, lane_active && g < rem, acc);
+                if (rem > 0) gather_batch<TS, VEC, LPR, 1, true, OFF32, 2 % NP>(c, v, full, g, addr, lane_active && g < rem, acc, ep);
         }
     } else if (t + 1 <= full) {
         gather_batch<TS, VEC, LPR, 1, MASKED, OFF32>(c, v, t, g, addr, lane_active, acc);
         if constexpr (G > 1)
-            if (rem > 0) gather_batch<TS, VEC, LPR, 1, true, OFF32, 1 % NP>(c, v, full, g, addr, lane_active && g < rem, acc);
+            if (rem > 0) gather_batch<TS, VEC, LPR, 1, true, OFF32, 1 % NP>(c, v, full, g, addr, lane_active && g < rem, acc, ep);
     } else {
         if constexpr (G > 1)
-            if (rem > 0) gather_batch<TS, VEC, LPR, 1, true, OFF32>(c, v, full, g, addr, lane_active && g < rem, acc);
+            if (rem > 0) gather_batch<TS, VEC, LPR, 1, true, OFF32>(c, v, full, g, addr, lane_active && g < rem, acc, ep);
     }
 }
 
@@ -444,6 +459,7 @@ typedef uint32_t u32x4 __attribute__((ext_vector_type(4), aligned(4)));
 struct WindowChunk {
     const uint32_t* ring;  // this (wave, hop)'s ring: the pair of element e at dwords 2 * (e % kRingCap)
     uint32_t e_lane;       // element index (low bits) of neighbour g of the chunk, g = this lane's group
+    static constexpr bool kExactPadding = false;   // (see gather_batch, EP)
     template <int G>
     __device__ __forceinline__ void fetch(int step, int g, int& cj, float& w) const {
         static_assert(G > 1, "the one-neighbour-per-load geometry keeps v_readlane");
@@ -453,11 +469,26 @@ struct WindowChunk {
     }
 };
 
+// ... of a ROWVAL kernel: the ring holds column ids only (element e at dword e % kRingCap, one ds_read_b32 per step); the
+// value is the row's, wave-uniform
+struct WindowChunkIds {
+    const uint32_t* ring;
+    uint32_t e_lane;
+    float w;
+    static constexpr bool kExactPadding = true;
+    template <int G>
+    __device__ __forceinline__ void fetch(int step, int g, int& cj, float& wj) const {
+        static_assert(G > 1, "the one-neighbour-per-load geometry keeps v_readlane");
+        cj = (int)ring[(e_lane + (uint32_t)(step * G)) & (kRingCap - 1)];
+        wj = w;
+    }
+};
+
 // gather_batch with the neighbours taken from the window: same steps, same partials.  (A function of its own, and a
 // process_chunk of its own below, rather than a chunk-source parameter of gather_batch: handing (c, v) over inside a struct
 // re-schedules the index loads of every kernel that shares gather_batch -- the in-tile short-row and list-driven ones too.)
-template <typename TS, int VEC, int LPR, int U, bool PREDICATED, bool OFF32, int PHASE = 0, int NP>
-__device__ __forceinline__ void gather_batch_window(const WindowChunk& ch, int t, int g, const GatherAddr<OFF32>& addr, bool take,
+template <typename TS, int VEC, int LPR, int U, bool PREDICATED, bool OFF32, int PHASE = 0, typename CH, int NP>
+__device__ __forceinline__ void gather_batch_window(const CH& ch, int t, int g, const GatherAddr<OFF32>& addr, bool take,
                                              float (&acc)[NP][VEC]) {
     constexpr int G = kWave / LPR;
     typename LoadT<TS, VEC>::type x[U];
@@ -471,7 +502,7 @@ __device__ __forceinline__ void gather_batch_window(const WindowChunk& ch, int t
             if (take) {
                 x[u] = load_vec<TS, VEC>(p);
             } else {
-                w[u] = 0.f;
+                w[u] = CH::kExactPadding ? -0.f : 0.f;
                 x[u] = zero_load<TS, VEC>();
             }
         } else {
@@ -488,8 +519,8 @@ __device__ __forceinline__ void gather_batch_window(const WindowChunk& ch, int t
 // MAXB: deepest load batch (8 in the bandwidth kernels; 4 where register pressure matters more than the last few
 // percent on long segments -- the fallback walk of the short-row kernels).  The batch depth only re-times loads: the
 // accumulation order, hence the bits, do not depend on it.
-template <typename TS, int VEC, int LPR, bool MASKED, bool OFF32, int MAXB = H2GCN_MAIN_MAXB, int NP>
-__device__ __forceinline__ void process_chunk_window(const WindowChunk& ch, int n, int g, const GatherAddr<OFF32>& addr,
+template <typename TS, int VEC, int LPR, bool MASKED, bool OFF32, int MAXB = H2GCN_MAIN_MAXB, typename CH, int NP>
+__device__ __forceinline__ void process_chunk_window(const CH& ch, int n, int g, const GatherAddr<OFF32>& addr,
                                               bool lane_active, float (&acc)[NP][VEC]) {
     constexpr int G = kWave / LPR;
     const int full = n / G;  // steps in which every lane group has a neighbour
@@ -529,20 +560,22 @@ __device__ __forceinline__ void process_chunk_window(const WindowChunk& ch, int 
 // Accumulate sum_j val_j * src[col_j, :] over the nonzeros [seg_begin, seg_end) of one CSR row, taking the
 // 64-wide chunks chunk0, chunk0+chunk_step, ... (regular path: all of them; long path: this wave's share).
 // Each lane group accumulates its neighbours in ascending order into acc.
-template <typename TS, int VEC, int LPR, bool MASKED, bool OFF32, int MAXB = H2GCN_MAIN_MAXB, int NP>
+// ROWVAL: the segment belongs to a row-constant hop -- `vals` is not read, every neighbour carries `w`.
+template <typename TS, int VEC, int LPR, bool MASKED, bool OFF32, int MAXB = H2GCN_MAIN_MAXB, bool ROWVAL = false, int NP>
 __device__ __forceinline__ void accumulate_segment(const int32_t* __restrict__ colidx,
                                                    const float* __restrict__ vals, int64_t seg_begin,
                                                    int64_t seg_end, int chunk0, int chunk_step,
                                                    const GatherAddr<OFF32>& addr, int lane, bool lane_active,
-                                                   float (&acc)[NP][VEC]) {
+                                                   float (&acc)[NP][VEC], float w = 0.f) {
     const int g = lane / LPR;
     for (int64_t base = seg_begin + (int64_t)chunk0 * kWave; base < seg_end; base += (int64_t)chunk_step * kWave) {
         const int64_t left = seg_end - base;
         const int n = left < kWave ? (int)left : kWave;
         int c;
         float v;
-        load_chunk(colidx, vals, base, seg_end, lane, c, v);
-        process_chunk<TS, VEC, LPR, MASKED, OFF32, MAXB>(c, v, n, g, addr, lane_active, acc);
+        if constexpr (ROWVAL) load_chunk_ids(colidx, w, base, seg_end, lane, c, v);
+        else load_chunk(colidx, vals, base, seg_end, lane, c, v);
+        process_chunk<TS, VEC, LPR, MASKED, OFF32, MAXB>(c, v, n, g, addr, lane_active, acc, std::integral_constant<bool, ROWVAL>{});
     }
 }
 
@@ -1095,12 +1128,18 @@ __device__ __forceinline__ T pick(int s, T of_hop0, T of_hop1) { return s ? of_h
 // b + 64 > j*128 - max(m); the slots it overwrites held elements below j*128 - 128 - min(m) < b, which are consumed.
 // Segments of the long path (and, in SUM mode, every segment of a row that has one) are stepped over by whole blocks.
 // The arithmetic is process_chunk's: same neighbours, same order, same tree.
-template <typename TS, typename TD, int VEC, int LPR, bool SUM, bool OFF32, bool EPI, int MAXB>
+// ROWVAL (every selected hop row-constant): the value stream is not read at all.  A block is kRingBlock column ids, fetched
+// by lanes 0-31 (lanes 32-63 issue no load), the ring holds ids only (WindowChunkIds), and m is the column array's
+// misalignment alone (min(m) = max(m): the ring-safety argument above holds as it stands).  The row's value comes in `rv`
+// (lane l: row l % (rpw+1) of hop l / (rpw+1), as the row pointers in `rp`) and is made wave-uniform per segment; the
+// multiply-adds take the operands the value stream would have delivered, so the bits are the same.
+template <typename TS, typename TD, int VEC, int LPR, bool SUM, bool OFF32, bool EPI, int MAXB, bool ROWVAL = false>
 __device__ __forceinline__ void window_tile_walk(const LaunchParams& p, int lane, int rpw, int64_t row0, int rows_here, int64_t rp,
                                                  int64_t lane_off0, int64_t src_col_begin, int lcol, int ecol,
-                                                 uint32_t (&ring)[kRingHops][2 * kRingCap]) {
+                                                 uint32_t (&ring)[kRingHops][(ROWVAL ? 1 : 2) * kRingCap], float rv = 0.f) {
     using off_t = typename std::conditional<OFF32, uint32_t, int64_t>::type;
     constexpr int NP = Tree<LPR>::NP;
+    static_assert(!ROWVAL || !SUM, "row-constant values exist for forward operands only");
     static_assert(kRingBlock == 4 * (kWave / 2) && kRingCap >= 2 * kRingBlock && kWave + 31 < kRingBlock, "ring safety (see above)");
     static_assert(kRingHops == 2, "hop state is selected with pick(s, hop 0's, hop 1's)");
     const int g = lane / LPR;
@@ -1119,8 +1158,8 @@ __device__ __forceinline__ void window_tile_walk(const LaunchParams& p, int lane
         if (lane >= l0) rel = (int)(rp - org);
         len = __builtin_amdgcn_readlane(rel, l0 + rows_here);
         col = p.hop[s].colidx + org;
-        val = p.hop[s].vals + org;
-        const int mc = misalign(col), mv = misalign(val);
+        if constexpr (!ROWVAL) val = p.hop[s].vals + org;
+        const int mc = misalign(col), mv = ROWVAL ? mc : misalign(val);
         mmin = min(mc, mv);
         mmax = max(mc, mv);
     };
@@ -1128,12 +1167,13 @@ __device__ __forceinline__ void window_tile_walk(const LaunchParams& p, int lane
     if (n_sel > 1) init_hop(1, col1, val1, len1, mmin1, mmax1);
     auto bound = [&](int l) __attribute__((always_inline)) { return __builtin_amdgcn_readlane(rel, l); };
     auto lane_array = [&](int s) __attribute__((always_inline)) {
-        return reinterpret_cast<const uint32_t*>(pick<const void*>(half, pick(s, col0, col1), pick(s, val0, val1)));
+        if constexpr (ROWVAL) return reinterpret_cast<const uint32_t*>(pick(s, col0, col1));
+        else return reinterpret_cast<const uint32_t*>(pick<const void*>(half, pick(s, col0, col1), pick(s, val0, val1)));
     };
     // this lane's four elements of block `blk` of hop s (zero outside the wave's range); the first one's index is x0
     auto block_load = [&](int s, int blk) __attribute__((always_inline)) {
         const uint32_t* a = lane_array(s);
-        const int hi = pick(s, len0, len1);
+        const int hi = (ROWVAL && half) ? 0 : pick(s, len0, len1);   // ROWVAL: the upper half of the wave fetches nothing
         const int x0 = blk * kRingBlock - misalign(a) + l4;
         u32x4 st = {0u, 0u, 0u, 0u};
         if (x0 >= 0 && x0 + 4 <= hi) {
@@ -1148,8 +1188,15 @@ __device__ __forceinline__ void window_tile_walk(const LaunchParams& p, int lane
     auto block_commit = [&](int s, int blk, const u32x4& st) __attribute__((always_inline)) {
         const int x0 = blk * kRingBlock - misalign(lane_array(s)) + l4;
         uint32_t* slots = ring[s];
+        if constexpr (ROWVAL) {
+            if (!half) {
 #pragma unroll
-        for (int i = 0; i < 4; ++i) slots[2 * ((uint32_t)(x0 + i) & (kRingCap - 1)) + half] = st[i];
+                for (int i = 0; i < 4; ++i) slots[(uint32_t)(x0 + i) & (kRingCap - 1)] = st[i];
+            }
+        } else {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) slots[2 * ((uint32_t)(x0 + i) & (kRingCap - 1)) + half] = st[i];
+        }
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
         __builtin_amdgcn_wave_barrier();
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -1183,6 +1230,8 @@ __device__ __forceinline__ void window_tile_walk(const LaunchParams& p, int lane
         } else {
             const GatherAddr<OFF32> addr{reinterpret_cast<const char*>(src_ptr<TS>(p.src) + p.src_hop_off[s] + src_col_begin - VEC),
                                          (off_t)lane_off0, (off_t)(p.ld_src * sizeof(TS))};
+            float w_row = 0.f;   // ROWVAL: the value of every entry of this segment, wave-uniform
+            if constexpr (ROWVAL) w_row = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rv), l0));
             for (int base = sb; base < se; base += kWave) {
                 const int n = min(se - base, kWave);
                 for (int b = blk_of(s); base + n > avail(s, b); set_blk(s, ++b)) {
@@ -1203,7 +1252,10 @@ __device__ __forceinline__ void window_tile_walk(const LaunchParams& p, int lane
                 const bool refill = pb < pe && min(pb + kWave, pe) > avail(ps, blk_of(ps));
                 u32x4 st = {0u, 0u, 0u, 0u};
                 if (refill) st = block_load(ps, blk_of(ps));
-                process_chunk_window<TS, VEC, LPR, false, OFF32, MAXB>(WindowChunk{ring[s], (uint32_t)(base + g)}, n, g, addr, true, acc);
+                if constexpr (ROWVAL)
+                    process_chunk_window<TS, VEC, LPR, false, OFF32, MAXB>(WindowChunkIds{ring[s], (uint32_t)(base + g), w_row}, n, g, addr, true, acc);
+                else
+                    process_chunk_window<TS, VEC, LPR, false, OFF32, MAXB>(WindowChunk{ring[s], (uint32_t)(base + g)}, n, g, addr, true, acc);
                 if (refill) {
                     block_commit(ps, blk_of(ps), st);
                     set_blk(ps, blk_of(ps) + 1);
@@ -1281,11 +1333,15 @@ constexpr int min_waves_per_simd() {
 // FB     deepest load batch of the wave-per-segment walk inside the SHORT kernels (their fallback) and the LISTS kernels
 //        (medium / long walks): 4 keeps them at 7-8 waves per SIMD (memory-resident operands dominated by short segments:
 //        occupancy buys bandwidth), 8 otherwise (cache-resident operands / launches dominated by longer segments)
+// ROWVAL every selected hop is row-constant (all stored values of a row carry the same bits; established once per plan, see
+//        h2gcn_plan_row_constant): the value stream is not read -- a row's value comes from p.rowval, once per segment.  Exists
+//        for the forward walk on the index window (uses_index_window, fp32 output); same neighbours, same tree, same bits.
 template <int VEC, int LPR, bool EXACT, bool SUM, bool OFF32, bool PIPE = false, bool SHORT = false, bool EPI = false, int FB = 8, bool LISTS = false,
-          typename TS = float, typename TD = float>
+          typename TS = float, typename TD = float, bool ROWVAL = false>
 __global__ __launch_bounds__(kBlock, (min_waves_per_simd<VEC, LPR, EXACT, SUM, OFF32, PIPE, SHORT, EPI, FB, LISTS, TS>())) void spmm_hops_kernel(const LaunchParams p) {
     static_assert(!LISTS || (EXACT && !SHORT && !PIPE && (LPR == 16 || LPR == 32)), "list-driven launches exist for 64- and 128-column slices");
     static_assert(EXACT || LPR == kWave, "column-tiled path uses the whole wave per row");
+    static_assert(!ROWVAL || (uses_index_window<LPR, EXACT, PIPE, SHORT, EPI, LISTS>() && !SUM), "row values: forward walk on the index window");
     __shared__ float partial[kWavesPerBlock][kMaxTileCols];
     using off_t = typename std::conditional<OFF32, uint32_t, int64_t>::type;
     constexpr int NP = Tree<LPR>::NP;
@@ -1330,8 +1386,12 @@ __global__ __launch_bounds__(kBlock, (min_waves_per_simd<VEC, LPR, EXACT, SUM, O
                 const int64_t sb = h.rowptr[row], se = h.rowptr[row + 1];
                 const GatherAddr<OFF32> addr{reinterpret_cast<const char*>(src_ptr<TS>(p.src) + p.src_hop_off[s] + src_col_begin + (col0 - col_begin) - kBias),
                                              EXACT ? lane_off0 : (off_t)(li * VEC * (int)sizeof(TS)), (off_t)(p.ld_src * sizeof(TS))};
-                accumulate_segment<TS, VEC, LPR, !EXACT, OFF32, kMainB>(h.colidx, h.vals, sb, se, wave, kWavesPerBlock, addr, lane,
-                                                            lane_active, acc);
+                if constexpr (ROWVAL)   // one load of the row's value per segment instead of a value fetch per chunk
+                    accumulate_segment<TS, VEC, LPR, !EXACT, OFF32, kMainB, true>(h.colidx, nullptr, sb, se, wave, kWavesPerBlock, addr, lane,
+                                                                              lane_active, acc, p.rowval[s][row]);
+                else
+                    accumulate_segment<TS, VEC, LPR, !EXACT, OFF32, kMainB>(h.colidx, h.vals, sb, se, wave, kWavesPerBlock, addr, lane,
+                                                                            lane_active, acc);
             }
             float tot[VEC];
             fold_tree<VEC, LPR, NP>(acc, tot);
@@ -1398,9 +1458,12 @@ __global__ __launch_bounds__(kBlock, (min_waves_per_simd<VEC, LPR, EXACT, SUM, O
 
     // one wave-wide load fetches every row pointer this wave needs: lane l -> hop l/(rpw+1), row l%(rpw+1)
     int64_t rp = 0;
+    float rv = 0.f;  // ROWVAL: ... and the values of its rows, in the same lanes
     {
         const int hs = lane / (rpw + 1), r = lane % (rpw + 1);
         if (hs < n_sel && r <= rows_here) rp = p.hop[hs].rowptr[row0 + r];
+        if constexpr (ROWVAL)
+            if (hs < n_sel && r < rows_here) rv = p.rowval[hs][row0 + r];
     }
     const int rp_lo = (int)(rp & 0xffffffff), rp_hi = (int)(rp >> 32);
     auto seg_bound = [&](int l) -> int64_t {
@@ -1414,14 +1477,14 @@ __global__ __launch_bounds__(kBlock, (min_waves_per_simd<VEC, LPR, EXACT, SUM, O
     if constexpr (uses_index_window<LPR, EXACT, PIPE, SHORT, EPI, LISTS>()) {
         // ---- the plain tile walk of 64-column slices on the index window; selections of more hops than the rings are
         //      sized for keep the walk below ----
-        __shared__ uint32_t ring[kWavesPerBlock][kRingHops][2 * kRingCap];
+        __shared__ uint32_t ring[kWavesPerBlock][kRingHops][(ROWVAL ? 1 : 2) * kRingCap];
         bool fits = n_sel <= kRingHops;  // ... and a wave whose range of a hop does not fit 32-bit relative indices (long segments inside)
 #pragma unroll
         for (int s = 0; s < kRingHops; ++s)
             if (s < n_sel && seg_bound(s * (rpw + 1) + rows_here) - seg_bound(s * (rpw + 1)) > kRingMaxRange) fits = false;
         if (fits) {
-            window_tile_walk<TS, TD, VEC, LPR, SUM, OFF32, EPI, kMainB>(p, lane, rpw, row0, rows_here, rp, (int64_t)lane_off0, src_col_begin, lcol, ecol,
-                                                                        ring[wave]);
+            window_tile_walk<TS, TD, VEC, LPR, SUM, OFF32, EPI, kMainB, ROWVAL>(p, lane, rpw, row0, rows_here, rp, (int64_t)lane_off0, src_col_begin, lcol,
+                                                                                ecol, ring[wave], rv);
             return;
         }
     }
@@ -1538,7 +1601,11 @@ __global__ __launch_bounds__(kBlock, (min_waves_per_simd<VEC, LPR, EXACT, SUM, O
                 const HopCsr& h = p.hop[s];
                 const GatherAddr<OFF32> addr{reinterpret_cast<const char*>(src_ptr<TS>(p.src) + p.src_hop_off[s] + src_col_begin + (col0 - col_begin) - kBias),
                                              EXACT ? lane_off0 : (off_t)(li * VEC * (int)sizeof(TS)), (off_t)(p.ld_src * sizeof(TS))};
-                accumulate_segment<TS, VEC, LPR, !EXACT, OFF32, kMainB>(h.colidx, h.vals, sb, se, 0, 1, addr, lane, lane_active, acc);
+                if constexpr (ROWVAL)   // (a wave whose range does not fit the window's 32-bit relative indices)
+                    accumulate_segment<TS, VEC, LPR, !EXACT, OFF32, kMainB, true>(h.colidx, nullptr, sb, se, 0, 1, addr, lane, lane_active, acc,
+                                                                              __int_as_float(__builtin_amdgcn_readlane(__float_as_int(rv), l0)));
+                else
+                    accumulate_segment<TS, VEC, LPR, !EXACT, OFF32, kMainB>(h.colidx, h.vals, sb, se, 0, 1, addr, lane, lane_active, acc);
                 if constexpr (!SUM) {
                     float tot[VEC];
                     fold_tree<VEC, LPR, NP>(acc, tot);
@@ -1630,6 +1697,7 @@ struct Schedule {
     bool gen;        // general store (bias / ReLU / accumulate epilogue, width not a multiple of 4)
     bool off32;      // 32-bit gather offsets
     int slice;       // 256 / 128 / 64 columns; 0: generic column-tiled kernel (d < 4)
+    bool rowval = false;  // forward walk on the index window, every selected hop row-constant: no value stream (set by launch())
 };
 
 // One function template per walk family, each fanning out its runtime flags once; launch_spmm picks the family and the lane
@@ -1642,6 +1710,15 @@ template <int VEC, int LPR, bool EXACT, bool SUM, typename TS, typename TD>
 void launch_tile_walk(const LaunchParams& p, const Schedule& k, dim3 grid, hipStream_t stream) {
     const dim3 block(kBlock);
     const bool pipe = EXACT && k.pipe;   // the column-tiled kernel has no index prefetch
+    if constexpr (uses_index_window<LPR, EXACT, false, false, false, false>() && !SUM && std::is_same<TD, float>::value) {
+        if (k.rowval && !k.gen && !pipe) {
+            if (k.off32)
+                hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, EXACT, SUM, true, false, false, false, 8, false, TS, TD, true>), grid, block, 0, stream, p);
+            else
+                hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, EXACT, SUM, false, false, false, false, 8, false, TS, TD, true>), grid, block, 0, stream, p);
+            return;
+        }
+    }
     if (k.gen && k.off32)
         hipLaunchKernelGGL((spmm_hops_kernel<VEC, LPR, EXACT, SUM, true, false, false, true, 8, false, TS, TD>), grid, block, 0, stream, p);
     else if (k.gen)

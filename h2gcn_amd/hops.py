@@ -241,6 +241,21 @@ class HopPlan:
             out.append(("none", "indices", "indices+values")[v])
         return out
 
+    @property
+    def row_constant(self) -> list:
+        """Per hop, 1 when every stored value of each row carries the bits of the row's first one (established at plan creation,
+        cleared by :meth:`set_values`), else 0: forward launches whose selected hops are all row-constant do not read the value
+        arrays (``h2gcn_plan_row_constant``)."""
+        if not _capi.has("h2gcn_plan_row_constant"):
+            return [0] * self.n_hops
+        L = _capi.lib()
+        out = []
+        for k in range(self.n_hops):
+            v = L.h2gcn_plan_row_constant(self._handle, k)
+            _capi.check(v)
+            out.append(int(v))
+        return out
+
     def device_bytes(self) -> int:
         """Device memory the plan owns now, in bytes: transposed arrays, permutations, a symmetric plan's transposed values, and
         the row lists built so far -- never the operand arrays it borrows (``h2gcn_plan_device_bytes``)."""

@@ -167,6 +167,10 @@ void h2gcn_plan_destroy(h2gcn_plan_t* plan);
  * Plans created with H2GCN_PLAN_SYMMETRIC_PATTERN: the same rule -- with H2GCN_PLAN_KEEP_PERMUTATION the plan-owned values of
  * A_k^T are refreshed through the mirror positions (the new values need not be symmetric; the PATTERN is what was verified),
  * without it the call fails as on any plan with transposed operands, whether or not the adjoint aliased the old values.
+ * A hop that was row-constant (h2gcn_plan_row_constant) falls back to the value stream for good: the new values are not
+ * examined.  The first such call on a row-constant hop releases the plan's row values (one hipFree; inside a stream capture
+ * they stay allocated until the plan is destroyed); every later call does nothing on that account -- no detection, no
+ * synchronisation.
  */
 int h2gcn_plan_set_values(h2gcn_plan_t* plan, int hop, const float* vals_dev, void* stream);
 
@@ -178,9 +182,20 @@ int h2gcn_plan_info(const h2gcn_plan_t* plan, int hop, int64_t* n_rows, int64_t*
  * transposes), 1 = rowptr and colidx, 2 = rowptr, colidx and vals (see H2GCN_PLAN_SYMMETRIC_PATTERN).  Negative: h2gcn_status. */
 int h2gcn_plan_transpose_sharing(const h2gcn_plan_t* plan, int hop);
 
+/* Whether hop `hop` is ROW-CONSTANT: 1 when every stored value of each row of A_k carries the same bit pattern as the row's
+ * first stored value (D^-1 A_k, an unnormalised 0/1 adjacency, mean aggregation ...; compared as 32-bit words: +0.0 next to
+ * -0.0 is not constant, NaNs of one payload are; empty rows and a hop without nonzeros are), 0 otherwise.  Established once,
+ * at h2gcn_plan_create (one read of vals, whether or not H2GCN_PLAN_SKIP_VALIDATION is set), cleared for good by
+ * h2gcn_plan_set_values on that hop.  The plan keeps one fp32 value per row of a row-constant hop (n_rows * 4 bytes), and a
+ * forward launch with an fp32 output that walks 64-column slices over at most two selected hops, ALL of them row-constant,
+ * takes a row's value from there instead of reading vals -- same neighbours, same summation tree, same bits.  Everything else
+ * (adjoint launches: A_k^T of a row-normalised matrix is not row-constant; per-launch values; the pattern kernels) reads the
+ * value arrays as before.  Negative: h2gcn_status. */
+int h2gcn_plan_row_constant(const h2gcn_plan_t* plan, int hop);
+
 /* Device memory the plan owns at this moment, in bytes: transposed arrays, permutations, the values of A_k^T of a symmetric
- * plan, and the device row lists built so far (they grow with the first launch of a hop selection).  Never the caller's
- * arrays.  0 for NULL. */
+ * plan, the row values of row-constant hops, and the device row lists built so far (they grow with the first launch of a hop
+ * selection).  Never the caller's arrays.  0 for NULL. */
 size_t h2gcn_plan_device_bytes(const h2gcn_plan_t* plan);
 
 /* The schedule a launch of this plan would use for feature width d and source row stride ld_src (reports, tests):

@@ -77,7 +77,7 @@ while "--used-in" in argv:
     while j < len(argv) and not argv[j].startswith("-"):
         for line in Path(argv[j]).read_text().splitlines():
             m = re.search(r"spmm_hops_kernel<(\d+), (\d+), (true|false), (true|false), (true|false), (true|false), (true|false), (true|false), (\d+)"
-                          r"(?:, (true|false))?(?:, (float|h2gcn::bf16), (float|h2gcn::bf16))?>", line)
+                          r"(?:, (true|false))?(?:, (float|h2gcn::bf16), (float|h2gcn::bf16))?(?:, (?:true|false))?>", line)
             if m:
                 key = tuple("1" if v == "true" else "0" if v in ("false", None) else DTYPE.get(v, v) for v in m.groups())
                 used.setdefault(key, []).append(f"{Path(argv[j]).name}: {' '.join(line.split()[-2:])}")
@@ -98,9 +98,10 @@ for b in re.split(r"remark: [^\n]*Function Name: ", txt)[1:]:
     def g(k):
         m = re.search(k + r": (\d+)", b)
         return int(m.group(1)) if m else -1
-    m = re.search(r"spmm_hops_kernelILi(\d+)ELi(\d+)ELb(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)ELi(\d+)ELb(\d)E(f|NS_4bf16E)?(f|S1_)?", name)
+    m = re.search(r"spmm_hops_kernelILi(\d+)ELi(\d+)ELb(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)ELb(\d)ELi(\d+)ELb(\d)E(f|NS_4bf16E)?(f|S1_)?(?:Lb(\d)E)?", name)
+    rowval = bool(m) and m.group(13) == "1"      # the row-constant mode (last template parameter)
     if m:
-        m_groups = m.groups()[:10] + tuple(DTYPE[t] for t in m.groups()[10:])
+        m_groups = m.groups()[:10] + tuple(DTYPE[t] for t in m.groups()[10:12])
     if used and not (m and m_groups in used):
         continue
     where = ("   <- " + "; ".join(used[m_groups])) if used and m else ""
@@ -108,6 +109,6 @@ for b in re.split(r"remark: [^\n]*Function Name: ", txt)[1:]:
         v, lpr, ex, su, o32, pipe, sh, epi, fb, lists, ts, td = m_groups
         name = f"spmm<VEC{v} LPR{lpr:>2s} {'EXACT' if ex=='1' else 'tiled'} {'SUM' if su=='1' else 'fwd'} {'off32' if o32=='1' else 'off64'}" \
                f"{' PIPE' if pipe=='1' else ''}{' SHORT' if sh=='1' else ''}{' LISTS' if lists=='1' else ''}{' GEN' if epi=='1' else ''} FB{fb}" \
-               f"{'' if ts == td == 'f32' else f' {ts}->{td}'}>"
+               f"{'' if ts == td == 'f32' else f' {ts}->{td}'}{' ROWVAL' if rowval else ''}>"
     scratch, occ = g(r"ScratchSize \[bytes/lane\]"), g(r"Occupancy \[waves/SIMD\]")
     print(f"{name:64s} vgpr {g('VGPRs'):3d} sgpr {g('SGPRs'):3d} scratch {scratch:3d} occupancy {occ}{where}")
