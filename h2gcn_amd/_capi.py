@@ -64,6 +64,11 @@ EXPORTED_SYMBOLS = (
     "h2gcn_row_softmax_backward_hops_f32",
     "h2gcn_edge_scores_hops_f32",
     "h2gcn_edge_scores_backward_hops_f32",
+    "h2gcn_sddmm_hops_heads_f32",
+    "h2gcn_row_softmax_hops_heads_f32",
+    "h2gcn_row_softmax_backward_hops_heads_f32",
+    "h2gcn_edge_scores_hops_heads_f32",
+    "h2gcn_edge_scores_backward_hops_heads_f32",
     "h2gcn_spmm_hops_values_f32",
     "h2gcn_spmm_hops_T_values_f32",
     "h2gcn_ring_scratch_bytes",
@@ -246,6 +251,20 @@ def lib() -> C.CDLL:
         L.h2gcn_edge_scores_hops_f32.argtypes = node_args + [C.c_void_p]
         L.h2gcn_edge_scores_backward_hops_f32.restype = C.c_int
         L.h2gcn_edge_scores_backward_hops_f32.argtypes = node_args + [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+    if hasattr(L, "h2gcn_sddmm_hops_heads_f32"):   # (the head dimension of the three calls above, added within ABI 5)
+        tbl = C.POINTER(C.c_void_p)
+        L.h2gcn_sddmm_hops_heads_f32.restype = C.c_int
+        L.h2gcn_sddmm_hops_heads_f32.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                                 C.c_int32, C.c_int32, tbl, C.c_void_p]
+        L.h2gcn_row_softmax_hops_heads_f32.restype = C.c_int
+        L.h2gcn_row_softmax_hops_heads_f32.argtypes = [C.c_void_p, C.c_uint32, tbl, tbl, C.c_int32, C.c_void_p]
+        L.h2gcn_row_softmax_backward_hops_heads_f32.restype = C.c_int
+        L.h2gcn_row_softmax_backward_hops_heads_f32.argtypes = [C.c_void_p, C.c_uint32, tbl, tbl, tbl, C.c_int32, C.c_void_p]
+        node_heads_args = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_float, tbl]
+        L.h2gcn_edge_scores_hops_heads_f32.restype = C.c_int
+        L.h2gcn_edge_scores_hops_heads_f32.argtypes = node_heads_args + [C.c_void_p]
+        L.h2gcn_edge_scores_backward_hops_heads_f32.restype = C.c_int
+        L.h2gcn_edge_scores_backward_hops_heads_f32.argtypes = node_heads_args + [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
     if hasattr(L, "h2gcn_spmm_hops_values_f32"):   # (the hop SpMM on per-launch values with heads, added within ABI 5)
         values_args = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32]
         L.h2gcn_spmm_hops_values_f32.restype = C.c_int

@@ -739,6 +739,169 @@ class HopPlan:
         _capi.check(st)
         return (dl.view(shapes[0]) if need_dl else None, dr.view(shapes[1]) if need_dr else None)
 
+    # ---- the head dimension of sddmm / row_softmax / edge_scores: entry-major [nnz_k, K] arrays, one launch for all heads
+    _HEADS_SYMBOLS = ("h2gcn_sddmm_hops_heads_f32", "h2gcn_row_softmax_hops_heads_f32", "h2gcn_row_softmax_backward_hops_heads_f32",
+                      "h2gcn_edge_scores_hops_heads_f32", "h2gcn_edge_scores_backward_hops_heads_f32")
+
+    @classmethod
+    def _heads_symbols(cls) -> None:
+        if not all(_capi.has(s) for s in cls._HEADS_SYMBOLS):
+            raise RuntimeError(f"{_capi.library_path()} predates the head-batched attention calls ({', '.join(cls._HEADS_SYMBOLS)}): rebuild it")
+
+    def _head_tensors(self, op: str, name: str, tensors, sel, n_heads: Optional[int] = None) -> tuple:
+        """``tensors`` as a list of one contiguous float32 ``[nnz_k, K]`` tensor per selected hop, one ``K`` for all -> ``(list, K)``."""
+        _require(not isinstance(tensors, torch.Tensor) and tensors is not None, f"{name} must be a sequence of {len(sel)} tensors (one per selected hop)")
+        tensors = list(tensors)
+        _require(len(tensors) == len(sel), f"{name} must list {len(sel)} tensors (one per selected hop), got {len(tensors)}")
+        for s, k in enumerate(sel):
+            t, nnz = tensors[s], self.colidx[k].numel()
+            _require(isinstance(t, torch.Tensor), f"{name}[{s}] must be a tensor, got {type(t).__name__}")
+            _require(t.dtype == torch.float32, f"{name}[{s}] must be float32 (the {op} is fp32 only), got {t.dtype}")
+            _require(t.device == self.device, f"{name}[{s}] on {t.device}, plan on {self.device}")
+            _require(t.dim() == 2 and t.shape[0] == nnz and t.shape[1] >= 1,
+                     f"{name}[{s}] must have shape [{nnz}, K] (one value per stored entry of hop {k} and head), got {tuple(t.shape)}")
+            _require(n_heads in (None, int(t.shape[1])),
+                     f"{name}[{s}] has {int(t.shape[1])} heads where {n_heads} are expected: every per-entry array needs the same K")
+            n_heads = int(t.shape[1])
+            _require(t.is_contiguous(), f"{name}[{s}] must be contiguous (entry-major: element (e, h) at e * K + h)")
+        return tensors, n_heads
+
+    def _head_outputs(self, op: str, out, sel, n_heads: int) -> list:
+        if out is not None:
+            return self._head_tensors(op, "out", out, sel, n_heads)[0]
+        return [torch.empty((self.colidx[k].numel(), n_heads), dtype=torch.float32, device=self.device) for k in sel]
+
+    def sddmm_heads(self, grad: torch.Tensor, x: torch.Tensor, heads: int, hops=None,
+                    out: Optional[Sequence[torch.Tensor]] = None) -> list:
+        """:meth:`sddmm` for ``K = heads`` heads in one launch: ``dvals[s][e, h] = sum_{c in head h} grad[i, s, c] * x[j, c]``, head
+        ``h`` owning columns ``h * d / K ..`` -> one contiguous float32 ``[nnz_k, K]`` tensor per selected hop
+        (``h2gcn_sddmm_hops_heads_f32``).  Per head the bits are those of :meth:`sddmm` on the head's column slices.
+
+        ``grad`` ``[n_rows, H_sel, d]`` and ``x`` ``[n_cols, d]``: float32 (bfloat16 is refused); row / hop strides pass through.
+        ``heads >= 1`` with ``d % heads == 0`` and, for ``heads > 1``, ``(d // heads) % 4 == 0``.  ``out``: a list of ``H_sel``
+        contiguous float32 ``[nnz_k, K]`` tensors to overwrite."""
+        h_sel = self.n_selected(hops)
+        _require(isinstance(grad, torch.Tensor) and grad.dim() == 3 and grad.shape[0] == self.n_rows and grad.shape[1] == h_sel,
+                 f"grad must be [{self.n_rows}, {h_sel}, d], got {tuple(getattr(grad, 'shape', ()))}")
+        d = int(grad.shape[2])
+        _require(d >= 1, "grad needs at least one column")
+        _require(isinstance(x, torch.Tensor) and x.dim() == 2 and tuple(x.shape) == (self.n_cols, d),
+                 f"x must be [{self.n_cols}, {d}], got {tuple(getattr(x, 'shape', ()))}")
+        _require(grad.dtype == torch.float32 and x.dtype == torch.float32,
+                 f"grad and x must be float32 (the values gradient with heads is fp32 only), got {grad.dtype} and {x.dtype}")
+        _require(grad.device == self.device and x.device == self.device, f"grad on {grad.device}, x on {x.device}, plan on {self.device}")
+        n_heads = int(heads)
+        _require(n_heads >= 1, f"heads = {heads} < 1")
+        _require(d % n_heads == 0, f"the width d = {d} is not a multiple of the number of heads K = {n_heads}")
+        _require(n_heads == 1 or (d // n_heads) % 4 == 0,
+                 f"with K = {n_heads} > 1 heads the head width d / K = {d // n_heads} must be a multiple of 4")
+        if grad.stride(2) != 1 or grad.stride(0) < d or (h_sel > 1 and grad.stride(1) < d):
+            grad = grad.contiguous()
+        if x.stride(1) != 1 or x.stride(0) < d:
+            x = x.contiguous()
+        mask, sel = self._mask(hops), self._selected(hops)
+        out = self._head_outputs("values gradient", out, sel, n_heads)
+        ld_row, ld_hop = (grad.stride(0) if self.n_rows > 1 else h_sel * d), (grad.stride(1) if h_sel > 1 else d)
+        ldx = x.stride(0) if self.n_cols > 1 else d
+        self._heads_symbols()
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            st = _capi.lib().h2gcn_sddmm_hops_heads_f32(self._handle, mask, C.c_void_p(grad.data_ptr()), ld_row, ld_hop,
+                                                        C.c_void_p(x.data_ptr()), ldx, d, n_heads, *self._segment_ptrs(out),
+                                                        C.c_void_p(stream))
+        _capi.check(st)
+        return out
+
+    def _row_softmax_heads_launch(self, symbol: str, hops, inputs: dict, out) -> list:
+        mask, sel = self._mask(hops), self._selected(hops)
+        tables, n_heads = [], None
+        for name, ts in inputs.items():
+            ts, n_heads = self._head_tensors("row softmax", name, ts, sel, n_heads)
+            tables.append(ts)
+        out = self._head_outputs("row softmax", out, sel, n_heads)
+        self._heads_symbols()
+        ptrs = self._segment_ptrs(*tables, out)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            st = getattr(_capi.lib(), symbol)(self._handle, mask, *ptrs, n_heads, C.c_void_p(stream))
+        _capi.check(st)
+        return out
+
+    def row_softmax_heads(self, scores: Sequence[torch.Tensor], hops=None, out: Optional[Sequence[torch.Tensor]] = None) -> list:
+        """:meth:`row_softmax` for ``K`` heads in one launch: one softmax per (row, hop, head) over contiguous float32
+        ``[nnz_k, K]`` scores -> ``[nnz_k, K]`` coefficients per selected hop (``h2gcn_row_softmax_hops_heads_f32``) -- the layout
+        :meth:`spmm_values` reads fastest.  Per head the bits are those of :meth:`row_softmax` on a contiguous copy of that
+        column.  ``out`` may be the ``scores`` tensors themselves."""
+        return self._row_softmax_heads_launch("h2gcn_row_softmax_hops_heads_f32", hops, {"scores": scores}, out)
+
+    def row_softmax_heads_backward(self, alpha: Sequence[torch.Tensor], grad: Sequence[torch.Tensor], hops=None,
+                                   out: Optional[Sequence[torch.Tensor]] = None) -> list:
+        """The backward of :meth:`row_softmax_heads` (``h2gcn_row_softmax_backward_hops_heads_f32``, one launch): ``alpha`` and
+        ``grad`` contiguous float32 ``[nnz_k, K]``; ``out`` may be the ``grad`` tensors themselves."""
+        return self._row_softmax_heads_launch("h2gcn_row_softmax_backward_hops_heads_f32", hops, {"alpha": alpha, "grad": grad}, out)
+
+    def _node_heads_operand(self, name: str, t, n: int, h_sel: int, n_heads: Optional[int] = None):
+        """A per-node operand of the edge scores with heads: float32 ``[n, h_sel, K]`` whose last two dimensions are contiguous (a
+        row stride passes through) -> ``(tensor, row stride in elements, K)``."""
+        _require(isinstance(t, torch.Tensor), f"{name} must be a tensor, got {type(t).__name__}")
+        _require(t.dtype == torch.float32, f"{name} must be float32 (the edge scores are fp32 only), got {t.dtype}")
+        _require(t.device == self.device, f"{name} on {t.device}, plan on {self.device}")
+        _require(t.dim() == 3 and t.shape[0] == n and t.shape[1] == h_sel and t.shape[2] >= 1 and n_heads in (None, int(t.shape[2])),
+                 f"{name} must have shape [{n}, {h_sel}, {'K' if n_heads is None else n_heads}] (node, selected hop, head), got {tuple(t.shape)}")
+        k = int(t.shape[2])
+        if (k > 1 and t.stride(2) != 1) or (h_sel > 1 and t.stride(1) != k) or (n > 1 and t.stride(0) < h_sel * k):
+            t = t.contiguous()
+        return t, (t.stride(0) if n > 1 else h_sel * k), k
+
+    def edge_scores_heads(self, l: torch.Tensor, r: torch.Tensor, negative_slope: float = 0.2, hops=None,
+                          out: Optional[Sequence[torch.Tensor]] = None) -> list:
+        """:meth:`edge_scores` for ``K`` heads in one launch: ``score[s][e, h] = leaky_relu(l[i, s, h] + r[j, s, h])`` -> one
+        contiguous float32 ``[nnz_k, K]`` tensor per selected hop (``h2gcn_edge_scores_hops_heads_f32``).  ``l`` ``[n_rows, H_sel,
+        K]``, ``r`` ``[n_cols, H_sel, K]``: float32; a row stride passes through.  Per head the bits are those of
+        :meth:`edge_scores` on ``l[:, :, h]``, ``r[:, :, h]``."""
+        mask, sel = self._mask(hops), self._selected(hops)
+        l, ldl, n_heads = self._node_heads_operand("l", l, self.n_rows, len(sel))
+        r, ldr, _ = self._node_heads_operand("r", r, self.n_cols, len(sel), n_heads)
+        out = self._head_outputs("edge scores", out, sel, n_heads)
+        self._heads_symbols()
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            st = _capi.lib().h2gcn_edge_scores_hops_heads_f32(self._handle, mask, C.c_void_p(l.data_ptr()), ldl, C.c_void_p(r.data_ptr()),
+                                                              ldr, n_heads, float(negative_slope), *self._segment_ptrs(out),
+                                                              C.c_void_p(stream))
+        _capi.check(st)
+        return out
+
+    def edge_scores_heads_backward(self, l: torch.Tensor, r: torch.Tensor, grad: Sequence[torch.Tensor], negative_slope: float = 0.2,
+                                   hops=None, need_dl: bool = True, need_dr: bool = True) -> tuple:
+        """The backward of :meth:`edge_scores_heads` -> ``(dl, dr)``, ``[n_rows, H_sel, K]`` and ``[n_cols, H_sel, K]``
+        (``h2gcn_edge_scores_backward_hops_heads_f32``): per head the row / column sums of :meth:`edge_scores_backward`, the same
+        bits.  ``grad``: ``H_sel`` contiguous float32 ``[nnz_k, K]`` tensors.  ``need_dl`` / ``need_dr`` and the plan requirements
+        of the column side as in :meth:`edge_scores_backward`."""
+        mask, sel = self._mask(hops), self._selected(hops)
+        h_sel = len(sel)
+        _require(need_dl or need_dr, "need_dl and need_dr are both False: nothing to compute")
+        l, ldl, n_heads = self._node_heads_operand("l", l, self.n_rows, h_sel)
+        r, ldr, _ = self._node_heads_operand("r", r, self.n_cols, h_sel, n_heads)
+        grad, _ = self._head_tensors("edge scores", "grad", grad, sel, n_heads)
+        _require(not need_dr or (self.has_transpose and self.keep_permutation),
+                 "the gradient wrt r sums over the COLUMNS of the hop matrices: it walks the plan's transposed operands through their "
+                 "permutation.  Build the plan with HopPlan(..., build_transpose=True, keep_permutation=True)"
+                 + ("" if self.has_transpose else " (this plan has no transposed operands)"))
+        self._heads_symbols()
+        dl = torch.empty((self.n_rows, h_sel, n_heads), dtype=torch.float32, device=self.device) if need_dl else None
+        dr = torch.empty((self.n_cols, h_sel, n_heads), dtype=torch.float32, device=self.device) if need_dr else None
+        if all(t is None or t.numel() == 0 for t in (dl, dr)):   # (no node on the requested sides: nothing to write)
+            return dl, dr
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            st = _capi.lib().h2gcn_edge_scores_backward_hops_heads_f32(
+                self._handle, mask, C.c_void_p(l.data_ptr()), ldl, C.c_void_p(r.data_ptr()), ldr, n_heads, float(negative_slope),
+                *self._segment_ptrs(grad), C.c_void_p(dl.data_ptr()) if need_dl else None, h_sel * n_heads,
+                C.c_void_p(dr.data_ptr()) if need_dr else None, h_sel * n_heads, C.c_void_p(stream))
+        _capi.check(st)
+        return dl, dr
+
     def __del__(self):
         h = getattr(self, "_handle", None)
         if h is not None and h.value:

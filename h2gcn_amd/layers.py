@@ -130,8 +130,9 @@ def hop_spmm(adjhops: HopPlan, inputs: torch.Tensor, hops: Optional[Iterable[int
 class _HopSpMMLaunchValues(torch.autograd.Function):
     """The hop SpMM on values handed to the launch (``HopPlan.spmm_values``), a function of the dense input and of the values of
     the SELECTED hops: forward -- one launch, ``inputs`` and ``values`` saved, nothing installed in the plan; backward -- one
-    ``spmm_values_t`` launch for the input, and for the values ``HopPlan.sddmm`` once per head on that head's column slices
-    (strided views), over the hops whose values want a gradient."""
+    ``spmm_values_t`` launch for the input, and for the values of the hops that want a gradient ONE ``HopPlan.sddmm_heads`` launch
+    when there are heads (``HopPlan.sddmm`` once per head on that head's column slices -- the same bits -- on a library that
+    predates it, and for a single head)."""
 
     @staticmethod
     def forward(ctx, x: torch.Tensor, plan: HopPlan, hops, *values):
@@ -152,6 +153,10 @@ class _HopSpMMLaunchValues(torch.autograd.Function):
             g = _hop_slots(grad_out, pos)
             n_heads = 1 if values[0].dim() == 1 else values[0].shape[1]
             w = x.shape[1] // n_heads
+            if n_heads > 1 and _capi.has("h2gcn_sddmm_hops_heads_f32"):
+                for i, dv in enumerate(plan.sddmm_heads(g, x, n_heads, hops=want)):   # one launch, [nnz_k, K]: the same bits
+                    dvals[pos[i]] = dv
+                return (dx, None, None, *dvals)
             per_head = [plan.sddmm(g[:, :, h * w:(h + 1) * w], x[:, h * w:(h + 1) * w], hops=want) for h in range(n_heads)]
             for i, s in enumerate(pos):
                 dvals[s] = per_head[0][i] if values[s].dim() == 1 else torch.stack([dv[i] for dv in per_head], dim=1)
@@ -291,6 +296,106 @@ def hop_edge_scores(adjhops: HopPlan, l: torch.Tensor, r: torch.Tensor, negative
     return tuple(adjhops.edge_scores(l, r, negative_slope, hops=sel))
 
 
+class _HopSoftmaxHeads(torch.autograd.Function):
+    """:class:`_HopSoftmax` on entry-major ``[nnz_k, K]`` arrays: one launch forward (``HopPlan.row_softmax_heads``), one backward."""
+
+    @staticmethod
+    def forward(ctx, plan: HopPlan, hops, *scores):
+        alpha = plan.row_softmax_heads(scores, hops=hops)
+        ctx.plan, ctx.hops = plan, hops
+        ctx.save_for_backward(*alpha)
+        return tuple(alpha)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        alpha = ctx.saved_tensors
+        if not any(ctx.needs_input_grad[2:]):
+            return (None, None) + (None,) * len(alpha)
+        grads = [torch.zeros_like(a) if g is None else g.contiguous() for g, a in zip(grads, alpha)]
+        dscores = ctx.plan.row_softmax_heads_backward(alpha, grads, hops=ctx.hops)
+        return (None, None, *[d if need else None for d, need in zip(dscores, ctx.needs_input_grad[2:])])
+
+
+def hop_softmax_heads(adjhops: HopPlan, scores, hops: Optional[Iterable[int]] = None) -> tuple:
+    """:func:`hop_softmax` for ``K`` heads at once: ``scores`` is a sequence of ``H_sel`` contiguous float32 ``[nnz_k, K]`` tensors
+    (entry-major: what :func:`hop_edge_scores_heads` returns), the result a tuple of ``[nnz_k, K]`` coefficients -- one softmax per
+    hop, row and head -- that :func:`hop_spmm_values` takes as they are.  Forward and backward are one launch each
+    (:meth:`HopPlan.row_softmax_heads` / :meth:`HopPlan.row_softmax_heads_backward`); per head the bits are those of
+    :func:`hop_softmax` on that column.  fp32 only.  Row-partitioned operands (``ShardedHops``) are not covered."""
+    if hasattr(adjhops, "aggregate"):
+        raise ValueError("hop_softmax_heads is not supported on row-partitioned operands (ShardedHops): pass a single-GPU HopPlan")
+    if not isinstance(adjhops, HopPlan):
+        raise TypeError(f"adjhops must be a HopPlan, got {type(adjhops).__name__}")
+    sel = None if hops is None else tuple(sorted(set(int(h) for h in hops)))
+    if isinstance(scores, torch.Tensor) or scores is None:
+        raise ValueError(f"scores must be a sequence of {adjhops.n_selected(sel)} tensors (one per selected hop)")
+    scores = tuple(scores)
+    if any(isinstance(t, torch.Tensor) and t.requires_grad for t in scores) and torch.is_grad_enabled():
+        # (the argument checks of the launch run first either way: HopPlan.row_softmax_heads refuses before any device work)
+        return _HopSoftmaxHeads.apply(adjhops, sel, *scores)
+    return tuple(adjhops.row_softmax_heads(scores, hops=sel))
+
+
+class _HopEdgeScoresHeads(torch.autograd.Function):
+    """:class:`_HopEdgeScores` with heads: one launch forward (``HopPlan.edge_scores_heads``), one call backward."""
+
+    @staticmethod
+    def forward(ctx, plan: HopPlan, hops, negative_slope: float, l: torch.Tensor, r: torch.Tensor):
+        scores = plan.edge_scores_heads(l, r, negative_slope, hops=hops)
+        ctx.plan, ctx.hops, ctx.negative_slope = plan, hops, negative_slope
+        ctx.save_for_backward(l, r)
+        return tuple(scores)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        need_dl, need_dr = ctx.needs_input_grad[3:5]
+        if not (need_dl or need_dr):
+            return None, None, None, None, None
+        l, r = ctx.saved_tensors
+        plan = ctx.plan
+        grads = [torch.zeros((plan.colidx[k].numel(), l.shape[2]), dtype=torch.float32, device=plan.device) if g is None
+                 else g.contiguous() for g, k in zip(grads, plan._selected(ctx.hops))]
+        dl, dr = plan.edge_scores_heads_backward(l, r, grads, ctx.negative_slope, hops=ctx.hops, need_dl=need_dl, need_dr=need_dr)
+        return None, None, None, dl, dr
+
+
+def hop_edge_scores_heads(adjhops: HopPlan, l: torch.Tensor, r: torch.Tensor, negative_slope: float = 0.2,
+                          hops: Optional[Iterable[int]] = None) -> tuple:
+    """:func:`hop_edge_scores` for ``K`` heads at once: ``scores[s][e, h] = leaky_relu(l[i, s, h] + r[j, s, h], negative_slope)`` as
+    a tuple of ``H_sel`` contiguous float32 ``[nnz_k, K]`` tensors (what :func:`hop_softmax_heads` takes), differentiable wrt ``l``
+    ``[n_rows, H_sel, K]`` and ``r`` ``[n_cols, H_sel, K]`` (float32; bfloat16 is refused).  Forward and backward are one call each
+    (:meth:`HopPlan.edge_scores_heads` / :meth:`HopPlan.edge_scores_heads_backward`), free of atomics; per head the bits are those
+    of :func:`hop_edge_scores` on ``l[:, :, h]``, ``r[:, :, h]``.  A gradient for ``r`` needs a plan built with
+    ``build_transpose=True, keep_permutation=True``.  Row-partitioned operands (``ShardedHops``) are not covered."""
+    if hasattr(adjhops, "aggregate"):
+        raise ValueError("hop_edge_scores_heads is not supported on row-partitioned operands (ShardedHops): pass a single-GPU HopPlan")
+    if not isinstance(adjhops, HopPlan):
+        raise TypeError(f"adjhops must be a HopPlan, got {type(adjhops).__name__}")
+    sel = None if hops is None else tuple(sorted(set(int(h) for h in hops)))
+    grads = [isinstance(t, torch.Tensor) and t.requires_grad and torch.is_grad_enabled() for t in (l, r)]
+    if grads[1] and not (adjhops.has_transpose and adjhops.keep_permutation):
+        raise ValueError("hop_edge_scores_heads with an r that requires a gradient: that gradient sums over the columns of the hop "
+                         "matrices, on the plan's transposed operands through their permutation.  Build the plan with "
+                         "HopPlan(..., build_transpose=True, keep_permutation=True)")
+    if any(grads):
+        # (the argument checks of the launch run first either way: HopPlan.edge_scores_heads refuses before any device work)
+        return _HopEdgeScoresHeads.apply(adjhops, sel, float(negative_slope), l, r)
+    return tuple(adjhops.edge_scores_heads(l, r, negative_slope, hops=sel))
+
+
+class _StackHeads(torch.autograd.Function):
+    """``torch.stack(per_head, dim=2)`` of ``K`` ``[N, H_sel]`` projections; the backward hands every head a CONTIGUOUS ``[N, H_sel]``
+    gradient, the operand the per-head chain gave the projection's GEMMs (so they run as before, on the same bits)."""
+
+    @staticmethod
+    def forward(ctx, *per_head):
+        return torch.stack(per_head, dim=2)
+
+    @staticmethod
+    def backward(ctx, grad):
+        return tuple(grad[:, :, h].contiguous() for h in range(grad.shape[2]))
+
+
 class HopAttention(torch.nn.Module):
     """``HopAttention(in_dim, hops=None, n_hops=2, negative_slope=0.2)(adjhops, inputs) -> [N, H_sel, d]``: the attention
     counterpart of :class:`GCNLayer` -- per selected hop ``s`` the rows of ``inputs`` are aggregated with coefficients
@@ -351,10 +456,11 @@ class MultiHeadHopAttention(torch.nn.Module):
 
     ``heads``: an integer ``K >= 1`` with ``in_dim % K == 0``, and ``(in_dim / K) % 4 == 0`` when ``K > 1``.  ``a_l``, ``a_r``:
     parameters ``[H_sel, K, in_dim / K]``, Glorot-uniform.  Head ``h`` scores with and aggregates columns ``h * in_dim / K ..`` of
-    ``inputs``: ``l[n, s, h] = <inputs[n, head h], a_l[s, h]>``, ``r`` likewise; per head :func:`hop_edge_scores` then
-    :func:`hop_softmax` (the launches of the single-head layer, on contiguous ``[nnz_k]`` arrays); per hop the heads are stacked to
-    ``[K, nnz_k]`` and handed as the ``.t()`` view to ONE aggregation launch for all heads.  Head ``h`` of the output is in columns
-    ``h * in_dim / K ..``.
+    ``inputs``: ``l[n, s, h] = <inputs[n, head h], a_l[s, h]>``, ``r`` likewise, stacked to ``[N, H_sel, K]``; then
+    :func:`hop_edge_scores_heads`, :func:`hop_softmax_heads` and ONE aggregation launch, every link one launch for all heads on
+    entry-major ``[nnz_k, K]`` arrays (the layout the aggregation and its adjoint read fastest).  The bits are those of the
+    per-head chain (:func:`hop_edge_scores`, :func:`hop_softmax` per head, stacked as ``[K, nnz_k].t()``), which a single head and
+    a library that predates the head-batched calls still run.  Head ``h`` of the output is in columns ``h * in_dim / K ..``.
 
     Because the coefficients are an argument of the launch, such layers can be stacked on one plan (the K propagation rounds of
     H2GCN run on the same ``adj_hops``), share it with a ``GCNLayer``, and their training step can be captured in a hipGraph after
@@ -395,6 +501,16 @@ class MultiHeadHopAttention(torch.nn.Module):
         if inputs.dim() != 2 or inputs.shape[1] != self.in_dim:
             raise ValueError(f"inputs must be [{adjhops.n_cols}, {self.in_dim}], got {tuple(inputs.shape)}")
         n_heads, w = self.heads, self.in_dim // self.heads
+        if n_heads > 1 and _capi.has("h2gcn_edge_scores_hops_heads_f32"):
+            # one launch per link: the per-head projections as before, stacked to [N, H_sel, K]; entry-major [nnz_k, K] from there on
+            ls, rs = [], []
+            for h in range(n_heads):
+                x_h = inputs[:, h * w:(h + 1) * w]
+                l, r = x_h @ self.a_l[:, h, :].t(), x_h @ self.a_r[:, h, :].t()
+                ls.append(l)
+                rs.append(r)
+            scores = hop_edge_scores_heads(adjhops, _StackHeads.apply(*ls), _StackHeads.apply(*rs), self.negative_slope, self.hops)
+            return hop_spmm_values(adjhops, inputs, hop_softmax_heads(adjhops, scores, self.hops), self.hops)
         alpha = []
         for h in range(n_heads):
             x_h = inputs if n_heads == 1 else inputs[:, h * w:(h + 1) * w]

@@ -548,6 +548,60 @@ int h2gcn_edge_scores_backward_hops_f32(const h2gcn_plan_t* plan, uint32_t hop_m
                                         float* dl_dev, int64_t lddl, float* dr_dev, int64_t lddr, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * The head dimension of the three calls above (added within ABI 5; found by symbol like them): the SDDMM, the row softmax and
+ * the edge scores for n_heads = K >= 1 heads in ONE launch each -- the links of the attention chain around
+ * h2gcn_spmm_hops_values_f32, which takes its heads in one launch already.
+ *
+ * Layout: every per-entry array of selected hop s is CONTIGUOUS ENTRY-MAJOR: element (e, h) at e * K + h, e in the entry order of
+ * colidx_dev[k]; nnz_k * K floats each (the layout h2gcn_spmm_hops_*values_f32 reads fastest: ldv_entry = K, ldv_head = 1).
+ * fp32 only.  Tables, NULL entries, aliasing and OVERWRITTEN outputs as in the single-head calls.
+ *
+ *   sddmm      dvals[s][e*K + h] = sum_{c in head h} dY[i*ldg_row + s*ldg_hop + c] * X[j*ldx + c]
+ *              head h owns the columns h*w .. (h+1)*w - 1, w = d / K.  Needs d % K == 0 and, for K > 1, w % 4 == 0 (the rule of
+ *              h2gcn_spmm_hops_values_f32); K == 1 takes any d.  dY / X / strides as for h2gcn_sddmm_hops_f32.
+ *   softmax    one softmax per (row, hop, head) segment: alpha[s][e*K + h] over the entries of e's row, head h alone; backward
+ *              likewise.  alpha_dev[s] == scores_dev[s] and dscores_dev[s] == dalpha_dev[s] are allowed.
+ *   scores     l_dev [n_rows, H_sel, K]: element (i, s, h) at i*ldl + s*K + h, ldl >= H_sel*K; r_dev, dl_dev, dr_dev likewise
+ *              (ldr, lddl, lddr >= H_sel*K).  score[s][e*K + h] = leaky(l[i, s, h] + r[j, s, h]); dl[i, s, h] / dr[j, s, h] are the
+ *              row / column sums of t[e, h].  Either of dl_dev / dr_dev may be NULL (both NULL is an error).  The column side has
+ *              the plan requirements and the two refusals of h2gcn_edge_scores_backward_hops_f32 (H2GCN_ERR_NO_TRANSPOSE;
+ *              H2GCN_ERR_INVALID_ARGUMENT naming H2GCN_PLAN_KEEP_PERMUTATION), before the device is touched and before the
+ *              row side runs.
+ *
+ * Arithmetic: NOTHING NEW.  For every head h the bits equal those of the single-head entry point applied to head h alone:
+ *   h2gcn_sddmm_hops_heads_f32            = h2gcn_sddmm_hops_f32 with d := w on the head's column slice of dY and X;
+ *   h2gcn_row_softmax*_hops_heads_f32     = h2gcn_row_softmax*_hops_f32 on a contiguous copy of column h;
+ *   h2gcn_edge_scores*_hops_heads_f32     = h2gcn_edge_scores*_hops_f32 on l[:, :, h] and r[:, :, h].
+ * The bit-invariance and error-bound statements of those calls carry over per (segment, head) / (entry, head): the bits do not
+ * depend on long_row_threshold, rows_per_wave, variant, the hop selection or on which kernel geometry served the launch; the
+ * SDDMM's bound is gamma_w * sum_c |g_c x_c| + w * 2^-149, the softmax and edge-score bounds are unchanged.
+ * Non-finite inputs stay inside their (segment, head) or (entry, head): a NaN in head h never changes a bit of another head.
+ * Empty segments write nothing (softmax) or +0 (dl, dr).  No atomics, no workspace, all offsets 64-bit.
+ *
+ * hipGraph capture: the rule of the single-head calls (the long-segment lists of the selection: the forward launch's for the
+ * SDDMM, the softmax, the scores and dl, the adjoint launch's for dr).
+ *
+ * Validation, all before the device is touched, each H2GCN_ERR_INVALID_ARGUMENT with a message naming the argument: a NULL
+ * plan ("plan is NULL"), a hop mask outside the plan, n_heads < 1, d % n_heads != 0, w % 4 != 0 with n_heads > 1, ldx / ldg_row /
+ * ldg_hop smaller than d, ldl / ldr / lddl / lddr smaller than H_sel * n_heads, a NULL operand or table when the selection has
+ * nonzeros, a NULL entry of a selected hop that has nonzeros, dl and dr both NULL.
+ */
+int h2gcn_sddmm_hops_heads_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* dY_dev, int64_t ldg_row, int64_t ldg_hop,
+                               const float* X_dev, int64_t ldx, int32_t d, int32_t n_heads, float* const* dvals_dev, void* stream);
+int h2gcn_row_softmax_hops_heads_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* const* scores_dev,
+                                     float* const* alpha_dev, int32_t n_heads, void* stream);
+int h2gcn_row_softmax_backward_hops_heads_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* const* alpha_dev,
+                                              const float* const* dalpha_dev, float* const* dscores_dev, int32_t n_heads,
+                                              void* stream);
+int h2gcn_edge_scores_hops_heads_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* l_dev, int64_t ldl,
+                                     const float* r_dev, int64_t ldr, int32_t n_heads, float negative_slope,
+                                     float* const* scores_dev, void* stream);
+int h2gcn_edge_scores_backward_hops_heads_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* l_dev, int64_t ldl,
+                                              const float* r_dev, int64_t ldr, int32_t n_heads, float negative_slope,
+                                              const float* const* dscores_dev, float* dl_dev, int64_t lddl, float* dr_dev,
+                                              int64_t lddr, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * The hop aggregation on values that are an ARGUMENT of the launch, with an optional head dimension (added within ABI 5;
  * found by symbol like the launches above) -- the last link of the attention chain without h2gcn_plan_set_values:
  *
