@@ -15,6 +15,8 @@ C ABI of ``include/h2gcn_hip.h``).  It mirrors the reference's operator interfac
   on one plan (new);
 * :func:`h2gcn_amd.layers.hop_edge_scores_heads` / :func:`h2gcn_amd.layers.hop_softmax_heads` -- scores and softmax for all heads
   in one launch each on entry-major ``[nnz_k, K]`` arrays, the links ``MultiHeadHopAttention`` chains (new);
+* :func:`h2gcn_amd.layers.hop_attention_heads` -- scores, softmax and aggregation of all heads in ONE launch for every forward
+  that needs no gradient (the chain's bits, no per-entry array) (new);
 * :class:`h2gcn_amd.hops.HopPlan` -- the device-resident ``adj_hops`` operand list
   (reference ``h2gcn/datasets/_dataset.py:559-576``);
 * :mod:`h2gcn_amd.operands` -- construction of the normalised exact-k-hop matrices: on the device with the HIP ring
@@ -42,4 +44,4 @@ __version__ = "0.6.0"
 from . import _capi  # noqa: F401  (does not load the library until first use)
 from .hops import HopPlan, RowSelection  # noqa: F401
 from .layers import (ConcatLayer, DropoutDense, GCNLayer, HopAttention, MultiHeadHopAttention, SliceLayer, SparseDense, SparseDropout,  # noqa: F401
-                     hop_edge_scores, hop_edge_scores_heads, hop_softmax, hop_softmax_heads, hop_spmm, hop_spmm_values)
+                     hop_attention_heads, hop_edge_scores, hop_edge_scores_heads, hop_softmax, hop_softmax_heads, hop_spmm, hop_spmm_values)

@@ -1,0 +1,618 @@
+// attention_fused.hip -- the forward of the attention chain in ONE launch, for every forward that needs no gradient:
+//
+//     Y[i, s, c] = sum_e alpha_s[e, h(c)] * X[j_e, c]          e over row i of selected hop s, h(c) = c / (d / K)
+//     alpha_s[., h] = softmax over the segment of leaky(l[i, s, h] + r[j_e, s, h])
+//
+// what h2gcn_edge_scores_hops_heads_f32 -> h2gcn_row_softmax_hops_heads_f32 -> h2gcn_spmm_hops_values_f32 compute through two
+// entry-major [nnz_k, K] arrays, BIT FOR BIT, without those arrays: nothing of size nnz is written or allocated, the only store
+// is Y.  A translation unit of its own: no existing kernel is compiled differently because of it.
+//
+// Why the bits are the chain's.  Every value the chain stores is a function of operands this kernel also has, so it is computed
+// again with the chain's own operations wherever it is needed (include/h2gcn_hip.h has the three orders):
+//   * score = leaky(l + r): one addition, one multiplication on the `pre > 0`-false branch -- per (entry, head), no order;
+//   * m: a maximum has no order; a NaN score is carried in a flag beside it, per head, and makes m NaN;
+//   * e_j = exp2((score_j - m) * log2e), the one hardware exponential; P[j mod 256] accumulated from +0 in ascending j -- a lane
+//     that is entry j mod 64 of chunk j / 64 keeps P[64 u + lane] for the chunks = u (mod 4); W_u the xor butterfly over
+//     P[64u .. 64u+63]; S = (W_0 + W_1) + (W_2 + W_3); one correctly rounded 1/S; alpha_j = e_j * (1/S), e_j recomputed by the same
+//     two operations.  A partial that got no entry is +0 and adds no bit, so W_u of an absent chunk class is skipped;
+//   * the aggregation is spmm_values.hip's walk with the loads of V[e, h] replaced by reads of alpha: entry jj of a chunk goes
+//     into P[jj & 3] of lane group jj & 3 with one fmaf, the element is (P0 + P1) + (P2 + P3), long segments ((T0 + T1) + T2) + T3.
+//
+// Mapping (gfx950, wave64; the pattern walk of pattern_walk.hip.h; no atomics, no scratch, no workspace):
+//   * a segment belongs to the wave that owns its row, a segment of the plan's long list to a workgroup whose wave w takes the
+//     chunks = w (mod 4): exactly the owner of W_w in the softmax tree and of T_w in the aggregation tree;
+//   * walk A, lane = entry: colidx 64 at a time, r[j, s, h0 .. h0+3] in one 16-byte gather, FOUR heads per pass (the head group);
+//     per head group one sweep for the maxima and one for the partial sums; (m, 1/S) of all heads go to 2 K floats of LDS;
+//   * a segment of at most 64 entries (most of them) is one chunk: its scores stay in registers between the sweeps and the
+//     coefficients e * (1/S) go straight into the tile -- one exponential per (entry, head);
+//   * segments of at most 16 entries take walk A FOUR AT A TIME, lane group gi the segment of row i0 + gi: the reductions stay
+//     inside the 16-lane group (DPP only), the colidx / r latencies of four segments overlap, and group gi's coefficients are the
+//     entries 16 gi .. of the tile; walk B then serves the four segments in turn;
+//   * walk B, per chunk: lane = entry writes the K coefficients of its entry into the wave's 64 x K LDS tile (entry-major, as the
+//     chain's array), then the geometry of spmm_values.hip -- 16 lanes x 4 columns per 64-column block, group gi the entries
+//     = gi (mod 4) -- reads tile[n * K + head] where that kernel loads V: the staged tile saves 16 redundant exponentials per
+//     (entry, head).  Column ids are fetched once per chunk (lane = entry) and handed out with ds_bpermute;
+//   * a width beyond 256 columns repeats walk B per column pass, never walk A.
+// LDS: 4 tiles of 64 x 16 floats (16 KiB) + statistics and cross-wave words (1 KiB) + the long path's wave totals (1 - 4 KiB).
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include <cstring>
+
+#include "pattern_walk.hip.h"
+
+namespace h2gcn {
+namespace attention_fused {
+
+using namespace pattern;
+constexpr int kBlockCols = 64;   // columns one lane group covers per load: 16 lanes x 4
+constexpr int kMaxBlocks = 4;    // 64-column blocks of accumulators a lane keeps (one column pass: 256 columns)
+constexpr int kLoads = 8;        // gather instructions in flight per batch of rounds (8 KiB per wave)
+constexpr int kMaxHeads = 16;    // K beyond it is refused: the tile is 64 x kMaxHeads floats per wave
+constexpr int kPartials = 256;   // partial sums of a softmax segment: entry j belongs to P[j mod 256]
+constexpr int kGroup = 16;       // lanes of a lane group
+
+struct Params {
+    Geom geom;
+    const int32_t* colidx[H2GCN_MAX_HOPS];   // the selected hops, packed as geom.rowptr
+    const float* l;                          // [n_rows, n_sel, K]: element (i, s, h) at i * ldl + s * K + h
+    const float* r;                          // [n_cols, n_sel, K]
+    const float* x;                          // [n_cols, d] through ldx
+    float* y;                                // [n_rows, n_sel, d] through ldy_row / ldy_hop
+    int64_t ldl, ldr, ldx, ldy_row, ldy_hop;
+    int d, K, head_cols;                     // head_cols = d / K
+    float slope;
+};
+
+// The LDS of a block.  NB: 64-column blocks of a column pass.
+template <int NB>
+struct Shared {
+    float tile[kWavesPerBlock][kWave * kMaxHeads];   // per wave: alpha of the chunk at hand, element (n, h) at n * K + h
+    float stat[kWavesPerBlock][2 * kMaxHeads];       // per wave (long path: [0]): m of head h at [h], 1/S at [kMaxHeads + h]
+    float red[2][kWavesPerBlock][4];                 // long path: wave maxima / wave totals of the head group at hand
+    float tot[kWavesPerBlock][NB * kBlockCols];      // long path: the wave totals of one column pass
+};
+
+typedef float float4u __attribute__((ext_vector_type(4), aligned(4)));   // 16-byte accesses need only dword alignment on gfx950
+
+struct Quad {
+    float v[4];
+};
+
+// Columns c0 .. c0+3 of a feature row; columns >= d read as +0 and are never loaded.
+__device__ __forceinline__ Quad load_quad(const float* row, int c0, int d) {
+    Quad r;
+    if (c0 + 3 < d) {
+        const float4u t = *reinterpret_cast<const float4u*>(row + c0);
+        r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) r.v[k] = c0 + k < d ? row[c0 + k] : 0.f;
+    }
+    return r;
+}
+__device__ __forceinline__ void store_quad(float* row, int c0, int d, const Quad& r) {
+    if (c0 + 3 < d) {
+        float4u t;
+        t.x = r.v[0]; t.y = r.v[1]; t.z = r.v[2]; t.w = r.v[3];
+        *reinterpret_cast<float4u*>(row + c0) = t;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (c0 + k < d) row[c0 + k] = r.v[k];
+    }
+}
+
+// ---- the softmax's own operations, as attention_heads.hip writes them
+// v[lane] op v[lane ^ 16], then the same over lane ^ 32: the last two steps of the xor butterfly.  v_permlane16_swap / v_permlane32_swap
+// hand a lane its partner's value without an LDS round trip; both operations commute, so which of the pair comes first is the same
+// bits (the maximum up to the sign of a zero, which no exponential sees: score - (+-0) differs from score only for score = +-0,
+// and exp2 of either zero is 1).
+template <typename Op>
+__device__ __forceinline__ float bfly_groups(float v) {
+    unsigned u = __float_as_uint(v);
+    auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+    v = Op::op(__uint_as_float(a[0]), __uint_as_float(a[1]));
+    u = __float_as_uint(v);
+    auto b = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+    return Op::op(__uint_as_float(b[0]), __uint_as_float(b[1]));
+}
+__device__ __forceinline__ float bfly64_add(float v) { return bfly_groups<Add>(bfly16<Add>(v)); }
+struct Max {   // (drops NaN like v_max_f32: the callers carry NaN in a flag of their own)
+    static __device__ __forceinline__ float op(float a, float b) { return fmaxf(a, b); }
+};
+__device__ __forceinline__ float bfly64_max(float v) { return bfly_groups<Max>(bfly16<Max>(v)); }
+__device__ __forceinline__ float exp_t(float t) { return __builtin_amdgcn_exp2f(t * 1.44269504088896340736f); }
+__device__ __forceinline__ float quiet_nan() { return __int_as_float(0x7fc00000); }
+__device__ __forceinline__ float neg_inf() { return __int_as_float((int)0xff800000u); }
+__device__ __forceinline__ float leaky(float pre, float slope) { return pre > 0.f ? pre : pre * slope; }
+
+// What one lane writes into LDS another lane of the same wave reads next: a wave's LDS operations complete in order, the fence
+// keeps the compiler from moving them across.
+__device__ __forceinline__ void wave_lds_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// Heads h0 .. h0 + nh - 1 (nh in 1..4, wave-uniform) of a node row at `row` (its head 0): absent heads read as +0.
+__device__ __forceinline__ void load_heads(const float* row, int h0, int nh, float (&v)[4]) {
+    float a, b = 0.f, c = 0.f, e = 0.f;
+    if (nh == 4) {
+        const float4u t = *reinterpret_cast<const float4u*>(row + h0);
+        a = t.x, b = t.y, c = t.z, e = t.w;
+    } else {
+        a = row[h0];
+        if (nh > 1) b = row[h0 + 1];
+        if (nh > 2) c = row[h0 + 2];
+    }
+    v[0] = a, v[1] = b, v[2] = c, v[3] = e;
+}
+
+// The scores of the head group of the entry whose column is `col`: lv = l[i, s, h0 ..].
+__device__ __forceinline__ void group_scores(const Params& p, int s, int col, int h0, int nh, const float (&lv)[4], float (&sc)[4]) {
+    float rv[4];
+    load_heads(p.r + (int64_t)col * p.ldr + (int64_t)s * p.K, h0, nh, rv);
+#pragma unroll
+    for (int k = 0; k < 4; ++k) sc[k] = leaky(lv[k] + rv[k], p.slope);
+}
+
+// (m, 1/S) of heads h0 .. h0 + nh - 1 of a segment of `len` >= 1 entries whose column ids start at `cols`, on NW waves: NW = 1 the
+// calling wave alone; NW = 4 every thread of the block must call, wave w takes the chunks = w (mod 4) and `red` is free again on
+// return.  All lanes return the same values.
+template <int NW>
+__device__ __forceinline__ void group_stats(const Params& p, int s, const int32_t* cols, int64_t len, int h0, int nh, const float (&lv)[4],
+                                            int lane, int wave, float (*red)[kWavesPerBlock][4], float (&m)[4], float (&rinv)[4]) {
+    constexpr int NA = 4 / NW;   // partials a lane keeps per head
+    const int64_t first = NW == 1 ? 0 : (int64_t)wave * kWave;
+    float mx[4];
+    bool nn[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) mx[k] = neg_inf(), nn[k] = false;
+    for (int64_t j0 = first; j0 < len; j0 += NW * kWave) {   // (wave-uniform)
+        const bool ok = j0 + lane < len;
+        float sc[4];
+        group_scores(p, s, cols[ok ? j0 + lane : j0], h0, nh, lv, sc);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (ok) {
+                mx[k] = fmaxf(mx[k], sc[k]);
+                nn[k] = nn[k] || sc[k] != sc[k];
+            }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        m[k] = 0.f;
+        if (k >= nh) continue;   // (wave-uniform)
+        m[k] = bfly64_max(mx[k]);
+        if (__ballot(nn[k]) != 0ull) m[k] = quiet_nan();
+    }
+    if (NW > 1) {
+        if (lane == 0) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) red[0][wave][k] = m[k];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float m0 = red[0][0][k], m1 = red[0][1][k], m2 = red[0][2][k], m3 = red[0][3][k];
+            m[k] = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
+            if (m0 != m0 || m1 != m1 || m2 != m2 || m3 != m3) m[k] = quiet_nan();
+        }
+    }
+    float acc[NA][4];
+#pragma unroll
+    for (int u = 0; u < NA; ++u)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[u][k] = 0.f;
+    for (int64_t base = 0; base < len; base += kPartials) {
+#pragma unroll
+        for (int u = 0; u < NA; ++u) {   // ascending j within every partial
+            const int64_t j0 = base + (NW == 1 ? u * kWave : first);
+            if (j0 >= len) continue;   // (wave-uniform)
+            const bool ok = j0 + lane < len;
+            float sc[4];
+            group_scores(p, s, cols[ok ? j0 + lane : j0], h0, nh, lv, sc);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) acc[u][k] = acc[u][k] + (ok ? exp_t(sc[k] - m[k]) : 0.f);
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        rinv[k] = 0.f;
+        if (k >= nh) continue;   // (wave-uniform)
+        float S;
+        if (NW == 1) {
+            float W[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                W[u] = 0.f;
+                if ((int64_t)u * kWave < len) W[u] = bfly64_add(acc[u < NA ? u : 0][k]);   // (wave-uniform; partials of +0 sum to +0)
+            }
+            S = (W[0] + W[1]) + (W[2] + W[3]);
+        } else {
+            const float Ww = bfly64_add(acc[0][k]);
+            if (lane == 0) red[1][wave][k] = Ww;
+            __syncthreads();
+            S = (red[1][0][k] + red[1][1][k]) + (red[1][2][k] + red[1][3][k]);
+        }
+        rinv[k] = 1.0f / S;
+    }
+    if (NW > 1) __syncthreads();   // the next head group's words must not overtake this one's reads
+}
+
+// A segment of `len` in 1..64 entries, lane = entry (col: its column, clamped): the coefficients of all heads into `tile`.
+__device__ __forceinline__ void single_chunk_tile(const Params& p, int s, const float* lrow, int col, int len, int lane, float* tile) {
+    const bool ok = lane < len;
+    for (int h0 = 0; h0 < p.K; h0 += 4) {
+        const int nh = p.K - h0 < 4 ? p.K - h0 : 4;   // (wave-uniform)
+        float lv[4], sc[4];
+        load_heads(lrow, h0, nh, lv);
+        group_scores(p, s, col, h0, nh, lv, sc);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (k >= nh) continue;   // (wave-uniform)
+            const float x = ok ? sc[k] : neg_inf();
+            float m = bfly64_max(x);
+            if (__ballot(x != x) != 0ull) m = quiet_nan();
+            const float e = ok ? exp_t(x - m) : 0.f;   // P[lane] = +0 + e, the partials 64 .. 255 are +0
+            const float S = bfly64_add(e);             // = (W_0 + 0) + (0 + 0)
+            const float a = e * (1.0f / S);
+            if (ok) tile[lane * p.K + h0 + k] = a;
+        }
+    }
+}
+
+// Lane group gi = lane >> 4 of a step at row i0: the segment of row i0 + gi in selected hop s.  n = -1: no such row, or a segment
+// of the plan's long list.
+__device__ __forceinline__ void group_segment(const Geom& g, int s, int i0, int64_t row0, int64_t rp, int lane, int64_t* beg, int64_t* n) {
+    const int rpw = g.rows_per_wave;
+    const int i = i0 + (lane >> 4);
+    const int src = rp_lane(g, s, i < rpw ? i : rpw - 1);
+    *beg = bpermute64(rp, src);
+    int64_t len = bpermute64(rp, src + 1) - *beg;
+    if (i >= rpw || row0 + i >= g.n_rows || len >= g.long_threshold) len = -1;
+    *n = len;
+}
+
+// Up to FOUR segments of at most 16 entries at once, lane group gi the segment of row `row` (per lane: its group's), lane q its
+// entry q: `len` in 0..16 entries from `beg` (0: the group has no such segment).  The reductions stay inside the 16-lane group --
+// the partials 16 .. 255 are +0, and W_0 + 0 adds no bit -- and the coefficients of group gi go to the entries 16 gi .. of `tile`.
+// Returns the column of the lane's entry.
+__device__ __forceinline__ int short_tiles(const Params& p, int s, int64_t row, int64_t beg, int len, int lane, float* tile) {
+    const bool ok = (lane & (kGroup - 1)) < len;
+    int col = 0;
+    if (ok) col = p.colidx[s][beg + (lane & (kGroup - 1))];
+    const float* lrow = p.l + row * p.ldl + (int64_t)s * p.K;
+    const float* rrow = p.r + (int64_t)col * p.ldr + (int64_t)s * p.K;
+    for (int h0 = 0; h0 < p.K; h0 += 4) {
+        const int nh = p.K - h0 < 4 ? p.K - h0 : 4;   // (wave-uniform)
+        float lv[4] = {0.f, 0.f, 0.f, 0.f}, rv[4] = {0.f, 0.f, 0.f, 0.f};
+        if (ok) {
+            load_heads(lrow, h0, nh, lv);
+            load_heads(rrow, h0, nh, rv);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (k >= nh) continue;   // (wave-uniform)
+            const float x = ok ? leaky(lv[k] + rv[k], p.slope) : neg_inf();
+            const unsigned long long nan_lanes = __ballot(x != x);
+            float m = bfly16<Max>(x);
+            if ((nan_lanes >> (lane & 48)) & 0xffffull) m = quiet_nan();
+            const float e = ok ? exp_t(x - m) : 0.f;   // P[q] = +0 + e
+            const float S = bfly16<Add>(e);            // = W_0
+            const float a = e * (1.0f / S);
+            if (ok) tile[lane * p.K + h0 + k] = a;
+        }
+    }
+    return col;
+}
+
+// The coefficients of `count` (1..64) entries of a longer segment, lane = entry (col: its column, clamped), from the segment's
+// statistics `stat`: e and alpha by the operations that produced S.
+__device__ __forceinline__ void chunk_tile(const Params& p, int s, const float* lrow, int col, int count, int lane, const float* stat,
+                                           float* tile) {
+    const bool ok = lane < count;
+    for (int h0 = 0; h0 < p.K; h0 += 4) {
+        const int nh = p.K - h0 < 4 ? p.K - h0 : 4;   // (wave-uniform)
+        float lv[4], sc[4];
+        load_heads(lrow, h0, nh, lv);
+        group_scores(p, s, col, h0, nh, lv, sc);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (k >= nh) continue;   // (wave-uniform)
+            const float a = exp_t(sc[k] - stat[h0 + k]) * stat[kMaxHeads + h0 + k];
+            if (ok) tile[lane * p.K + h0 + k] = a;
+        }
+    }
+}
+
+// sum over the lanes {l, l^16}, then {l, l^32}: (P[gi] + P[gi^1]) + (P[gi^2] + P[gi^3])
+__device__ __forceinline__ float fold_groups(float v) { return bfly_groups<Add>(v); }
+
+// One batch of U rounds of a chunk: group gi serves entry 4r + gi in round r.  FULL: every round of the batch exists.  All the
+// gathers of the batch go out before its first FMA; an entry beyond `count` loads (a clamped, valid address) and adds nothing.
+template <int NB, int U, bool FULL>
+__device__ __forceinline__ void batch(const Params& p, const float* tile, const int (&head)[NB], int cbase, int r0, int rounds, int count,
+                                      int ecol, int lane0, int lane, Quad (&acc)[NB]) {
+    const int q = lane & 15, gi = lane >> 4;
+    Quad xv[U][NB];
+    float vv[U][NB];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        if (FULL || r0 + u < rounds) {
+            const int n = 4 * (r0 + u) + gi < count ? 4 * (r0 + u) + gi : count - 1;
+            const int c = __builtin_amdgcn_ds_bpermute((lane0 + n) << 2, ecol);
+            const float* xrow = p.x + (int64_t)c * p.ldx;
+#pragma unroll
+            for (int b = 0; b < NB; ++b) vv[u][b] = tile[n * p.K + head[b]];
+#pragma unroll
+            for (int b = 0; b < NB; ++b) xv[u][b] = load_quad(xrow, cbase + b * kBlockCols + 4 * q, p.d);
+        }
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        if (FULL || r0 + u < rounds) {
+            if (4 * (r0 + u) + gi < count) {
+#pragma unroll
+                for (int b = 0; b < NB; ++b)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) acc[b].v[k] = __builtin_fmaf(vv[u][b], xv[u][b].v[k], acc[b].v[k]);
+            }
+        }
+    }
+}
+
+// `count` (1..64) consecutive entries whose coefficients are in `tile` (entry n at n * K) and whose columns are in `ecol` of the
+// lanes lane0 + n: every entry goes into the partial of its group, in ascending order.  All 64 lanes must be active.
+template <int NB, int U>
+__device__ __forceinline__ void gather_chunk(const Params& p, const float* tile, const int (&head)[NB], int cbase, int count, int ecol,
+                                             int lane0, int lane, Quad (&acc)[NB]) {
+    const int rounds = (count + 3) >> 2;
+    int r0 = 0;
+    for (; r0 + U <= rounds; r0 += U) batch<NB, U, true>(p, tile, head, cbase, r0, rounds, count, ecol, lane0, lane, acc);
+    if (r0 < rounds) batch<NB, U, false>(p, tile, head, cbase, r0, rounds, count, ecol, lane0, lane, acc);
+}
+
+// The head of every block of the pass for this lane's quad (a quad beyond d: the last head, its sums are never stored).
+template <int NB>
+__device__ __forceinline__ void pass_heads(const Params& p, int cbase, int q, int (&head)[NB]) {
+#pragma unroll
+    for (int b = 0; b < NB; ++b) {
+        const int h = (cbase + b * kBlockCols + 4 * q) / p.head_cols;
+        head[b] = h < p.K ? h : p.K - 1;
+    }
+}
+
+template <int NB>
+__device__ __forceinline__ void clear(Quad (&acc)[NB]) {
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[b].v[k] = 0.f;
+}
+
+// (P0 + P1) + (P2 + P3) of every accumulator; returns the quad of block gi (the one this lane's group stores).
+template <int NB>
+__device__ __forceinline__ Quad fold_blocks(const Quad (&acc)[NB], int gi) {
+    Quad mine;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) mine.v[k] = 0.f;
+#pragma unroll
+    for (int b = 0; b < NB; ++b)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const float t = fold_groups(acc[b].v[k]);
+            if (gi == b) mine.v[k] = t;
+        }
+    return mine;
+}
+
+// The statistics of all heads of a segment of `len` >= 1 entries into `stat` (see group_stats for NW).
+template <int NW>
+__device__ __forceinline__ void segment_stats(const Params& p, int s, const float* lrow, const int32_t* cols, int64_t len, int lane,
+                                              int wave, float (*red)[kWavesPerBlock][4], float* stat) {
+    for (int h0 = 0; h0 < p.K; h0 += 4) {
+        const int nh = p.K - h0 < 4 ? p.K - h0 : 4;   // (wave-uniform)
+        float lv[4], m[4], rinv[4];
+        load_heads(lrow, h0, nh, lv);
+        group_stats<NW>(p, s, cols, len, h0, nh, lv, lane, wave, red, m, rinv);
+        if (lane == 0 && (NW == 1 || wave == 0)) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                if (k < nh) stat[h0 + k] = m[k], stat[kMaxHeads + h0 + k] = rinv[k];
+        }
+    }
+}
+
+template <int NB>
+__global__ __launch_bounds__(kBlock) void attention_fused_kernel(const Params p) {
+    constexpr int U = kLoads / NB;
+    constexpr int kPassCols = NB * kBlockCols;
+    __shared__ Shared<NB> sh;
+    const int lane = threadIdx.x & (kWave - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int q = lane & 15, gi = lane >> 4;
+    float* tile = sh.tile[wave];
+    int head[NB];
+    Quad acc[NB];
+    const bool one_pass = p.d <= kPassCols;   // the heads of the lane's blocks are then the same for every segment
+    pass_heads(p, 0, q, head);
+    int64_t row, beg, end;
+    int s;
+    if (long_segment(p.geom, blockIdx.x, &row, &s, &beg, &end)) {
+        // ---- a long segment: 64-entry chunks over the 4 waves ----
+        const int64_t len = end - beg;   // (the same for the whole block)
+        const float* lrow = p.l + row * p.ldl + (int64_t)s * p.K;
+        const int32_t* cols = p.colidx[s] + beg;
+        float* out = p.y + row * p.ldy_row + (int64_t)s * p.ldy_hop;
+        if (len > 0) segment_stats<kWavesPerBlock>(p, s, lrow, cols, len, lane, wave, sh.red, sh.stat[0]);
+        __syncthreads();
+        for (int cbase = 0; cbase < p.d; cbase += kPassCols) {
+            clear(acc);
+            if (!one_pass) pass_heads(p, cbase, q, head);
+            for (int64_t c = (int64_t)wave * kWave; c < len; c += kBlock) {
+                const int count = (int)(len - c < kWave ? len - c : kWave);
+                const int ecol = cols[c + (lane < count ? lane : count - 1)];
+                wave_lds_sync();   // the previous chunk's reads of the tile come first
+                chunk_tile(p, s, lrow, ecol, count, lane, sh.stat[0], tile);
+                wave_lds_sync();
+                gather_chunk<NB, U>(p, tile, head, cbase, count, ecol, 0, lane, acc);
+            }
+            const Quad mine = fold_blocks(acc, gi);
+            if (gi < NB) {
+#pragma unroll
+                for (int k = 0; k < 4; ++k) sh.tot[wave][gi * kBlockCols + 4 * q + k] = mine.v[k];
+            }
+            __syncthreads();
+            const int c = threadIdx.x;
+            if (c < kPassCols && cbase + c < p.d) out[cbase + c] = ((sh.tot[0][c] + sh.tot[1][c]) + sh.tot[2][c]) + sh.tot[3][c];
+            __syncthreads();
+        }
+        return;
+    }
+    // ---- the tile walk: each wave walks rows_per_wave consecutive rows ----
+    int64_t row0, rp;
+    if (!wave_rows(p.geom, blockIdx.x, wave, lane, &row0, &rp)) return;
+    float* stat = sh.stat[wave];
+    const int rpw = p.geom.rows_per_wave;
+    for (s = 0; s < p.geom.n_sel; ++s) {
+        for (int i0 = 0; i0 < rpw && row0 + i0 < p.geom.n_rows; i0 += 4) {
+            // lane group gi looks at row i0 + gi: segments of at most 16 entries get their coefficients FOUR AT A TIME
+            int64_t gbeg, glen;
+            group_segment(p.geom, s, i0, row0, rp, lane, &gbeg, &glen);
+            const bool is_short = glen >= 1 && glen <= kGroup;
+            int ecol = 0;
+            wave_lds_sync();   // the previous segments' reads of the tile come first
+            if (__ballot(is_short) != 0ull) ecol = short_tiles(p, s, row0 + i0 + gi, gbeg, is_short ? (int)glen : 0, lane, tile);
+            wave_lds_sync();
+#pragma unroll 1
+            for (int k = 0; k < 4; ++k) {
+                const int64_t len = readlane64(glen, k * kGroup);
+                if (len < 0 || len > kGroup) continue;   // (wave-uniform) no such row, a long segment, or one for the loop below
+                float* out = p.y + (row0 + i0 + k) * p.ldy_row + (int64_t)s * p.ldy_hop;
+                for (int cbase = 0; cbase < p.d; cbase += kPassCols) {
+                    clear(acc);
+                    if (!one_pass) pass_heads(p, cbase, q, head);
+                    if (len > 0) gather_chunk<NB, U>(p, tile + k * kGroup * p.K, head, cbase, (int)len, ecol, k * kGroup, lane, acc);
+                    const Quad mine = fold_blocks(acc, gi);   // (an empty segment: +0)
+                    if (gi < NB) store_quad(out, cbase + gi * kBlockCols + 4 * q, p.d, mine);
+                }
+            }
+            // the longer segments of these rows, one at a time on the whole wave
+#pragma unroll 1
+            for (int k = 0; k < 4; ++k) {
+                const int64_t len = readlane64(glen, k * kGroup);
+                if (len <= kGroup) continue;   // (wave-uniform)
+                beg = readlane64(gbeg, k * kGroup);
+                const float* lrow = p.l + (row0 + i0 + k) * p.ldl + (int64_t)s * p.K;
+                const int32_t* cols = p.colidx[s] + beg;
+                float* out = p.y + (row0 + i0 + k) * p.ldy_row + (int64_t)s * p.ldy_hop;
+                const bool single = len <= kWave;   // (wave-uniform)
+                wave_lds_sync();   // the previous segment's reads of the tile and of the statistics come first
+                if (single) {
+                    ecol = cols[lane < len ? lane : len - 1];
+                    single_chunk_tile(p, s, lrow, ecol, (int)len, lane, tile);
+                } else {
+                    segment_stats<1>(p, s, lrow, cols, len, lane, 0, nullptr, stat);
+                }
+                wave_lds_sync();
+                for (int cbase = 0; cbase < p.d; cbase += kPassCols) {
+                    clear(acc);
+                    if (!one_pass) pass_heads(p, cbase, q, head);
+                    if (single) {
+                        gather_chunk<NB, U>(p, tile, head, cbase, (int)len, ecol, 0, lane, acc);
+                    } else {
+                        for (int64_t c = 0; c < len; c += kWave) {
+                            const int count = (int)(len - c < kWave ? len - c : kWave);
+                            ecol = cols[c + (lane < count ? lane : count - 1)];
+                            wave_lds_sync();
+                            chunk_tile(p, s, lrow, ecol, count, lane, stat, tile);
+                            wave_lds_sync();
+                            gather_chunk<NB, U>(p, tile, head, cbase, count, ecol, 0, lane, acc);
+                        }
+                    }
+                    const Quad mine = fold_blocks(acc, gi);
+                    if (gi < NB) store_quad(out, cbase + gi * kBlockCols + 4 * q, p.d, mine);
+                }
+            }
+        }
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------ host
+int run(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* l, int64_t ldl, const float* r, int64_t ldr, int32_t n_heads, float slope,
+        const float* X, int64_t ldx, int32_t d, float* Y, int64_t ldy_row, int64_t ldy_hop, void* stream_v) {
+    try {
+        // every check below comes before the device is touched
+        PatternView v;
+        int st = pattern_view(plan, hop_mask, &v);
+        if (st != H2GCN_OK) return st;
+        if (d < 1) return fail(H2GCN_ERR_INVALID_ARGUMENT, "d = %d", d);
+        if (n_heads < 1) return fail(H2GCN_ERR_INVALID_ARGUMENT, "n_heads = %d < 1", n_heads);
+        if (n_heads > kMaxHeads)
+            return fail(H2GCN_ERR_INVALID_ARGUMENT, "n_heads = %d > %d: the fused attention forward serves at most %d heads (run the chain)",
+                        n_heads, kMaxHeads, kMaxHeads);
+        if (d % n_heads) return fail(H2GCN_ERR_INVALID_ARGUMENT, "d = %d is not a multiple of n_heads = %d", d, n_heads);
+        if (n_heads > 1 && (d / n_heads) % 4)
+            return fail(H2GCN_ERR_INVALID_ARGUMENT, "d / n_heads = %d is not a multiple of 4 (a lane's four columns must lie in one head)",
+                        d / n_heads);
+        const int64_t need = (int64_t)v.n_sel * n_heads;
+        if (ldl < need) return fail(H2GCN_ERR_INVALID_ARGUMENT, "ldl = %lld < H_sel * n_heads = %lld", (long long)ldl, (long long)need);
+        if (ldr < need) return fail(H2GCN_ERR_INVALID_ARGUMENT, "ldr = %lld < H_sel * n_heads = %lld", (long long)ldr, (long long)need);
+        if (ldx < d) return fail(H2GCN_ERR_INVALID_ARGUMENT, "ldx = %lld < d = %d", (long long)ldx, d);
+        if (ldy_row < d) return fail(H2GCN_ERR_INVALID_ARGUMENT, "ldy_row = %lld < d = %d", (long long)ldy_row, d);
+        if (ldy_hop < 0 || (v.n_sel > 1 && ldy_hop < d))
+            return fail(H2GCN_ERR_INVALID_ARGUMENT, "ldy_hop = %lld < d = %d: hop outputs would overlap", (long long)ldy_hop, d);
+        if (v.n_rows == 0) return H2GCN_OK;   // nothing to store
+        if (!Y) return fail(H2GCN_ERR_INVALID_ARGUMENT, "Y is NULL");
+        if (selected_nnz(v) > 0 && !l) return fail(H2GCN_ERR_INVALID_ARGUMENT, "l is NULL");
+        if (selected_nnz(v) > 0 && !r) return fail(H2GCN_ERR_INVALID_ARGUMENT, "r is NULL");
+        if (selected_nnz(v) > 0 && !X) return fail(H2GCN_ERR_INVALID_ARGUMENT, "X is NULL");
+        if (Y == X) return fail(H2GCN_ERR_INVALID_ARGUMENT, "Y aliases X");
+        if (Y == l) return fail(H2GCN_ERR_INVALID_ARGUMENT, "Y aliases l");
+        if (Y == r) return fail(H2GCN_ERR_INVALID_ARGUMENT, "Y aliases r");
+        hipStream_t stream = (hipStream_t)stream_v;
+        Params p;
+        memset(&p, 0, sizeof(p));
+        int64_t n_blocks;
+        if ((st = launch_geometry(plan, v, stream, &p.geom, &n_blocks)) != H2GCN_OK) return st;
+        if (n_blocks == 0) {   // a selection without nonzeros: every row is empty
+            for (int s = 0; s < v.n_sel; ++s)
+                H2GCN_HIP_TRY(hipMemset2DAsync(Y + (int64_t)s * ldy_hop, (size_t)ldy_row * sizeof(float), 0, (size_t)d * sizeof(float),
+                                               (size_t)v.n_rows, stream));
+            return H2GCN_OK;
+        }
+        for (int s = 0; s < v.n_sel; ++s) p.colidx[s] = v.colidx[s];
+        p.l = l, p.ldl = ldl;
+        p.r = r, p.ldr = ldr;
+        p.x = X, p.ldx = ldx;
+        p.y = Y, p.ldy_row = ldy_row, p.ldy_hop = ldy_hop;
+        p.d = d, p.K = n_heads, p.head_cols = d / n_heads;
+        p.slope = slope;
+        const dim3 grid((unsigned)n_blocks), block(kBlock);
+        // blocks of accumulators a lane keeps: the narrowest geometry that covers d in one column pass, four blocks beyond 256 columns
+        // (the bits are the same for all three: every column has its own tree)
+        if (d <= kBlockCols) hipLaunchKernelGGL((attention_fused_kernel<1>), grid, block, 0, stream, p);
+        else if (d <= 2 * kBlockCols) hipLaunchKernelGGL((attention_fused_kernel<2>), grid, block, 0, stream, p);
+        else hipLaunchKernelGGL((attention_fused_kernel<kMaxBlocks>), grid, block, 0, stream, p);
+        H2GCN_HIP_TRY(hipGetLastError());
+        return H2GCN_OK;
+    } catch (...) {
+        return fail(H2GCN_ERR_INTERNAL, "unexpected exception in attention_hops_heads_f32");
+    }
+}
+
+}  // namespace attention_fused
+}  // namespace h2gcn
+
+extern "C" {
+
+int h2gcn_attention_hops_heads_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* l_dev, int64_t ldl, const float* r_dev,
+                                   int64_t ldr, int32_t n_heads, float negative_slope, const float* X_dev, int64_t ldx, int32_t d,
+                                   float* Y_dev, int64_t ldy_row, int64_t ldy_hop, void* stream) {
+    return h2gcn::attention_fused::run(plan, hop_mask, l_dev, ldl, r_dev, ldr, n_heads, negative_slope, X_dev, ldx, d, Y_dev, ldy_row,
+                                       ldy_hop, stream);
+}
+
+}  // extern "C"

@@ -902,6 +902,62 @@ class HopPlan:
         _capi.check(st)
         return dl, dr
 
+    #: the largest K the fused attention forward serves (``h2gcn_attention_hops_heads_f32``); beyond it the chain is the way
+    ATTENTION_FUSED_MAX_HEADS = 16
+
+    def attention_heads(self, x: torch.Tensor, l: torch.Tensor, r: torch.Tensor, negative_slope: float = 0.2, hops=None,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The attention forward in ONE launch: ``out[i, s, c] = sum_e alpha_s[e, h(c)] * x[j_e, c]`` with ``alpha_s[:, h]`` the
+        softmax over row ``i`` of ``leaky_relu(l[i, s, h] + r[j, s, h], negative_slope)`` -> ``[n_rows, H_sel, d]``
+        (``h2gcn_attention_hops_heads_f32``).  The bits are those of :meth:`edge_scores_heads` -> :meth:`row_softmax_heads` ->
+        :meth:`spmm_values` on the same operands, but no ``[nnz_k, K]`` array exists: the launch allocates nothing and writes only
+        ``out``.  Forward only (no gradient flows through it); only the forward pattern is read, the plan's values are not.
+
+        ``l`` ``[n_rows, H_sel, K]``, ``r`` ``[n_cols, H_sel, K]``, ``x`` ``[n_cols, d]``: float32 on the plan's device; row strides
+        pass through.  ``1 <= K <= 16``; ``K > 1`` needs ``d % K == 0`` and ``(d // K) % 4 == 0``.  ``out``: float32 ``[n_rows,
+        H_sel, d]`` with a contiguous last dimension (a view into a wider buffer is fine: its strides pass through) that overlaps
+        none of the inputs."""
+        _require(isinstance(x, torch.Tensor) and x.dim() == 2, f"inputs must be [n_cols, d], got shape {tuple(getattr(x, 'shape', ()))}")
+        _require(x.dtype == torch.float32, f"inputs must be float32 (the fused attention forward is fp32 only), got {x.dtype}")
+        _require(x.device == self.device, f"inputs on {x.device}, plan on {self.device}")
+        _require(x.shape[0] == self.n_cols, f"inputs have {x.shape[0]} rows, hop matrices have {self.n_cols} columns")
+        d = int(x.shape[1])
+        _require(d >= 1, "inputs need at least one column")
+        mask, sel = self._mask(hops), self._selected(hops)
+        h_sel = len(sel)
+        l, ldl, n_heads = self._node_heads_operand("l", l, self.n_rows, h_sel)
+        r, ldr, _ = self._node_heads_operand("r", r, self.n_cols, h_sel, n_heads)
+        _require(n_heads <= self.ATTENTION_FUSED_MAX_HEADS,
+                 f"the fused attention forward serves at most K = {self.ATTENTION_FUSED_MAX_HEADS} heads, got K = {n_heads}: run the chain "
+                 "(edge_scores_heads, row_softmax_heads, spmm_values)")
+        _require(d % n_heads == 0, f"the width d = {d} is not a multiple of the number of heads K = {n_heads}")
+        _require(n_heads == 1 or (d // n_heads) % 4 == 0,
+                 f"with K = {n_heads} > 1 heads the head width d / K = {d // n_heads} must be a multiple of 4")
+        if (d > 1 and x.stride(1) != 1) or (self.n_cols > 1 and x.stride(0) < d):
+            x = x.contiguous()
+        if out is not None:
+            _require(isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.device == self.device,
+                     "out must be float32 on the plan's device")
+            _require(tuple(out.shape) == (self.n_rows, h_sel, d), f"out has shape {tuple(out.shape)}, expected {(self.n_rows, h_sel, d)}")
+            _require(d == 1 or out.stride(2) == 1, "out's last dimension must be contiguous")
+            _require((self.n_rows <= 1 or out.stride(0) >= d) and (h_sel == 1 or out.stride(1) >= d), "out's rows / hop slots overlap")
+            for name, t in (("the inputs", x), ("l", l), ("r", r)):
+                _require(not self._overlap(out, t), f"out overlaps {name}: the launch gathers rows of x and r while it stores rows of out")
+        if not _capi.has("h2gcn_attention_hops_heads_f32"):
+            raise RuntimeError(f"{_capi.library_path()} predates the fused attention forward (h2gcn_attention_hops_heads_f32): rebuild it")
+        if out is None:
+            out = torch.empty((self.n_rows, h_sel, d), dtype=torch.float32, device=self.device)
+        if self.n_rows == 0:
+            return out
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            st = _capi.lib().h2gcn_attention_hops_heads_f32(
+                self._handle, mask, C.c_void_p(l.data_ptr()), ldl, C.c_void_p(r.data_ptr()), ldr, n_heads, float(negative_slope),
+                C.c_void_p(x.data_ptr()), x.stride(0) if self.n_cols > 1 else d, d, C.c_void_p(out.data_ptr()),
+                out.stride(0) if self.n_rows > 1 else h_sel * d, out.stride(1) if h_sel > 1 else d, C.c_void_p(stream))
+        _capi.check(st)
+        return out
+
     def __del__(self):
         h = getattr(self, "_handle", None)
         if h is not None and h.value:

@@ -383,6 +383,34 @@ def hop_edge_scores_heads(adjhops: HopPlan, l: torch.Tensor, r: torch.Tensor, ne
     return tuple(adjhops.edge_scores_heads(l, r, negative_slope, hops=sel))
 
 
+def hop_attention_heads(adjhops: HopPlan, inputs: torch.Tensor, l: torch.Tensor, r: torch.Tensor, negative_slope: float = 0.2,
+                        hops: Optional[Iterable[int]] = None) -> torch.Tensor:
+    """Multi-head attention over the hop pattern, scores to aggregation: ``[n_cols, d] -> [n_rows, H_sel, d]`` with
+    ``out[i, s, c] = sum_e alpha_s[e, h(c)] * inputs[j_e, c]``, ``alpha_s[:, h]`` the softmax over row ``i`` of
+    ``leaky_relu(l[i, s, h] + r[j, s, h], negative_slope)`` and ``h(c) = c // (d // K)`` -- what
+    ``hop_spmm_values(plan, inputs, hop_softmax_heads(plan, hop_edge_scores_heads(plan, l, r, slope, hops), hops), hops)`` computes.
+
+    When gradients are disabled, or none of ``inputs``, ``l``, ``r`` requires one, this is ONE launch
+    (:meth:`HopPlan.attention_heads`) that allocates nothing but its result: the two ``[nnz_k, K]`` arrays per hop of the chain
+    never exist.  Otherwise it IS the expression above, so the result is always differentiable, and it always has the same bits:
+    the launch reproduces the chain's arithmetic bit for bit.  For the same reason ``K > 16`` (which the launch refuses) and a
+    library that predates the launch take the chain as well, whatever the gradient mode.
+
+    ``l`` ``[n_rows, H_sel, K]``, ``r`` ``[n_cols, H_sel, K]``, ``inputs`` ``[n_cols, d]``: float32 on the plan's device;
+    ``K > 1`` needs ``d % K == 0`` and ``(d // K) % 4 == 0``.  Row-partitioned operands (``ShardedHops``) are not covered."""
+    if hasattr(adjhops, "aggregate"):
+        raise ValueError("hop_attention_heads is not supported on row-partitioned operands (ShardedHops): pass a single-GPU HopPlan")
+    if not isinstance(adjhops, HopPlan):
+        raise TypeError(f"adjhops must be a HopPlan, got {type(adjhops).__name__}")
+    sel = None if hops is None else tuple(sorted(set(int(h) for h in hops)))
+    wants_grad = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (inputs, l, r))
+    n_heads = int(l.shape[2]) if isinstance(l, torch.Tensor) and l.dim() == 3 else 1
+    if wants_grad or n_heads > HopPlan.ATTENTION_FUSED_MAX_HEADS or not _capi.has("h2gcn_attention_hops_heads_f32"):
+        scores = hop_edge_scores_heads(adjhops, l, r, negative_slope, sel)
+        return hop_spmm_values(adjhops, inputs, hop_softmax_heads(adjhops, scores, sel), sel)
+    return adjhops.attention_heads(inputs, l, r, negative_slope, hops=sel)
+
+
 class _StackHeads(torch.autograd.Function):
     """``torch.stack(per_head, dim=2)`` of ``K`` ``[N, H_sel]`` projections; the backward hands every head a CONTIGUOUS ``[N, H_sel]``
     gradient, the operand the per-head chain gave the projection's GEMMs (so they run as before, on the same bits)."""
@@ -466,7 +494,11 @@ class MultiHeadHopAttention(torch.nn.Module):
     H2GCN run on the same ``adj_hops``), share it with a ``GCNLayer``, and their training step can be captured in a hipGraph after
     one eager warm-up; the plan's stored values are neither read nor replaced.  ``heads=1`` computes what :class:`HopAttention`
     computes, bit for bit, without touching the plan.  Training needs a square plan built with ``build_transpose=True,
-    keep_permutation=True``, as for :class:`HopAttention`.  Row-partitioned operands (``ShardedHops``) are not covered."""
+    keep_permutation=True``, as for :class:`HopAttention`.  Row-partitioned operands (``ShardedHops``) are not covered.
+
+    The layer runs the chain in every gradient mode.  :func:`hop_attention_heads` computes the same bits in ONE launch without
+    the per-entry arrays for a forward that needs no gradient; the layer is not routed to it because the launch is not faster
+    than the chain at every measured shape: a caller short of memory calls it on the layer's projections."""
 
     SIGNATURE = ["adjhops", "inputs"]
 

@@ -658,6 +658,54 @@ int h2gcn_spmm_hops_T_values_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, co
                                  float* dX_dev, int64_t ldx, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * The forward of the attention chain in ONE launch (added within ABI 5; found by symbol like the launches above) -- for every
+ * forward that needs no gradient (validation and test passes, inference): scores, softmax and aggregation without the two
+ * entry-major [nnz_k, K] arrays the chain writes and reads back.  For every selected hop s, row i and column c, h = c / (d / K):
+ *
+ *     Y[i, s, c] = sum_e alpha_s[e, h] * X[j_e, c]                             e over row i of selected hop s
+ *     alpha_s[., h] = softmax over that segment of leaky(l[i, s, h] + r[j_e, s, h])
+ *
+ *   l_dev [n_rows, H_sel, K]: element (i, s, h) at i*ldl + s*K + h, ldl >= H_sel*K; r_dev [n_cols, H_sel, K] likewise through
+ *   ldr -- the operands of h2gcn_edge_scores_hops_heads_f32.  X_dev [n_cols, d] through ldx; Y_dev [n_rows, H_sel, d] through
+ *   ldy_row / ldy_hop -- those of h2gcn_spmm_hops_values_f32.  n_heads = K: K == 1 takes any d; K > 1 needs d % K == 0 and
+ *   (d / K) % 4 == 0; K <= 16 is served, a larger K is refused with H2GCN_ERR_INVALID_ARGUMENT naming the limit (run the chain).
+ * The launch reads only rowptr / colidx: no transposes are needed, n_rows != n_cols is legal (sub-plans of selected rows), the
+ * plan's stored values are never read and nothing in the plan changes.  No workspace, no atomics, no allocation; all offsets
+ * 64-bit; fp32 only.  Every element of Y is written; an empty segment stores +0.  Forward only: there is no backward, the chain
+ * is what training runs.
+ *
+ * THE CONTRACT IS THE CHAIN'S BITS.  For every head, Y equals bit for bit what these three launches give on the same operands:
+ *   1. h2gcn_edge_scores_hops_heads_f32      scores
+ *   2. h2gcn_row_softmax_hops_heads_f32      alpha
+ *   3. h2gcn_spmm_hops_values_f32            Y, with entry-major values (ldv_entry = K, ldv_head = 1)
+ * Nothing is new in the arithmetic; the three orders above are reproduced, every stored value recomputed by its own operations:
+ *   score    one fp32 addition, one multiplication on the `pre > 0`-false branch (a NaN pre takes the slope branch);
+ *   softmax  t_j = score_j - m; e_j = exp2(t_j * log2e) with the one hardware exponential; 256 partials P[j mod 256], each from
+ *            +0, accumulated in ascending j; W_w the xor butterfly over index distances 1..32 of P[64w .. 64w+63];
+ *            S = (W_0 + W_1) + (W_2 + W_3); one correctly rounded 1/S per segment; alpha_j = e_j * (1/S).  The butterfly is
+ *            defined on the partial's index: any lane placement with the same pairings gives the same bits;
+ *   non-finite: a NaN or a +inf score makes its segment NaN throughout, a segment of -inf only is NaN throughout, -inf next to
+ *            finite scores gives exactly +0; a head that holds a NaN never changes a bit of another head;
+ *   aggregation: the canonical tree -- entry jj of a 64-entry chunk goes into P[jj & 3] with one fmaf from +0, the element is
+ *            (P0 + P1) + (P2 + P3); a segment of the plan's long list is dealt in 64-entry chunks to 4 waves and the wave
+ *            totals are combined as ((T0 + T1) + T2) + T3; an explicit-zero coefficient still multiplies (0 * inf = NaN).
+ * The bits therefore do not depend on long_row_threshold, rows_per_wave, the hop selection or the kernel geometry, exactly as the
+ * chain's do not.  Where the chain's result is NaN this one is NaN; the payload is not specified.
+ *
+ * hipGraph capture: the rule of the forward launch (the long-segment list of the selection, built by the first launch of that
+ * selection; a launch that would have to build one during capture returns H2GCN_ERR_INVALID_ARGUMENT with the existing advice).
+ * A selection without nonzeros is a memset of the output.
+ *
+ * Validation, all before the device is touched, each H2GCN_ERR_INVALID_ARGUMENT with a message naming the argument: a NULL
+ * plan ("plan is NULL"), a hop mask outside the plan, d < 1, n_heads < 1, n_heads > 16, d % n_heads, (d / n_heads) % 4 with
+ * heads, ldl / ldr smaller than H_sel * n_heads, ldx / ldy_row smaller than d, an ldy_hop that makes the hop outputs overlap, a
+ * NULL Y, a NULL l / r / X when the selection has nonzeros, a Y that IS X, l or r.
+ */
+int h2gcn_attention_hops_heads_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* l_dev, int64_t ldl, const float* r_dev,
+                                   int64_t ldr, int32_t n_heads, float negative_slope, const float* X_dev, int64_t ldx, int32_t d,
+                                   float* Y_dev, int64_t ldy_row, int64_t ldy_hop, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Operand construction on the device: exact-k-hop neighbourhood rings and their normalisation -- the step that
  * FEEDS the aggregation.  Stands in for TransformSPAdj.nhoodSplit (reference h2gcn/datasets/_dataset.py:138-158:
  * `mt <- bin(mt @ (A + I))`, ring_k = mt_k - mt_{k-1}, a host SpGEMM in scipy) and TransformSPAdj.normalize
