@@ -39,7 +39,7 @@
 
 #include <cstring>
 
-#include "pattern_walk.hip.h"
+#include "segment_ops.hip.h"
 
 namespace h2gcn {
 namespace attention_fused {
@@ -49,8 +49,6 @@ constexpr int kBlockCols = 64;   // columns one lane group covers per load: 16 l
 constexpr int kMaxBlocks = 4;    // 64-column blocks of accumulators a lane keeps (one column pass: 256 columns)
 constexpr int kLoads = 8;        // gather instructions in flight per batch of rounds (8 KiB per wave)
 constexpr int kMaxHeads = 16;    // K beyond it is refused: the tile is 64 x kMaxHeads floats per wave
-constexpr int kPartials = 256;   // partial sums of a softmax segment: entry j belongs to P[j mod 256]
-constexpr int kGroup = 16;       // lanes of a lane group
 
 struct Params {
     Geom geom;
@@ -73,37 +71,7 @@ struct Shared {
     float tot[kWavesPerBlock][NB * kBlockCols];      // long path: the wave totals of one column pass
 };
 
-typedef float float4u __attribute__((ext_vector_type(4), aligned(4)));   // 16-byte accesses need only dword alignment on gfx950
-
-struct Quad {
-    float v[4];
-};
-
-// Columns c0 .. c0+3 of a feature row; columns >= d read as +0 and are never loaded.
-__device__ __forceinline__ Quad load_quad(const float* row, int c0, int d) {
-    Quad r;
-    if (c0 + 3 < d) {
-        const float4u t = *reinterpret_cast<const float4u*>(row + c0);
-        r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) r.v[k] = c0 + k < d ? row[c0 + k] : 0.f;
-    }
-    return r;
-}
-__device__ __forceinline__ void store_quad(float* row, int c0, int d, const Quad& r) {
-    if (c0 + 3 < d) {
-        float4u t;
-        t.x = r.v[0]; t.y = r.v[1]; t.z = r.v[2]; t.w = r.v[3];
-        *reinterpret_cast<float4u*>(row + c0) = t;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (c0 + k < d) row[c0 + k] = r.v[k];
-    }
-}
-
-// ---- the softmax's own operations, as attention_heads.hip writes them
+// ---- the last two butterfly steps of the softmax's reductions (the scalars and the 16-lane steps: segment_ops.hip.h)
 // v[lane] op v[lane ^ 16], then the same over lane ^ 32: the last two steps of the xor butterfly.  v_permlane16_swap / v_permlane32_swap
 // hand a lane its partner's value without an LDS round trip; both operations commute, so which of the pair comes first is the same
 // bits (the maximum up to the sign of a zero, which no exponential sees: score - (+-0) differs from score only for score = +-0,
@@ -118,14 +86,7 @@ __device__ __forceinline__ float bfly_groups(float v) {
     return Op::op(__uint_as_float(b[0]), __uint_as_float(b[1]));
 }
 __device__ __forceinline__ float bfly64_add(float v) { return bfly_groups<Add>(bfly16<Add>(v)); }
-struct Max {   // (drops NaN like v_max_f32: the callers carry NaN in a flag of their own)
-    static __device__ __forceinline__ float op(float a, float b) { return fmaxf(a, b); }
-};
 __device__ __forceinline__ float bfly64_max(float v) { return bfly_groups<Max>(bfly16<Max>(v)); }
-__device__ __forceinline__ float exp_t(float t) { return __builtin_amdgcn_exp2f(t * 1.44269504088896340736f); }
-__device__ __forceinline__ float quiet_nan() { return __int_as_float(0x7fc00000); }
-__device__ __forceinline__ float neg_inf() { return __int_as_float((int)0xff800000u); }
-__device__ __forceinline__ float leaky(float pre, float slope) { return pre > 0.f ? pre : pre * slope; }
 
 // What one lane writes into LDS another lane of the same wave reads next: a wave's LDS operations complete in order, the fence
 // keeps the compiler from moving them across.
@@ -261,18 +222,6 @@ __device__ __forceinline__ void single_chunk_tile(const Params& p, int s, const 
             if (ok) tile[lane * p.K + h0 + k] = a;
         }
     }
-}
-
-// Lane group gi = lane >> 4 of a step at row i0: the segment of row i0 + gi in selected hop s.  n = -1: no such row, or a segment
-// of the plan's long list.
-__device__ __forceinline__ void group_segment(const Geom& g, int s, int i0, int64_t row0, int64_t rp, int lane, int64_t* beg, int64_t* n) {
-    const int rpw = g.rows_per_wave;
-    const int i = i0 + (lane >> 4);
-    const int src = rp_lane(g, s, i < rpw ? i : rpw - 1);
-    *beg = bpermute64(rp, src);
-    int64_t len = bpermute64(rp, src + 1) - *beg;
-    if (i >= rpw || row0 + i >= g.n_rows || len >= g.long_threshold) len = -1;
-    *n = len;
 }
 
 // Up to FOUR segments of at most 16 entries at once, lane group gi the segment of row `row` (per lane: its group's), lane q its
@@ -480,7 +429,7 @@ __global__ __launch_bounds__(kBlock) void attention_fused_kernel(const Params p)
         for (int i0 = 0; i0 < rpw && row0 + i0 < p.geom.n_rows; i0 += 4) {
             // lane group gi looks at row i0 + gi: segments of at most 16 entries get their coefficients FOUR AT A TIME
             int64_t gbeg, glen;
-            group_segment(p.geom, s, i0, row0, rp, lane, &gbeg, &glen);
+            group_segment<false>(p.geom, s, i0, row0, rp, lane, &gbeg, &glen);
             const bool is_short = glen >= 1 && glen <= kGroup;
             int ecol = 0;
             wave_lds_sync();   // the previous segments' reads of the tile come first

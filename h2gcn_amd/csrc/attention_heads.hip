@@ -8,8 +8,8 @@
 //
 // A translation unit of its own: no existing kernel is compiled differently because of it.  Nothing is new in the arithmetic:
 // per head every call gives the bits of its single-head counterpart on that head alone (include/h2gcn_hip.h), because every
-// reduction below is the documented tree of that call -- the lane that holds an element and the order of the additions are
-// the same, only the address of element (e, h) differs.
+// reduction below is the documented tree of that call, from the one copy in segment_ops.hip.h -- the lane that holds an element
+// and the order of the additions are the same, only the address of element (e, h) differs.
 //
 // Mapping (gfx950, wave64; the pattern walk of pattern_walk.hip.h, no atomics, no scratch, no workspace):
 //   * softmax / score backward: the wave that owns a segment loops over the heads INSIDE the segment, so the K passes read lines
@@ -31,55 +31,12 @@
 
 #include <cstring>
 
-#include "pattern_walk.hip.h"
+#include "segment_ops.hip.h"
 
 namespace h2gcn {
 namespace heads {
 
 using namespace pattern;
-constexpr int kGroup = 16;       // lanes of a lane group
-constexpr int kPartials = 256;   // partial sums of a segment: entry j belongs to P[j mod 256]
-
-typedef float float4u __attribute__((ext_vector_type(4), aligned(4)));   // 16-byte accesses need only dword alignment on gfx950
-
-__device__ __forceinline__ float bfly64_add(float v) {
-    v = bfly16<Add>(v);
-    v = v + __shfl_xor(v, 16);
-    v = v + __shfl_xor(v, 32);
-    return v;
-}
-struct Max {   // (drops NaN like v_max_f32: the callers carry NaN in a flag of their own)
-    static __device__ __forceinline__ float op(float a, float b) { return fmaxf(a, b); }
-};
-__device__ __forceinline__ float bfly64_max(float v) {
-    v = bfly16<Max>(v);
-    v = fmaxf(v, __shfl_xor(v, 16));
-    v = fmaxf(v, __shfl_xor(v, 32));
-    return v;
-}
-__device__ __forceinline__ float exp_t(float t) { return __builtin_amdgcn_exp2f(t * 1.44269504088896340736f); }
-__device__ __forceinline__ float quiet_nan() { return __int_as_float(0x7fc00000); }
-__device__ __forceinline__ float neg_inf() { return __int_as_float((int)0xff800000u); }
-
-// Lane group gi = lane >> 4 of a step at row i0: the segment of row i0 + gi in selected hop s, as the single-head kernels cut
-// it.  n = -1: no such row, or a long segment (BY_ROW, the adjoint's list: a row that is long in ANY selected hop).
-template <bool BY_ROW>
-__device__ __forceinline__ void group_segment(const Geom& g, int s, int i0, int64_t row0, int64_t rp, int lane, int64_t* beg, int64_t* n) {
-    const int rpw = g.rows_per_wave;
-    const int i = i0 + (lane >> 4);
-    const int ic = i < rpw ? i : rpw - 1;
-    const int src = rp_lane(g, s, ic);
-    *beg = bpermute64(rp, src);
-    int64_t len = bpermute64(rp, src + 1) - *beg;
-    bool is_long = len >= g.long_threshold;
-    if (BY_ROW)
-        for (int s2 = 0; s2 < g.n_sel; ++s2) {
-            const int src2 = rp_lane(g, s2, ic);
-            is_long = is_long || bpermute64(rp, src2 + 1) - bpermute64(rp, src2) >= g.long_threshold;
-        }
-    if (i >= rpw || row0 + i >= g.n_rows || is_long) len = -1;
-    *n = len;
-}
 
 // ====================================================================================================== row softmax
 namespace softmax {
@@ -91,108 +48,6 @@ struct Params {
     float* out[H2GCN_MAX_HOPS];       // forward: alpha; backward: dscores
     int K;
 };
-
-// A segment of at most 16 entries of one head on the lane's own 16-lane group: x / y are entry q = lane & 15 (padding where !ok).
-template <bool BWD>
-__device__ __forceinline__ void seg16(float x, float y, bool ok, float* dst, int lane) {
-    if (!BWD) {
-        const unsigned long long nan_lanes = __ballot(x != x);
-        float m = bfly16<Max>(x);
-        if ((nan_lanes >> (lane & 48)) & 0xffffull) m = quiet_nan();
-        const float e = ok ? exp_t(x - m) : 0.f;   // P[q] = +0 + e
-        const float S = bfly16<Add>(e);            // = W_0: the partials 16 .. 255 are +0
-        const float r = 1.0f / S;
-        if (ok) *dst = e * r;
-    } else {
-        const float D = bfly16<Add>(__builtin_fmaf(x, y, 0.f));
-        if (ok) *dst = x * (y - D);
-    }
-}
-
-// One head of one segment of any length on NW waves: entry j at a[j * K] (the caller has added the head).  Lane l of accumulator /
-// wave w holds the partial P[64 w + l], accumulated in ascending j; a segment of at most NW * 256 entries stays in registers, a
-// longer one runs in passes.  NW = 4: every thread of the block must call, and `lds` is free again on return.
-template <bool BWD, int NW>
-__device__ __forceinline__ void head_segment(const float* a, const float* g, float* out, int64_t len, int64_t K, int lane, int wave, float* lds) {
-    constexpr int NA = 4 / NW;
-    constexpr int kSpan = NW * kPartials;
-    const int first = NW == 1 ? lane : wave * kWave + lane;
-    const bool single = len <= kSpan;   // (wave- and block-uniform)
-    float x[NW][NA], y[NW][NA];
-    auto index = [&](int64_t base, int c, int u) -> int64_t { return base + c * kPartials + first + u * kWave; };
-    auto fetch = [&](int64_t base) {
-#pragma unroll
-        for (int c = 0; c < NW; ++c)
-#pragma unroll
-            for (int u = 0; u < NA; ++u) {
-                const int64_t j = index(base, c, u);
-                x[c][u] = j < len ? a[j * K] : (BWD ? 0.f : neg_inf());
-                y[c][u] = BWD && j < len ? g[j * K] : 0.f;
-            }
-    };
-    if (single) fetch(0);
-    float m = 0.f;
-    if (!BWD) {
-        float mx = neg_inf();
-        bool nn = false;
-        for (int64_t base = 0; base < len; base += kSpan) {
-            if (!single) fetch(base);
-#pragma unroll
-            for (int c = 0; c < NW; ++c)
-#pragma unroll
-                for (int u = 0; u < NA; ++u) {
-                    mx = fmaxf(mx, x[c][u]);
-                    nn = nn || x[c][u] != x[c][u];
-                }
-        }
-        m = bfly64_max(mx);
-        if (__ballot(nn) != 0ull) m = quiet_nan();
-        if (NW > 1) {
-            if (lane == 0) lds[wave] = m;
-            __syncthreads();
-            const float m0 = lds[0], m1 = lds[1], m2 = lds[2], m3 = lds[3];
-            m = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
-            if (m0 != m0 || m1 != m1 || m2 != m2 || m3 != m3) m = quiet_nan();
-        }
-    }
-    float acc[NA];
-#pragma unroll
-    for (int u = 0; u < NA; ++u) acc[u] = 0.f;
-    for (int64_t base = 0; base < len; base += kSpan) {
-        if (!single) fetch(base);
-#pragma unroll
-        for (int c = 0; c < NW; ++c)   // ascending j within every partial
-#pragma unroll
-            for (int u = 0; u < NA; ++u) {
-                if (!BWD) acc[u] = acc[u] + (index(base, c, u) < len ? exp_t(x[c][u] - m) : 0.f);
-                else acc[u] = __builtin_fmaf(x[c][u], y[c][u], acc[u]);   // (beyond the segment: fma(0, 0, acc) = acc)
-            }
-    }
-    float T;
-    if (NW == 1) {
-        float W[NA];
-#pragma unroll
-        for (int u = 0; u < NA; ++u) W[u] = bfly64_add(acc[u]);
-        T = (W[0] + W[NA > 1 ? 1 : 0]) + (W[NA > 2 ? 2 : 0] + W[NA > 3 ? 3 : 0]);
-    } else {
-        const float Ww = bfly64_add(acc[0]);
-        if (lane == 0) lds[4 + wave] = Ww;
-        __syncthreads();
-        T = (lds[4] + lds[5]) + (lds[6] + lds[7]);
-    }
-    const float r = 1.0f / T;
-    for (int64_t base = 0; base < len; base += kSpan) {
-        if (!single) fetch(base);
-#pragma unroll
-        for (int c = 0; c < NW; ++c)
-#pragma unroll
-            for (int u = 0; u < NA; ++u) {
-                const int64_t j = index(base, c, u);
-                if (j < len) out[j * K] = BWD ? x[c][u] * (y[c][u] - T) : exp_t(x[c][u] - m) * r;
-            }
-    }
-    if (NW > 1) __syncthreads();   // the next head's wave totals must not overtake this head's reads
-}
 
 // A segment of at most 64 entries, up to FOUR heads per pass: lane `lane` holds entry `lane` of the heads h0 .. h0 + nh - 1 (one
 // 16-byte access when nh == 4) and the wave runs the single-head call's one-register reduction once per head, the four of them
@@ -224,13 +79,13 @@ __device__ __forceinline__ void seg64_heads(const float* a, const float* g, floa
     for (int k = 0; k < 4; ++k) {
         if (k >= nh) continue;   // (wave-uniform)
         if (!BWD) {
-            float m = bfly64_max(x[k]);
+            float m = bfly64<Max>(x[k]);
             if (__ballot(x[k] != x[k]) != 0ull) m = quiet_nan();
             const float e = ok ? exp_t(x[k] - m) : 0.f;
-            const float S = bfly64_add(e);   // = (W_0 + 0) + (0 + 0)
+            const float S = bfly64<Add>(e);   // = (W_0 + 0) + (0 + 0)
             o[k] = e * (1.0f / S);
         } else {
-            const float D = bfly64_add(__builtin_fmaf(x[k], y[k], 0.f));
+            const float D = bfly64<Add>(__builtin_fmaf(x[k], y[k], 0.f));
             o[k] = x[k] * (y[k] - D);
         }
     }
@@ -258,8 +113,8 @@ __global__ __launch_bounds__(kBlock) void row_softmax_heads_kernel(const Params 
     if (long_segment(p.geom, blockIdx.x, &row, &s, &beg, &end)) {
         if (end <= beg) return;   // (the same for the whole block)
         for (int h = 0; h < p.K; ++h)
-            head_segment<BWD, kWavesPerBlock>(p.a[s] + beg * K + h, BWD ? p.g[s] + beg * K + h : nullptr, p.out[s] + beg * K + h,
-                                              end - beg, K, lane, wave, lds);
+            loop_segment<BWD, kWavesPerBlock, true>(p.a[s] + beg * K + h, BWD ? p.g[s] + beg * K + h : nullptr, p.out[s] + beg * K + h,
+                                                    end - beg, K, lane, wave, lds);
         return;
     }
     int64_t row0, rp;
@@ -289,41 +144,9 @@ __global__ __launch_bounds__(kBlock) void row_softmax_heads_kernel(const Params 
                                      p.K - h0 < 4 ? p.K - h0 : 4, lane);
             } else {
                 for (int h = 0; h < p.K; ++h)
-                    head_segment<BWD, 1>(a + beg * K + h, BWD ? g + beg * K + h : nullptr, out + beg * K + h, len, K, lane, 0, nullptr);
+                    loop_segment<BWD, 1, true>(a + beg * K + h, BWD ? g + beg * K + h : nullptr, out + beg * K + h, len, K, lane, 0, nullptr);
             }
         }
-    }
-}
-
-template <bool BWD>
-int launch(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* const* a, const char* a_name, const float* const* g,
-           const char* g_name, float* const* out, const char* out_name, int32_t n_heads, void* stream_v) {
-    try {
-        // every check below comes before the device is touched
-        PatternView v;
-        int st = pattern_view(plan, hop_mask, &v);
-        if (st != H2GCN_OK) return st;
-        if (n_heads < 1) return fail(H2GCN_ERR_INVALID_ARGUMENT, "n_heads = %d < 1", n_heads);
-        if ((st = check_hop_arrays(v, a_name, a)) != H2GCN_OK) return st;
-        if (BWD && (st = check_hop_arrays(v, g_name, g)) != H2GCN_OK) return st;
-        if ((st = check_hop_arrays(v, out_name, out)) != H2GCN_OK) return st;
-        hipStream_t stream = (hipStream_t)stream_v;
-        Params p;
-        memset(&p, 0, sizeof(p));
-        int64_t n_blocks;
-        if ((st = launch_geometry(plan, v, stream, &p.geom, &n_blocks)) != H2GCN_OK) return st;
-        if (n_blocks == 0) return H2GCN_OK;
-        for (int s = 0; s < v.n_sel; ++s) {
-            p.a[s] = a[s];
-            p.g[s] = BWD ? g[s] : nullptr;
-            p.out[s] = out[s];
-        }
-        p.K = n_heads;
-        hipLaunchKernelGGL((row_softmax_heads_kernel<BWD>), dim3((unsigned)n_blocks), dim3(kBlock), 0, stream, p);
-        H2GCN_HIP_TRY(hipGetLastError());
-        return H2GCN_OK;
-    } catch (...) {
-        return fail(H2GCN_ERR_INTERNAL, "unexpected exception in row_softmax%s_hops_heads_f32", BWD ? "_backward" : "");
     }
 }
 
@@ -346,7 +169,6 @@ struct Params {
     float slope;
 };
 
-__device__ __forceinline__ float leaky(float pre, float slope) { return pre > 0.f ? pre : pre * slope; }
 
 // The K scores of one entry: self / other / dst at head 0 of the entry's (row, s) / (column, s) / own element.
 __device__ __forceinline__ void entry_scores(const float* self, const float* other, float* dst, int K, float slope) {
@@ -409,48 +231,6 @@ __device__ __forceinline__ float term(const Params& p, int s, int h, float self,
     return pre > 0.f ? g : g * p.slope;
 }
 
-// The sum of one head of a segment of any length n >= 0 on NW waves: the single-head call's tree.  NW = 4: every thread of the
-// block must call; `lds` is free for the next call on return.
-template <bool T, int NW>
-__device__ __forceinline__ float segment_sum(const Params& p, int s, int h, float self, int64_t beg, int64_t n, int lane, int wave, float* lds) {
-    constexpr int NA = 4 / NW;                             // accumulators per lane
-    constexpr int kStride = NW == 1 ? kWave : kPartials;   // between the four entries of a lane in one iteration
-    const int first = NW == 1 ? 0 : wave * kWave;          // (wave-uniform)
-    float acc[NA];
-#pragma unroll
-    for (int u = 0; u < NA; ++u) acc[u] = 0.f;
-    for (int64_t base = 0; base < n; base += 4 * kStride) {
-        float t[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const int64_t m0 = base + k * kStride + first;
-            t[k] = 0.f;
-            if (m0 < n) {   // (wave-uniform)
-                const bool ok = m0 + lane < n;
-                const float v = term<T>(p, s, h, self, beg + (ok ? m0 + lane : m0));
-                t[k] = ok ? v : 0.f;
-            }
-        }
-#pragma unroll
-        for (int k = 0; k < 4; ++k) acc[NW == 1 ? k : 0] = acc[NW == 1 ? k : 0] + t[k];   // ascending m within every partial
-    }
-    if (NW == 1) {
-        float W[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            W[u] = 0.f;
-            if (u * kWave < n) W[u] = bfly64_add(acc[u < NA ? u : 0]);   // (wave-uniform; a wave of +0 sums to +0)
-        }
-        return (W[0] + W[1]) + (W[2] + W[3]);
-    }
-    const float Ww = bfly64_add(acc[0]);
-    if (lane == 0) lds[wave] = Ww;
-    __syncthreads();
-    const float total = (lds[0] + lds[1]) + (lds[2] + lds[3]);
-    __syncthreads();
-    return total;
-}
-
 template <bool T>
 __global__ __launch_bounds__(kBlock) void edge_scores_heads_backward_kernel(const Params p) {
     __shared__ float lds[kWavesPerBlock];   // long segments: the wave totals
@@ -466,7 +246,8 @@ __global__ __launch_bounds__(kBlock) void edge_scores_heads_backward_kernel(cons
             const int64_t beg = p.geom.rowptr[s][row], end = p.geom.rowptr[s][row + 1];
             for (int h = 0; h < p.K; ++h) {
                 const float self = p.self[row * p.ld_self + s * K + h];
-                const float total = segment_sum<T, kWavesPerBlock>(p, s, h, self, beg, end - beg, lane, wave, lds);
+                const float total = segment_sum<kWavesPerBlock>([&](int64_t m) { return term<T>(p, s, h, self, beg + m); }, end - beg, lane,
+                                                                wave, lds);
                 if (threadIdx.x == 0) p.out[row * p.ld_out + s * K + h] = total;
             }
         }
@@ -522,13 +303,14 @@ __global__ __launch_bounds__(kBlock) void edge_scores_heads_backward_kernel(cons
                             const float sf = self[h0 + k];
                             const float pre = T ? ov[k] + sf : sf + ov[k];   // l[i] + r[j]
                             const float t = ok ? (pre > 0.f ? gv[k] : gv[k] * p.slope) : 0.f;
-                            const float total = bfly64_add(0.f + t);
+                            const float total = bfly64<Add>(0.f + t);
                             if (lane == 0) out[h0 + k] = total;
                         }
                     }
                 } else {
                     for (int h = 0; h < p.K; ++h) {
-                        const float total = segment_sum<T, 1>(p, s, h, self[h], beg, n, lane, 0, nullptr);
+                        const float sf = self[h];
+                        const float total = segment_sum<1>([&](int64_t m) { return term<T>(p, s, h, sf, beg + m); }, n, lane, 0, nullptr);
                         if (lane == 0) out[h] = total;
                     }
                 }
@@ -536,114 +318,8 @@ __global__ __launch_bounds__(kBlock) void edge_scores_heads_backward_kernel(cons
         }
 }
 
-int check_node_operands(const PatternView& v, int32_t K, const float* l, int64_t ldl, const float* r, int64_t ldr) {
-    const int64_t need = (int64_t)v.n_sel * K;
-    if (ldl < need) return fail(H2GCN_ERR_INVALID_ARGUMENT, "ldl = %lld < H_sel * n_heads = %lld", (long long)ldl, (long long)need);
-    if (ldr < need) return fail(H2GCN_ERR_INVALID_ARGUMENT, "ldr = %lld < H_sel * n_heads = %lld", (long long)ldr, (long long)need);
-    if (selected_nnz(v) > 0 && !l) return fail(H2GCN_ERR_INVALID_ARGUMENT, "l is NULL");
-    if (selected_nnz(v) > 0 && !r) return fail(H2GCN_ERR_INVALID_ARGUMENT, "r is NULL");
-    return H2GCN_OK;
-}
-
-void fill(Params* p, const PatternView& v, const float* self, int64_t ld_self, const float* other, int64_t ld_other, int32_t K, float slope) {
-    for (int s = 0; s < v.n_sel; ++s) p->idx[s] = v.colidx[s];
-    p->self = self, p->ld_self = ld_self;
-    p->other = other, p->ld_other = ld_other;
-    p->K = K;
-    p->slope = slope;
-}
-
-int forward(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* l, int64_t ldl, const float* r, int64_t ldr, int32_t n_heads,
-            float slope, float* const* scores, void* stream_v) {
-    try {
-        // every check below comes before the device is touched
-        PatternView v;
-        int st = pattern_view(plan, hop_mask, &v);
-        if (st != H2GCN_OK) return st;
-        if (n_heads < 1) return fail(H2GCN_ERR_INVALID_ARGUMENT, "n_heads = %d < 1", n_heads);
-        if ((st = check_node_operands(v, n_heads, l, ldl, r, ldr)) != H2GCN_OK) return st;
-        if ((st = check_hop_arrays(v, "scores", scores)) != H2GCN_OK) return st;
-        hipStream_t stream = (hipStream_t)stream_v;
-        Params p;
-        memset(&p, 0, sizeof(p));
-        int64_t n_blocks;
-        if ((st = launch_geometry(plan, v, stream, &p.geom, &n_blocks)) != H2GCN_OK) return st;
-        if (n_blocks == 0) return H2GCN_OK;
-        fill(&p, v, l, ldl, r, ldr, n_heads, slope);
-        for (int s = 0; s < v.n_sel; ++s) p.score[s] = scores[s];
-        hipLaunchKernelGGL(edge_scores_heads_kernel, dim3((unsigned)n_blocks), dim3(kBlock), 0, stream, p);
-        H2GCN_HIP_TRY(hipGetLastError());
-        return H2GCN_OK;
-    } catch (...) {
-        return fail(H2GCN_ERR_INTERNAL, "unexpected exception in edge_scores_hops_heads_f32");
-    }
-}
-
-// One side of the backward, in two steps so that both sides' refusals come before either side's launch.
-template <bool T>
-struct Side {
-    Params p;
-    int64_t n_blocks = 0;
-    int n_sel = 0;
-    int64_t n_rows = 0;
-
-    int prepare(const h2gcn_plan_t* plan, const PatternView& v, const uint32_t* const* perm, const float* self, int64_t ld_self,
-                const float* other, int64_t ld_other, int32_t K, float slope, const float* const* g, float* out, int64_t ld_out,
-                hipStream_t stream) {
-        memset(&p, 0, sizeof(p));
-        n_sel = v.n_sel, n_rows = v.n_rows;
-        p.K = K;
-        const int st = launch_geometry(plan, v, stream, &p.geom, &n_blocks, T);
-        if (st != H2GCN_OK || n_blocks == 0) {
-            p.out = out, p.ld_out = ld_out;
-            return st;
-        }
-        fill(&p, v, self, ld_self, other, ld_other, K, slope);
-        for (int s = 0; s < v.n_sel; ++s) p.g[s] = g[s], p.perm[s] = T ? perm[s] : nullptr;
-        p.out = out, p.ld_out = ld_out;
-        return H2GCN_OK;
-    }
-    int run(hipStream_t stream) {
-        if (n_blocks == 0) {   // a selection without nonzeros: every segment is empty
-            if (n_rows > 0)
-                H2GCN_HIP_TRY(hipMemset2DAsync(p.out, (size_t)p.ld_out * sizeof(float), 0, (size_t)n_sel * p.K * sizeof(float),
-                                               (size_t)n_rows, stream));
-            return H2GCN_OK;
-        }
-        hipLaunchKernelGGL((edge_scores_heads_backward_kernel<T>), dim3((unsigned)n_blocks), dim3(kBlock), 0, stream, p);
-        H2GCN_HIP_TRY(hipGetLastError());
-        return H2GCN_OK;
-    }
-};
-
-int backward(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* l, int64_t ldl, const float* r, int64_t ldr, int32_t n_heads,
-             float slope, const float* const* g, float* dl, int64_t lddl, float* dr, int64_t lddr, void* stream_v) {
-    try {
-        // every check below comes before the device is touched
-        PatternView v, tv;
-        const uint32_t* perm[H2GCN_MAX_HOPS] = {};
-        int st = pattern_view(plan, hop_mask, &v);
-        if (st != H2GCN_OK) return st;
-        if (n_heads < 1) return fail(H2GCN_ERR_INVALID_ARGUMENT, "n_heads = %d < 1", n_heads);
-        if (!dl && !dr) return fail(H2GCN_ERR_INVALID_ARGUMENT, "dl and dr are both NULL: nothing to compute");
-        if ((st = check_node_operands(v, n_heads, l, ldl, r, ldr)) != H2GCN_OK) return st;
-        const int64_t need = (int64_t)v.n_sel * n_heads;
-        if (dl && lddl < need) return fail(H2GCN_ERR_INVALID_ARGUMENT, "lddl = %lld < H_sel * n_heads = %lld", (long long)lddl, (long long)need);
-        if (dr && lddr < need) return fail(H2GCN_ERR_INVALID_ARGUMENT, "lddr = %lld < H_sel * n_heads = %lld", (long long)lddr, (long long)need);
-        if ((st = check_hop_arrays(v, "dscores", g)) != H2GCN_OK) return st;
-        if (dr && (st = adjoint_view(plan, hop_mask, &tv, perm)) != H2GCN_OK) return st;
-        hipStream_t stream = (hipStream_t)stream_v;
-        Side<false> rows;
-        Side<true> cols;
-        if (dl && (st = rows.prepare(plan, v, nullptr, l, ldl, r, ldr, n_heads, slope, g, dl, lddl, stream)) != H2GCN_OK) return st;
-        if (dr && (st = cols.prepare(plan, tv, perm, r, ldr, l, ldl, n_heads, slope, g, dr, lddr, stream)) != H2GCN_OK) return st;
-        if (dl && (st = rows.run(stream)) != H2GCN_OK) return st;
-        if (dr && (st = cols.run(stream)) != H2GCN_OK) return st;
-        return H2GCN_OK;
-    } catch (...) {
-        return fail(H2GCN_ERR_INTERNAL, "unexpected exception in edge_scores_backward_hops_heads_f32");
-    }
-}
+// the row side and the column side (named here, ahead of the SDDMM's kernels: the code object keeps its kernels in this order)
+constexpr Kernel<Params> kBackward[2] = {edge_scores_heads_backward_kernel<false>, edge_scores_heads_backward_kernel<true>};
 
 }  // namespace scores
 
@@ -662,30 +338,6 @@ struct Params {
     const float* x;                          // X, [n_cols, d] through ldx
     int64_t ldx;
 };
-
-struct Quad {
-    float v[4];
-};
-
-// Columns c0 .. c0+3 of a feature row whose width `d` is a multiple of 4: a quad is whole or reads as +0 and is never loaded.
-__device__ __forceinline__ Quad load_quad(const float* row, int c0, int d) {
-    Quad r;
-    r.v[0] = r.v[1] = r.v[2] = r.v[3] = 0.f;
-    if (c0 < d) {
-        const float4u t = *reinterpret_cast<const float4u*>(row + c0);
-        r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
-    }
-    return r;
-}
-
-// The quad value of the documented order: t = g0*x0, then fma(g1, x1, t), fma(g2, x2, t), fma(g3, x3, t).
-__device__ __forceinline__ float dot_quad(const Quad& g, const Quad& x) {
-    float t = g.v[0] * x.v[0];
-    t = __builtin_fmaf(g.v[1], x.v[1], t);
-    t = __builtin_fmaf(g.v[2], x.v[2], t);
-    t = __builtin_fmaf(g.v[3], x.v[3], t);
-    return t;
-}
 
 // The first steps of bfly16 over the L = w / 4 lanes of one head (an aligned run of L lanes): afterwards they all hold the sum
 // of the head's quads in the single-head call's order.  Its remaining steps would add quads of +0: v + (+0) changes no bit but
@@ -710,7 +362,7 @@ __device__ __forceinline__ void walk_chunk_packed(const Params& p, const float* 
     for (int cbase = 0; cbase < p.d; cbase += NB * kBlockCols) {
         Quad g[NB];
 #pragma unroll
-        for (int b = 0; b < NB; ++b) g[b] = load_quad(grow, cbase + b * kBlockCols + 4 * q, p.d);
+        for (int b = 0; b < NB; ++b) g[b] = load_quad<false>(grow, cbase + b * kBlockCols + 4 * q, p.d);
         float res[NB][kKeep];
 #pragma unroll
         for (int b = 0; b < NB; ++b)
@@ -726,7 +378,7 @@ __device__ __forceinline__ void walk_chunk_packed(const Params& p, const float* 
                         const int c = __builtin_amdgcn_ds_bpermute(((lane & 48) + r0 + u) << 2, mycol);
                         const float* xrow = p.x + (int64_t)c * p.ldx;
 #pragma unroll
-                        for (int b = 0; b < NB; ++b) xv[u][b] = load_quad(xrow, cbase + b * kBlockCols + 4 * q, p.d);
+                        for (int b = 0; b < NB; ++b) xv[u][b] = load_quad<false>(xrow, cbase + b * kBlockCols + 4 * q, p.d);
                     }
 #pragma unroll
                 for (int u = 0; u < U; ++u)
@@ -760,7 +412,7 @@ __device__ __forceinline__ float walk_chunk_head(const Params& p, const float* g
     for (int cbase = 0; cbase < p.w; cbase += NB * kBlockCols) {
         Quad g[NB];
 #pragma unroll
-        for (int b = 0; b < NB; ++b) g[b] = load_quad(grow, cbase + b * kBlockCols + 4 * q, p.w);
+        for (int b = 0; b < NB; ++b) g[b] = load_quad<false>(grow, cbase + b * kBlockCols + 4 * q, p.w);
         for (int r0 = 0; r0 < rounds; r0 += U) {
             Quad xv[U][NB];
 #pragma unroll
@@ -769,7 +421,7 @@ __device__ __forceinline__ float walk_chunk_head(const Params& p, const float* g
                     const int c = __builtin_amdgcn_ds_bpermute(((lane & 48) + r0 + u) << 2, mycol);
                     const float* xrow = x + (int64_t)c * p.ldx;
 #pragma unroll
-                    for (int b = 0; b < NB; ++b) xv[u][b] = load_quad(xrow, cbase + b * kBlockCols + 4 * q, p.w);
+                    for (int b = 0; b < NB; ++b) xv[u][b] = load_quad<false>(xrow, cbase + b * kBlockCols + 4 * q, p.w);
                 }
 #pragma unroll
             for (int u = 0; u < U; ++u)
@@ -890,6 +542,7 @@ int launch(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* dY, int64_t
 }  // namespace heads
 }  // namespace h2gcn
 
+
 extern "C" {
 
 int h2gcn_sddmm_hops_heads_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* dY_dev, int64_t ldg_row, int64_t ldg_hop,
@@ -899,26 +552,32 @@ int h2gcn_sddmm_hops_heads_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, cons
 
 int h2gcn_row_softmax_hops_heads_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* const* scores_dev,
                                      float* const* alpha_dev, int32_t n_heads, void* stream) {
-    return h2gcn::heads::softmax::launch<false>(plan, hop_mask, scores_dev, "scores", nullptr, "", alpha_dev, "alpha", n_heads, stream);
+    using namespace h2gcn::heads;
+    return softmax_launch<softmax::Params, true, false>(softmax::row_softmax_heads_kernel<false>, plan, hop_mask, scores_dev, "scores", nullptr, "",
+                                                        alpha_dev, "alpha", n_heads, stream);
 }
 
 int h2gcn_row_softmax_backward_hops_heads_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* const* alpha_dev,
                                               const float* const* dalpha_dev, float* const* dscores_dev, int32_t n_heads, void* stream) {
-    return h2gcn::heads::softmax::launch<true>(plan, hop_mask, alpha_dev, "alpha", dalpha_dev, "dalpha", dscores_dev, "dscores", n_heads,
-                                               stream);
+    using namespace h2gcn::heads;
+    return softmax_launch<softmax::Params, true, true>(softmax::row_softmax_heads_kernel<true>, plan, hop_mask, alpha_dev, "alpha", dalpha_dev,
+                                                       "dalpha", dscores_dev, "dscores", n_heads, stream);
 }
 
 int h2gcn_edge_scores_hops_heads_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* l_dev, int64_t ldl, const float* r_dev,
                                      int64_t ldr, int32_t n_heads, float negative_slope, float* const* scores_dev, void* stream) {
-    return h2gcn::heads::scores::forward(plan, hop_mask, l_dev, ldl, r_dev, ldr, n_heads, negative_slope, scores_dev, stream);
+    using namespace h2gcn::heads;
+    return scores_forward<scores::Params, true>(scores::edge_scores_heads_kernel, plan, hop_mask, l_dev, ldl, r_dev, ldr, n_heads, negative_slope,
+                                                scores_dev, stream);
 }
 
 int h2gcn_edge_scores_backward_hops_heads_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* l_dev, int64_t ldl,
                                               const float* r_dev, int64_t ldr, int32_t n_heads, float negative_slope,
                                               const float* const* dscores_dev, float* dl_dev, int64_t lddl, float* dr_dev,
                                               int64_t lddr, void* stream) {
-    return h2gcn::heads::scores::backward(plan, hop_mask, l_dev, ldl, r_dev, ldr, n_heads, negative_slope, dscores_dev, dl_dev, lddl,
-                                          dr_dev, lddr, stream);
+    using namespace h2gcn::heads;
+    return scores_backward<scores::Params, true>(scores::kBackward[0], scores::kBackward[1], plan, hop_mask, l_dev, ldl, r_dev, ldr, n_heads, negative_slope, dscores_dev, dl_dev, lddl, dr_dev,
+                                                 lddr, stream);
 }
 
 }  // extern "C"

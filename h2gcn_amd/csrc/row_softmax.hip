@@ -23,23 +23,20 @@
 //     and store -- backward two) that re-read from L2, four loads per lane in flight.
 //   All loads and stores are lane-contiguous; a lane writes only entries it has read (alpha may overwrite scores, dscore dalpha).
 //
-// Arithmetic (documented in include/h2gcn_hip.h): ONE order per segment, a function of its contents alone -- 256 partials
-// P[j mod 256] accumulated in ascending j, four 64-lane xor butterflies, (W0 + W1) + (W2 + W3).  A partial without an entry is +0
-// and adding +0 changes no bit here, which is why all the mappings above give the same bits.
+// Arithmetic (documented in include/h2gcn_hip.h): ONE order per segment, a function of its contents alone -- the tree of
+// segment_ops.hip.h, which is why all the mappings above give the same bits.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <cmath>
 #include <cstring>
 
-#include "pattern_walk.hip.h"
+#include "segment_ops.hip.h"
 
 namespace h2gcn {
 namespace row_softmax {
 
 using namespace pattern;
-constexpr int kGroup = 16;       // lanes of a lane group: the longest segment it serves
-constexpr int kPartials = 256;   // partial sums of a segment: entry j belongs to P[j mod 256]
 
 struct Params {
     Geom geom;
@@ -47,42 +44,6 @@ struct Params {
     const float* g[H2GCN_MAX_HOPS];          // backward: dalpha
     float* out[H2GCN_MAX_HOPS];              // forward: alpha; backward: dscores
 };
-
-struct Max {   // (drops NaN like v_max_f32: the callers carry NaN in a flag of their own)
-    static __device__ __forceinline__ float op(float a, float b) { return fmaxf(a, b); }
-};
-
-// the 16-lane xor butterfly, and on over distances 16 and 32: the 64 lanes of the wave
-template <typename Op>
-__device__ __forceinline__ float bfly64(float v) {
-    v = bfly16<Op>(v);
-    v = Op::op(v, __shfl_xor(v, 16));
-    v = Op::op(v, __shfl_xor(v, 32));
-    return v;
-}
-
-// THE exponential of every path: v_exp_f32 (2^x, 1 ulp) on the fp32 product t * log2(e)
-__device__ __forceinline__ float exp_t(float t) { return __builtin_amdgcn_exp2f(t * 1.44269504088896340736f); }
-
-__device__ __forceinline__ float quiet_nan() { return __int_as_float(0x7fc00000); }
-__device__ __forceinline__ float neg_inf() { return __int_as_float((int)0xff800000u); }
-
-// ---- a segment of at most 16 entries on the lane's own 16-lane group: x / y are entry q = lane & 15 (padding where !ok)
-template <bool BWD>
-__device__ __forceinline__ void seg16(float x, float y, bool ok, float* dst, int lane) {
-    if (!BWD) {
-        const unsigned long long nan_lanes = __ballot(x != x);
-        float m = bfly16<Max>(x);
-        if ((nan_lanes >> (lane & 48)) & 0xffffull) m = quiet_nan();
-        const float e = ok ? exp_t(x - m) : 0.f;    // P[q] = +0 + e
-        const float S = bfly16<Add>(e);              // = W_0: the partials 16 .. 255 are +0
-        const float r = 1.0f / S;
-        if (ok) *dst = e * r;
-    } else {
-        const float D = bfly16<Add>(__builtin_fmaf(x, y, 0.f));
-        if (ok) *dst = x * (y - D);
-    }
-}
 
 // ---- a segment of at most 64 entries on the wave, one register: x / y are entry `lane`
 template <bool BWD>
@@ -135,98 +96,6 @@ __device__ __forceinline__ void seg256(float (&x)[4], const float (&y)[4], float
     }
 }
 
-// ---- one segment of any length on NW waves (1: a wave of the tile walk, four accumulators per lane; 4: the workgroup of a long
-// segment, wave w taking the 64-entry chunks = w (mod 4), one accumulator per lane).  Either way lane l of accumulator / wave w
-// holds the partial P[64 w + l], accumulated in ascending j, and an iteration covers NW * 256 entries with FOUR loads per lane in
-// flight.  A segment that fits one iteration (256 entries on one wave, 1024 on the workgroup) stays in registers: one read, one
-// write; a longer one runs in passes (max; sum; recompute and store -- backward two) that re-read from L2.
-template <bool BWD, int NW>
-struct Span {
-    static constexpr int NA = 4 / NW;   // accumulators per lane
-    float x[NW][NA], y[NW][NA];
-    __device__ __forceinline__ int64_t index(int64_t base, int first, int c, int u) const { return base + c * kPartials + first + u * kWave; }
-    __device__ __forceinline__ void fetch(const float* a, const float* g, int64_t base, int first, int64_t len) {
-#pragma unroll
-        for (int c = 0; c < NW; ++c)
-#pragma unroll
-            for (int u = 0; u < NA; ++u) {
-                const int64_t j = index(base, first, c, u);
-                x[c][u] = j < len ? a[j] : (BWD ? 0.f : neg_inf());
-                y[c][u] = BWD && j < len ? g[j] : 0.f;
-            }
-    }
-};
-
-template <bool BWD, int NW>
-__device__ __forceinline__ void loop_segment(const float* a, const float* g, float* out, int64_t len, int lane, int wave, float* lds) {
-    constexpr int NA = 4 / NW;
-    constexpr int kSpan = NW * kPartials;
-    const int first = NW == 1 ? lane : wave * kWave + lane;
-    const bool single = len <= kSpan;   // (wave- and block-uniform)
-    Span<BWD, NW> sp;
-    if (single) sp.fetch(a, g, 0, first, len);
-    float m = 0.f;
-    if (!BWD) {
-        float mx = neg_inf();
-        bool nn = false;
-        for (int64_t base = 0; base < len; base += kSpan) {
-            if (!single) sp.fetch(a, g, base, first, len);
-#pragma unroll
-            for (int c = 0; c < NW; ++c)
-#pragma unroll
-                for (int u = 0; u < NA; ++u) {
-                    mx = fmaxf(mx, sp.x[c][u]);
-                    nn = nn || sp.x[c][u] != sp.x[c][u];
-                }
-        }
-        m = bfly64<Max>(mx);
-        if (__ballot(nn) != 0ull) m = quiet_nan();
-        if (NW > 1) {
-            if (lane == 0) lds[wave] = m;
-            __syncthreads();
-            const float m0 = lds[0], m1 = lds[1], m2 = lds[2], m3 = lds[3];
-            m = fmaxf(fmaxf(m0, m1), fmaxf(m2, m3));
-            if (m0 != m0 || m1 != m1 || m2 != m2 || m3 != m3) m = quiet_nan();
-        }
-    }
-    float acc[NA];
-#pragma unroll
-    for (int u = 0; u < NA; ++u) acc[u] = 0.f;
-    for (int64_t base = 0; base < len; base += kSpan) {
-        if (!single) sp.fetch(a, g, base, first, len);
-#pragma unroll
-        for (int c = 0; c < NW; ++c)       // ascending j within every partial
-#pragma unroll
-            for (int u = 0; u < NA; ++u) {
-                if (!BWD) acc[u] = acc[u] + (sp.index(base, first, c, u) < len ? exp_t(sp.x[c][u] - m) : 0.f);
-                else acc[u] = __builtin_fmaf(sp.x[c][u], sp.y[c][u], acc[u]);   // (beyond the segment: fma(0, 0, acc) = acc)
-            }
-    }
-    float T;
-    if (NW == 1) {
-        float W[NA];
-#pragma unroll
-        for (int u = 0; u < NA; ++u) W[u] = bfly64<Add>(acc[u]);
-        T = (W[0] + W[NA > 1 ? 1 : 0]) + (W[NA > 2 ? 2 : 0] + W[NA > 3 ? 3 : 0]);
-    } else {
-        const float Ww = bfly64<Add>(acc[0]);
-        if (lane == 0) lds[4 + wave] = Ww;
-        __syncthreads();
-        T = (lds[4] + lds[5]) + (lds[6] + lds[7]);
-    }
-    const float r = 1.0f / T;
-    for (int64_t base = 0; base < len; base += kSpan) {
-        if (!single) sp.fetch(a, g, base, first, len);
-#pragma unroll
-        for (int c = 0; c < NW; ++c)
-#pragma unroll
-            for (int u = 0; u < NA; ++u) {
-                const int64_t j = sp.index(base, first, c, u);
-                // (forward: the same instructions on the same operands as in the sum: the same e_j)
-                if (j < len) out[j] = BWD ? sp.x[c][u] * (sp.y[c][u] - T) : exp_t(sp.x[c][u] - m) * r;
-            }
-    }
-}
 
 // ---- the tile walk.  A STEP is four consecutive rows of one hop, lane group gi standing for row i0 + gi; its class is
 // wave-uniform.  step_begin reads the step's row pointers and, for the two register-light classes, issues its loads; the kernel
@@ -322,7 +191,7 @@ __device__ __forceinline__ void step_finish(const Params& p, Step& st, int lane)
                 load256<BWD>(a + bk, g + bk, nk, lane, x, y);
                 seg256<BWD>(x, y, out + bk, nk, lane);
             } else {
-                loop_segment<BWD, 1>(a + bk, g + bk, out + bk, nk, lane, 0, nullptr);
+                loop_segment<BWD, 1, false>(a + bk, g + bk, out + bk, nk, kUnitStride, lane, 0, nullptr);
             }
         }
     }
@@ -338,7 +207,8 @@ __global__ __launch_bounds__(kBlock) void row_softmax_hops_kernel(const Params p
     if (long_segment(p.geom, blockIdx.x, &row, &s, &beg, &end)) {
         // ---- a long segment: 64-entry chunks over the 4 waves ----
         if (end <= beg) return;   // (the same for the whole block)
-        loop_segment<BWD, kWavesPerBlock>(p.a[s] + beg, BWD ? p.g[s] + beg : nullptr, p.out[s] + beg, end - beg, lane, wave, lds);
+        loop_segment<BWD, kWavesPerBlock, false>(p.a[s] + beg, BWD ? p.g[s] + beg : nullptr, p.out[s] + beg, end - beg, kUnitStride, lane,
+                                                 wave, lds);
         return;
     }
     // ---- the tile walk: each wave walks rows_per_wave consecutive rows, four at a time ----
@@ -356,36 +226,6 @@ __global__ __launch_bounds__(kBlock) void row_softmax_hops_kernel(const Params p
     }
 }
 
-template <bool BWD>
-int launch(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* const* a, const char* a_name, const float* const* g,
-           const char* g_name, float* const* out, const char* out_name, void* stream_v) {
-    try {
-        // every check below comes before the device is touched
-        PatternView v;
-        int st = pattern_view(plan, hop_mask, &v);
-        if (st != H2GCN_OK) return st;
-        if ((st = check_hop_arrays(v, a_name, a)) != H2GCN_OK) return st;
-        if (BWD && (st = check_hop_arrays(v, g_name, g)) != H2GCN_OK) return st;
-        if ((st = check_hop_arrays(v, out_name, out)) != H2GCN_OK) return st;
-        hipStream_t stream = (hipStream_t)stream_v;
-        Params p;
-        memset(&p, 0, sizeof(p));
-        int64_t n_blocks;
-        if ((st = launch_geometry(plan, v, stream, &p.geom, &n_blocks)) != H2GCN_OK) return st;
-        if (n_blocks == 0) return H2GCN_OK;
-        for (int s = 0; s < v.n_sel; ++s) {
-            p.a[s] = a[s];
-            p.g[s] = BWD ? g[s] : nullptr;
-            p.out[s] = out[s];
-        }
-        hipLaunchKernelGGL((row_softmax_hops_kernel<BWD>), dim3((unsigned)n_blocks), dim3(kBlock), 0, stream, p);
-        H2GCN_HIP_TRY(hipGetLastError());
-        return H2GCN_OK;
-    } catch (...) {
-        return fail(H2GCN_ERR_INTERNAL, "unexpected exception in row_softmax%s_hops_f32", BWD ? "_backward" : "");
-    }
-}
-
 }  // namespace row_softmax
 }  // namespace h2gcn
 
@@ -393,12 +233,16 @@ extern "C" {
 
 int h2gcn_row_softmax_hops_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* const* scores, float* const* alpha,
                                void* stream) {
-    return h2gcn::row_softmax::launch<false>(plan, hop_mask, scores, "scores", nullptr, "", alpha, "alpha", stream);
+    using namespace h2gcn::row_softmax;
+    return softmax_launch<Params, false, false>(row_softmax_hops_kernel<false>, plan, hop_mask, scores, "scores", nullptr, "", alpha, "alpha", 1,
+                                                stream);
 }
 
 int h2gcn_row_softmax_backward_hops_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* const* alpha,
                                         const float* const* dalpha, float* const* dscores, void* stream) {
-    return h2gcn::row_softmax::launch<true>(plan, hop_mask, alpha, "alpha", dalpha, "dalpha", dscores, "dscores", stream);
+    using namespace h2gcn::row_softmax;
+    return softmax_launch<Params, false, true>(row_softmax_hops_kernel<true>, plan, hop_mask, alpha, "alpha", dalpha, "dalpha", dscores,
+                                               "dscores", 1, stream);
 }
 
 }  // extern "C"

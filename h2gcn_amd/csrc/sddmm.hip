@@ -23,7 +23,7 @@
 //   * segments with >= long_row_threshold nonzeros belong to workgroups of their own: the 4 waves take 64-entry chunks in turn.
 //     Every result belongs to one entry, so nothing is summed across waves.
 //
-// Arithmetic (documented in include/h2gcn_hip.h): one order per element, a function of d alone -- see dot_block / walk_chunk.
+// Arithmetic (documented in include/h2gcn_hip.h): one order per element, a function of d alone -- see batch / walk_chunk.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -31,7 +31,7 @@
 #include <cstring>
 #include <type_traits>
 
-#include "pattern_walk.hip.h"
+#include "segment_ops.hip.h"
 
 namespace h2gcn {
 namespace sddmm {
@@ -55,25 +55,10 @@ struct Params {
     int64_t ldx;
 };
 
-typedef float float4u __attribute__((ext_vector_type(4), aligned(4)));     // 16-byte loads need only dword alignment on gfx950
-typedef uint32_t uint2u __attribute__((ext_vector_type(2), aligned(4)));
+typedef uint32_t uint2u __attribute__((ext_vector_type(2), aligned(4)));   // 8-byte loads need only dword alignment on gfx950
 
-struct Quad {
-    float v[4];
-};
-
-// Columns c0 .. c0+3 of a feature row, widened to fp32; columns >= d read as +0 and are never loaded.
-__device__ __forceinline__ Quad load_quad(const float* row, int c0, int d) {
-    Quad r;
-    if (c0 + 3 < d) {
-        const float4u t = *reinterpret_cast<const float4u*>(row + c0);
-        r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) r.v[k] = c0 + k < d ? row[c0 + k] : 0.f;
-    }
-    return r;
-}
+// Columns c0 .. c0+3 of a feature row, widened to fp32; columns >= d read as +0 and are never loaded.  fp32: segment_ops.hip.h
+using pattern::load_quad;
 // bf16: d is even and every row starts on a dword, so a quad holds 4, 2 or 0 valid columns
 __device__ __forceinline__ Quad load_quad(const bf16* row, int c0, int d) {
     Quad r;
@@ -87,16 +72,6 @@ __device__ __forceinline__ Quad load_quad(const bf16* row, int c0, int d) {
     r.v[0] = __uint_as_float(lo << 16); r.v[1] = __uint_as_float(lo & 0xffff0000u);
     r.v[2] = __uint_as_float(hi << 16); r.v[3] = __uint_as_float(hi & 0xffff0000u);
     return r;
-}
-
-// The total of one 64-column block: the quad's value t = g0*x0, then fma(g1, x1, t), fma(g2, x2, t), fma(g3, x3, t), and the 16
-// quads summed by the xor butterfly over lane distances 1, 2, 4, 8 (afterwards all 16 lanes hold the same bits).
-__device__ __forceinline__ float dot_block(const Quad& g, const Quad& x) {
-    float t = g.v[0] * x.v[0];
-    t = __builtin_fmaf(g.v[1], x.v[1], t);
-    t = __builtin_fmaf(g.v[2], x.v[2], t);
-    t = __builtin_fmaf(g.v[3], x.v[3], t);
-    return bfly16<Add>(t);
 }
 
 // One batch of U rounds of a chunk: group gi serves entry 4r + gi in round r.  FULL: every round of the batch exists.
@@ -120,8 +95,9 @@ __device__ __forceinline__ void batch(const Params& p, const Quad (&g)[NB], int 
         if (FULL || r0 + u < rounds) {
 #pragma unroll
             for (int b = 0; b < NB; ++b) {
-                // (blocks that start at or beyond d hold +0 on both sides: they add +0, as the documented order says)
-                const float t = dot_block(g[b], xv[u][b]);
+                // the total of one 64-column block: the 16 quads' values (dot_quad) summed by the xor butterfly over lane distances
+                // 1, 2, 4, 8 (blocks that start at or beyond d hold +0 on both sides: they add +0, as the documented order says)
+                const float t = bfly16<Add>(dot_quad(g[b], xv[u][b]));
                 if (q == r0 + u) res = res + t;   // block totals in ascending block order, starting from +0
             }
         }

@@ -26,7 +26,7 @@
 
 #include <cstring>
 
-#include "pattern_walk.hip.h"
+#include "segment_ops.hip.h"
 
 namespace h2gcn {
 namespace spmm_values {
@@ -48,36 +48,6 @@ struct Params {
     float* dst;                               // Y [n_rows, n_sel, d] (forward) / dX [n_cols, d] (adjoint)
     int64_t ld_dst, ld_dst_hop;               // (ld_dst_hop: forward only)
 };
-
-typedef float float4u __attribute__((ext_vector_type(4), aligned(4)));   // 16-byte accesses need only dword alignment on gfx950
-
-struct Quad {
-    float v[4];
-};
-
-// Columns c0 .. c0+3 of a feature row; columns >= d read as +0 and are never loaded.
-__device__ __forceinline__ Quad load_quad(const float* row, int c0, int d) {
-    Quad r;
-    if (c0 + 3 < d) {
-        const float4u t = *reinterpret_cast<const float4u*>(row + c0);
-        r.v[0] = t.x; r.v[1] = t.y; r.v[2] = t.z; r.v[3] = t.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) r.v[k] = c0 + k < d ? row[c0 + k] : 0.f;
-    }
-    return r;
-}
-__device__ __forceinline__ void store_quad(float* row, int c0, int d, const Quad& r) {
-    if (c0 + 3 < d) {
-        float4u t;
-        t.x = r.v[0]; t.y = r.v[1]; t.z = r.v[2]; t.w = r.v[3];
-        *reinterpret_cast<float4u*>(row + c0) = t;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-            if (c0 + k < d) row[c0 + k] = r.v[k];
-    }
-}
 
 // sum over the lanes {l, l^16}, then {l, l^32}: (P[gi] + P[gi^1]) + (P[gi^2] + P[gi^3])
 __device__ __forceinline__ float fold_groups(float v) {

@@ -478,6 +478,13 @@ class HopPlan:
         _capi.check(st)
         return out
 
+    @staticmethod
+    def _head_width(d: int, n_heads: int) -> None:
+        """``K`` heads share ``d`` columns evenly, and a lane's four columns lie in one head."""
+        _require(d % n_heads == 0, f"the width d = {d} is not a multiple of the number of heads K = {n_heads}")
+        _require(n_heads == 1 or (d // n_heads) % 4 == 0,
+                 f"with K = {n_heads} > 1 heads the head width d / K = {d // n_heads} must be a multiple of 4")
+
     def _launch_values(self, values, sel, d: int):
         """The ``values`` of :meth:`spmm_values` / :meth:`spmm_values_t`, checked -> ``(tensors, K, pointer table, ldv_entry,
         ldv_head)``.  Strides pass through as they are: nothing is made contiguous."""
@@ -496,9 +503,7 @@ class HopPlan:
             heads = 1 if t.dim() == 1 else int(t.shape[1])
             _require(n_heads in (None, heads), f"values[{s}] has {heads} heads, values[0] has {n_heads}: every hop needs the same K")
             n_heads = heads
-        _require(d % n_heads == 0, f"the width d = {d} is not a multiple of the number of heads K = {n_heads}")
-        _require(n_heads == 1 or (d // n_heads) % 4 == 0,
-                 f"with K = {n_heads} > 1 heads the head width d / K = {d // n_heads} must be a multiple of 4")
+        self._head_width(d, n_heads)
         ptrs = (C.c_void_p * len(sel))(*[t.data_ptr() if t.numel() else None for t in values])
         ldv_entry = (C.c_int64 * len(sel))(*[t.stride(0) if t.shape[0] > 1 else 1 for t in values])
         ldv_head = (C.c_int64 * len(sel))(*[t.stride(1) if t.dim() == 2 and t.shape[1] > 1 else 0 for t in values])
@@ -520,6 +525,23 @@ class HopPlan:
         (a0, a1), (b0, b1) = extent(a), extent(b)
         return a0 < b1 and b0 < a1
 
+    def _dense_inputs(self, x, what: str) -> int:
+        """The gathered operand ``x`` of :meth:`spmm_values` / :meth:`attention_heads`, checked -> its width ``d``."""
+        _require(isinstance(x, torch.Tensor) and x.dim() == 2, f"inputs must be [n_cols, d], got shape {tuple(getattr(x, 'shape', ()))}")
+        _require(x.dtype == torch.float32, f"inputs must be float32 (the {what} is fp32 only), got {x.dtype}")
+        _require(x.device == self.device, f"inputs on {x.device}, plan on {self.device}")
+        _require(x.shape[0] == self.n_cols, f"inputs have {x.shape[0]} rows, hop matrices have {self.n_cols} columns")
+        _require(x.shape[1] >= 1, "inputs need at least one column")
+        return int(x.shape[1])
+
+    def _dense_output(self, out, h_sel: int, d: int) -> None:
+        """The caller's ``out`` of the same two calls: float32 ``[n_rows, h_sel, d]`` whose rows and hop slots do not overlap."""
+        _require(isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.device == self.device,
+                 "out must be float32 on the plan's device")
+        _require(tuple(out.shape) == (self.n_rows, h_sel, d), f"out has shape {tuple(out.shape)}, expected {(self.n_rows, h_sel, d)}")
+        _require(d == 1 or out.stride(2) == 1, "out's last dimension must be contiguous")
+        _require((self.n_rows <= 1 or out.stride(0) >= d) and (h_sel == 1 or out.stride(1) >= d), "out's rows / hop slots overlap")
+
     def spmm_values(self, x: torch.Tensor, values: Sequence[torch.Tensor], hops=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The hop SpMM on values that are an argument of the launch: ``out[i, s, c] = sum_e values[s][e, h(c)] * x[j_e, c]`` over
         the stored entries ``e = (i, j_e)`` of selected hop ``s``, ``h(c) = c // (d // K)`` -> ``[n_rows, H_sel, d]``
@@ -532,12 +554,7 @@ class HopPlan:
         copied).  ``K > 1`` needs ``d % K == 0`` and ``(d // K) % 4 == 0``.  ``x``: float32 ``[n_cols, d]`` (a row stride passes
         through); ``out``: float32 ``[n_rows, H_sel, d]`` with a contiguous last dimension (a view into a wider buffer is
         fine) that does not overlap ``x``.  fp32 only; no transposed operand is needed."""
-        _require(isinstance(x, torch.Tensor) and x.dim() == 2, f"inputs must be [n_cols, d], got shape {tuple(getattr(x, 'shape', ()))}")
-        _require(x.dtype == torch.float32, f"inputs must be float32 (the launch on per-launch values is fp32 only), got {x.dtype}")
-        _require(x.device == self.device, f"inputs on {x.device}, plan on {self.device}")
-        _require(x.shape[0] == self.n_cols, f"inputs have {x.shape[0]} rows, hop matrices have {self.n_cols} columns")
-        d = int(x.shape[1])
-        _require(d >= 1, "inputs need at least one column")
+        d = self._dense_inputs(x, "launch on per-launch values")
         mask, sel = self._mask(hops), self._selected(hops)
         h_sel = len(sel)
         values, n_heads, ptrs, ldv_entry, ldv_head = self._launch_values(values, sel, d)
@@ -546,11 +563,7 @@ class HopPlan:
         if out is None:
             out = torch.empty((self.n_rows, h_sel, d), dtype=torch.float32, device=self.device)
         else:
-            _require(isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.device == self.device,
-                     "out must be float32 on the plan's device")
-            _require(tuple(out.shape) == (self.n_rows, h_sel, d), f"out has shape {tuple(out.shape)}, expected {(self.n_rows, h_sel, d)}")
-            _require(d == 1 or out.stride(2) == 1, "out's last dimension must be contiguous")
-            _require((self.n_rows <= 1 or out.stride(0) >= d) and (h_sel == 1 or out.stride(1) >= d), "out's rows / hop slots overlap")
+            self._dense_output(out, h_sel, d)
             _require(not self._overlap(out, x), "out overlaps the inputs: the launch gathers rows of x while it stores rows of out")
         self._values_symbols()
         if self.n_rows == 0:
@@ -605,8 +618,9 @@ class HopPlan:
         _capi.check(st)
         return out
 
-    def _segment_tensors(self, op: str, name: str, tensors, sel) -> list:
-        """``tensors`` as a list of one contiguous float32 ``[nnz_k]`` tensor per selected hop; ``op`` names the operation."""
+    def _segment_tensors(self, op: str, name: str, tensors, sel, heads: Optional[int] = None) -> tuple:
+        """``tensors`` as a list of one contiguous float32 tensor per selected hop -> ``(list, K)``; ``op`` names the operation.
+        ``heads`` None: ``[nnz_k]`` tensors; 0: entry-major ``[nnz_k, K]`` tensors, one ``K`` for all; ``K > 0``: that ``K``."""
         _require(not isinstance(tensors, torch.Tensor) and tensors is not None, f"{name} must be a sequence of {len(sel)} tensors (one per selected hop)")
         tensors = list(tensors)
         _require(len(tensors) == len(sel), f"{name} must list {len(sel)} tensors (one per selected hop), got {len(tensors)}")
@@ -615,15 +629,24 @@ class HopPlan:
             _require(isinstance(t, torch.Tensor), f"{name}[{s}] must be a tensor, got {type(t).__name__}")
             _require(t.dtype == torch.float32, f"{name}[{s}] must be float32 (the {op} is fp32 only), got {t.dtype}")
             _require(t.device == self.device, f"{name}[{s}] on {t.device}, plan on {self.device}")
-            _require(tuple(t.shape) == (nnz,), f"{name}[{s}] must have shape [{nnz}] (one value per stored entry of hop {k}), got {tuple(t.shape)}")
-            _require(t.is_contiguous(), f"{name}[{s}] must be contiguous")
-        return tensors
+            if heads is None:
+                _require(tuple(t.shape) == (nnz,), f"{name}[{s}] must have shape [{nnz}] (one value per stored entry of hop {k}), got {tuple(t.shape)}")
+                _require(t.is_contiguous(), f"{name}[{s}] must be contiguous")
+                continue
+            _require(t.dim() == 2 and t.shape[0] == nnz and t.shape[1] >= 1,
+                     f"{name}[{s}] must have shape [{nnz}, K] (one value per stored entry of hop {k} and head), got {tuple(t.shape)}")
+            _require(heads in (0, int(t.shape[1])),
+                     f"{name}[{s}] has {int(t.shape[1])} heads where {heads} are expected: every per-entry array needs the same K")
+            heads = int(t.shape[1])
+            _require(t.is_contiguous(), f"{name}[{s}] must be contiguous (entry-major: element (e, h) at e * K + h)")
+        return tensors, heads
 
-    def _segment_outputs(self, op: str, out, sel) -> list:
-        """The caller's ``out`` list, checked, or new tensors."""
+    def _segment_outputs(self, op: str, out, sel, heads: Optional[int] = None) -> list:
+        """The caller's ``out`` list, checked, or new tensors (``heads`` as in :meth:`_segment_tensors`, but not 0)."""
         if out is not None:
-            return self._segment_tensors(op, "out", out, sel)
-        return [torch.empty(self.colidx[k].numel(), dtype=torch.float32, device=self.device) for k in sel]
+            return self._segment_tensors(op, "out", out, sel, heads)[0]
+        return [torch.empty((self.colidx[k].numel(),) + (() if heads is None else (heads,)), dtype=torch.float32, device=self.device)
+                for k in sel]
 
     @staticmethod
     def _segment_ptrs(*tables) -> list:
@@ -631,16 +654,22 @@ class HopPlan:
         arr_t = C.c_void_p * len(tables[0])
         return [arr_t(*[t.data_ptr() if t.numel() else None for t in ts]) for ts in tables]
 
-    def _row_softmax_launch(self, symbol: str, hops, inputs: dict, out) -> list:
+    def _row_softmax_launch(self, symbol: str, hops, inputs: dict, out, heads: Optional[int] = None) -> list:
+        """The four row-softmax calls; ``heads`` as in :meth:`_segment_tensors` (0: the head-batched symbols, which take ``K``)."""
         mask, sel = self._mask(hops), self._selected(hops)
-        tables = [self._segment_tensors("row softmax", name, ts, sel) for name, ts in inputs.items()]
-        out = self._segment_outputs("row softmax", out, sel)
-        if not _capi.has(symbol):
+        tables = []
+        for name, ts in inputs.items():
+            ts, heads = self._segment_tensors("row softmax", name, ts, sel, heads)
+            tables.append(ts)
+        out = self._segment_outputs("row softmax", out, sel, heads)
+        if heads is not None:
+            self._heads_symbols()
+        elif not _capi.has(symbol):
             raise RuntimeError(f"{_capi.library_path()} predates the row softmax (h2gcn_row_softmax_hops_f32 / _backward_hops_f32): rebuild it")
         ptrs = self._segment_ptrs(*tables, out)
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            st = getattr(_capi.lib(), symbol)(self._handle, mask, *ptrs, C.c_void_p(stream))
+            st = getattr(_capi.lib(), symbol)(self._handle, mask, *ptrs, *(() if heads is None else (heads,)), C.c_void_p(stream))
         _capi.check(st)
         return out
 
@@ -675,6 +704,13 @@ class HopPlan:
         if (h_sel > 1 and t.stride(1) != 1) or (n > 1 and t.stride(0) < h_sel):
             t = t.contiguous()
         return t, (t.stride(0) if n > 1 else h_sel)
+
+    def _column_side(self, need_dr: bool) -> None:
+        """What ``dr`` of the edge-score backwards needs of the plan."""
+        _require(not need_dr or (self.has_transpose and self.keep_permutation),
+                 "the gradient wrt r sums over the COLUMNS of the hop matrices: it walks the plan's transposed operands through their "
+                 "permutation.  Build the plan with HopPlan(..., build_transpose=True, keep_permutation=True)"
+                 + ("" if self.has_transpose else " (this plan has no transposed operands)"))
 
     @staticmethod
     def _edge_scores_symbols() -> None:
@@ -722,11 +758,8 @@ class HopPlan:
         shapes = (l.shape if isinstance(l, torch.Tensor) else None, r.shape if isinstance(r, torch.Tensor) else None)
         l, ldl = self._node_operand("l", l, self.n_rows, h_sel)
         r, ldr = self._node_operand("r", r, self.n_cols, h_sel)
-        grad = self._segment_tensors("edge scores", "grad", grad, sel)
-        _require(not need_dr or (self.has_transpose and self.keep_permutation),
-                 "the gradient wrt r sums over the COLUMNS of the hop matrices: it walks the plan's transposed operands through their "
-                 "permutation.  Build the plan with HopPlan(..., build_transpose=True, keep_permutation=True)"
-                 + ("" if self.has_transpose else " (this plan has no transposed operands)"))
+        grad, _ = self._segment_tensors("edge scores", "grad", grad, sel)
+        self._column_side(need_dr)
         self._edge_scores_symbols()
         dl = torch.empty((self.n_rows, h_sel), dtype=torch.float32, device=self.device) if need_dl else None
         dr = torch.empty((self.n_cols, h_sel), dtype=torch.float32, device=self.device) if need_dr else None
@@ -747,29 +780,6 @@ class HopPlan:
     def _heads_symbols(cls) -> None:
         if not all(_capi.has(s) for s in cls._HEADS_SYMBOLS):
             raise RuntimeError(f"{_capi.library_path()} predates the head-batched attention calls ({', '.join(cls._HEADS_SYMBOLS)}): rebuild it")
-
-    def _head_tensors(self, op: str, name: str, tensors, sel, n_heads: Optional[int] = None) -> tuple:
-        """``tensors`` as a list of one contiguous float32 ``[nnz_k, K]`` tensor per selected hop, one ``K`` for all -> ``(list, K)``."""
-        _require(not isinstance(tensors, torch.Tensor) and tensors is not None, f"{name} must be a sequence of {len(sel)} tensors (one per selected hop)")
-        tensors = list(tensors)
-        _require(len(tensors) == len(sel), f"{name} must list {len(sel)} tensors (one per selected hop), got {len(tensors)}")
-        for s, k in enumerate(sel):
-            t, nnz = tensors[s], self.colidx[k].numel()
-            _require(isinstance(t, torch.Tensor), f"{name}[{s}] must be a tensor, got {type(t).__name__}")
-            _require(t.dtype == torch.float32, f"{name}[{s}] must be float32 (the {op} is fp32 only), got {t.dtype}")
-            _require(t.device == self.device, f"{name}[{s}] on {t.device}, plan on {self.device}")
-            _require(t.dim() == 2 and t.shape[0] == nnz and t.shape[1] >= 1,
-                     f"{name}[{s}] must have shape [{nnz}, K] (one value per stored entry of hop {k} and head), got {tuple(t.shape)}")
-            _require(n_heads in (None, int(t.shape[1])),
-                     f"{name}[{s}] has {int(t.shape[1])} heads where {n_heads} are expected: every per-entry array needs the same K")
-            n_heads = int(t.shape[1])
-            _require(t.is_contiguous(), f"{name}[{s}] must be contiguous (entry-major: element (e, h) at e * K + h)")
-        return tensors, n_heads
-
-    def _head_outputs(self, op: str, out, sel, n_heads: int) -> list:
-        if out is not None:
-            return self._head_tensors(op, "out", out, sel, n_heads)[0]
-        return [torch.empty((self.colidx[k].numel(), n_heads), dtype=torch.float32, device=self.device) for k in sel]
 
     def sddmm_heads(self, grad: torch.Tensor, x: torch.Tensor, heads: int, hops=None,
                     out: Optional[Sequence[torch.Tensor]] = None) -> list:
@@ -792,15 +802,13 @@ class HopPlan:
         _require(grad.device == self.device and x.device == self.device, f"grad on {grad.device}, x on {x.device}, plan on {self.device}")
         n_heads = int(heads)
         _require(n_heads >= 1, f"heads = {heads} < 1")
-        _require(d % n_heads == 0, f"the width d = {d} is not a multiple of the number of heads K = {n_heads}")
-        _require(n_heads == 1 or (d // n_heads) % 4 == 0,
-                 f"with K = {n_heads} > 1 heads the head width d / K = {d // n_heads} must be a multiple of 4")
+        self._head_width(d, n_heads)
         if grad.stride(2) != 1 or grad.stride(0) < d or (h_sel > 1 and grad.stride(1) < d):
             grad = grad.contiguous()
         if x.stride(1) != 1 or x.stride(0) < d:
             x = x.contiguous()
         mask, sel = self._mask(hops), self._selected(hops)
-        out = self._head_outputs("values gradient", out, sel, n_heads)
+        out = self._segment_outputs("values gradient", out, sel, n_heads)
         ld_row, ld_hop = (grad.stride(0) if self.n_rows > 1 else h_sel * d), (grad.stride(1) if h_sel > 1 else d)
         ldx = x.stride(0) if self.n_cols > 1 else d
         self._heads_symbols()
@@ -812,33 +820,18 @@ class HopPlan:
         _capi.check(st)
         return out
 
-    def _row_softmax_heads_launch(self, symbol: str, hops, inputs: dict, out) -> list:
-        mask, sel = self._mask(hops), self._selected(hops)
-        tables, n_heads = [], None
-        for name, ts in inputs.items():
-            ts, n_heads = self._head_tensors("row softmax", name, ts, sel, n_heads)
-            tables.append(ts)
-        out = self._head_outputs("row softmax", out, sel, n_heads)
-        self._heads_symbols()
-        ptrs = self._segment_ptrs(*tables, out)
-        with torch.cuda.device(self.device):
-            stream = torch.cuda.current_stream(self.device).cuda_stream
-            st = getattr(_capi.lib(), symbol)(self._handle, mask, *ptrs, n_heads, C.c_void_p(stream))
-        _capi.check(st)
-        return out
-
     def row_softmax_heads(self, scores: Sequence[torch.Tensor], hops=None, out: Optional[Sequence[torch.Tensor]] = None) -> list:
         """:meth:`row_softmax` for ``K`` heads in one launch: one softmax per (row, hop, head) over contiguous float32
         ``[nnz_k, K]`` scores -> ``[nnz_k, K]`` coefficients per selected hop (``h2gcn_row_softmax_hops_heads_f32``) -- the layout
         :meth:`spmm_values` reads fastest.  Per head the bits are those of :meth:`row_softmax` on a contiguous copy of that
         column.  ``out`` may be the ``scores`` tensors themselves."""
-        return self._row_softmax_heads_launch("h2gcn_row_softmax_hops_heads_f32", hops, {"scores": scores}, out)
+        return self._row_softmax_launch("h2gcn_row_softmax_hops_heads_f32", hops, {"scores": scores}, out, heads=0)
 
     def row_softmax_heads_backward(self, alpha: Sequence[torch.Tensor], grad: Sequence[torch.Tensor], hops=None,
                                    out: Optional[Sequence[torch.Tensor]] = None) -> list:
         """The backward of :meth:`row_softmax_heads` (``h2gcn_row_softmax_backward_hops_heads_f32``, one launch): ``alpha`` and
         ``grad`` contiguous float32 ``[nnz_k, K]``; ``out`` may be the ``grad`` tensors themselves."""
-        return self._row_softmax_heads_launch("h2gcn_row_softmax_backward_hops_heads_f32", hops, {"alpha": alpha, "grad": grad}, out)
+        return self._row_softmax_launch("h2gcn_row_softmax_backward_hops_heads_f32", hops, {"alpha": alpha, "grad": grad}, out, heads=0)
 
     def _node_heads_operand(self, name: str, t, n: int, h_sel: int, n_heads: Optional[int] = None):
         """A per-node operand of the edge scores with heads: float32 ``[n, h_sel, K]`` whose last two dimensions are contiguous (a
@@ -862,7 +855,7 @@ class HopPlan:
         mask, sel = self._mask(hops), self._selected(hops)
         l, ldl, n_heads = self._node_heads_operand("l", l, self.n_rows, len(sel))
         r, ldr, _ = self._node_heads_operand("r", r, self.n_cols, len(sel), n_heads)
-        out = self._head_outputs("edge scores", out, sel, n_heads)
+        out = self._segment_outputs("edge scores", out, sel, n_heads)
         self._heads_symbols()
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
@@ -883,11 +876,8 @@ class HopPlan:
         _require(need_dl or need_dr, "need_dl and need_dr are both False: nothing to compute")
         l, ldl, n_heads = self._node_heads_operand("l", l, self.n_rows, h_sel)
         r, ldr, _ = self._node_heads_operand("r", r, self.n_cols, h_sel, n_heads)
-        grad, _ = self._head_tensors("edge scores", "grad", grad, sel, n_heads)
-        _require(not need_dr or (self.has_transpose and self.keep_permutation),
-                 "the gradient wrt r sums over the COLUMNS of the hop matrices: it walks the plan's transposed operands through their "
-                 "permutation.  Build the plan with HopPlan(..., build_transpose=True, keep_permutation=True)"
-                 + ("" if self.has_transpose else " (this plan has no transposed operands)"))
+        grad, _ = self._segment_tensors("edge scores", "grad", grad, sel, n_heads)
+        self._column_side(need_dr)
         self._heads_symbols()
         dl = torch.empty((self.n_rows, h_sel, n_heads), dtype=torch.float32, device=self.device) if need_dl else None
         dr = torch.empty((self.n_cols, h_sel, n_heads), dtype=torch.float32, device=self.device) if need_dr else None
@@ -917,12 +907,7 @@ class HopPlan:
         pass through.  ``1 <= K <= 16``; ``K > 1`` needs ``d % K == 0`` and ``(d // K) % 4 == 0``.  ``out``: float32 ``[n_rows,
         H_sel, d]`` with a contiguous last dimension (a view into a wider buffer is fine: its strides pass through) that overlaps
         none of the inputs."""
-        _require(isinstance(x, torch.Tensor) and x.dim() == 2, f"inputs must be [n_cols, d], got shape {tuple(getattr(x, 'shape', ()))}")
-        _require(x.dtype == torch.float32, f"inputs must be float32 (the fused attention forward is fp32 only), got {x.dtype}")
-        _require(x.device == self.device, f"inputs on {x.device}, plan on {self.device}")
-        _require(x.shape[0] == self.n_cols, f"inputs have {x.shape[0]} rows, hop matrices have {self.n_cols} columns")
-        d = int(x.shape[1])
-        _require(d >= 1, "inputs need at least one column")
+        d = self._dense_inputs(x, "fused attention forward")
         mask, sel = self._mask(hops), self._selected(hops)
         h_sel = len(sel)
         l, ldl, n_heads = self._node_heads_operand("l", l, self.n_rows, h_sel)
@@ -930,17 +915,11 @@ class HopPlan:
         _require(n_heads <= self.ATTENTION_FUSED_MAX_HEADS,
                  f"the fused attention forward serves at most K = {self.ATTENTION_FUSED_MAX_HEADS} heads, got K = {n_heads}: run the chain "
                  "(edge_scores_heads, row_softmax_heads, spmm_values)")
-        _require(d % n_heads == 0, f"the width d = {d} is not a multiple of the number of heads K = {n_heads}")
-        _require(n_heads == 1 or (d // n_heads) % 4 == 0,
-                 f"with K = {n_heads} > 1 heads the head width d / K = {d // n_heads} must be a multiple of 4")
+        self._head_width(d, n_heads)
         if (d > 1 and x.stride(1) != 1) or (self.n_cols > 1 and x.stride(0) < d):
             x = x.contiguous()
         if out is not None:
-            _require(isinstance(out, torch.Tensor) and out.dtype == torch.float32 and out.device == self.device,
-                     "out must be float32 on the plan's device")
-            _require(tuple(out.shape) == (self.n_rows, h_sel, d), f"out has shape {tuple(out.shape)}, expected {(self.n_rows, h_sel, d)}")
-            _require(d == 1 or out.stride(2) == 1, "out's last dimension must be contiguous")
-            _require((self.n_rows <= 1 or out.stride(0) >= d) and (h_sel == 1 or out.stride(1) >= d), "out's rows / hop slots overlap")
+            self._dense_output(out, h_sel, d)
             for name, t in (("the inputs", x), ("l", l), ("r", r)):
                 _require(not self._overlap(out, t), f"out overlaps {name}: the launch gathers rows of x and r while it stores rows of out")
         if not _capi.has("h2gcn_attention_hops_heads_f32"):
