@@ -72,6 +72,8 @@ EXPORTED_SYMBOLS = (
     "h2gcn_spmm_hops_values_f32",
     "h2gcn_spmm_hops_T_values_f32",
     "h2gcn_attention_hops_heads_f32",
+    "h2gcn_attention_hops_heads_stats_f32",
+    "h2gcn_attention_hops_heads_backward_f32",
     "h2gcn_ring_scratch_bytes",
     "h2gcn_ring_count",
     "h2gcn_ring_fill",
@@ -277,6 +279,15 @@ def lib() -> C.CDLL:
         L.h2gcn_attention_hops_heads_f32.argtypes = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32,
                                                      C.c_float, C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_int64, C.c_int64,
                                                      C.c_void_p]
+    if hasattr(L, "h2gcn_attention_hops_heads_stats_f32"):   # (the forward that stores the softmax statistics, and the recomputing
+        node_args = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_float,   # backward: added within ABI 5)
+                     C.c_void_p, C.c_int64, C.c_int32]
+        L.h2gcn_attention_hops_heads_stats_f32.restype = C.c_int
+        L.h2gcn_attention_hops_heads_stats_f32.argtypes = node_args + [C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+        L.h2gcn_attention_hops_heads_backward_f32.restype = C.c_int
+        L.h2gcn_attention_hops_heads_backward_f32.argtypes = node_args + [
+            C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+            C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
     L.h2gcn_ring_scratch_bytes.restype = C.c_size_t
     L.h2gcn_ring_scratch_bytes.argtypes = [C.c_int64]
     ring_common = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -51,6 +51,10 @@ int pattern_long_list(const h2gcn_plan* plan, uint32_t mask, hipStream_t stream,
 // adjoint launch of the selection uses.
 int adjoint_view(const h2gcn_plan* plan, uint32_t hop_mask, PatternView* out, const uint32_t** perm);
 
+// adjoint_view for a kernel that walks A_k^T but indexes no per-entry array (attention_backward.hip): the same PatternView, no
+// permutation asked for -- a plan created without H2GCN_PLAN_KEEP_PERMUTATION is served.  H2GCN_ERR_NO_TRANSPOSE as above.
+int adjoint_pattern_view(const h2gcn_plan* plan, uint32_t hop_mask, PatternView* out);
+
 }  // namespace h2gcn
 
 #define H2GCN_HIP_TRY(expr)                                                                          \

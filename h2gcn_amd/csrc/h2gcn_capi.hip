@@ -1351,6 +1351,24 @@ int adjoint_view(const h2gcn_plan* plan, uint32_t hop_mask, PatternView* out, co
     }
     return H2GCN_OK;
 }
+
+int adjoint_pattern_view(const h2gcn_plan* plan, uint32_t hop_mask, PatternView* out) {
+    int st = pattern_view(plan, hop_mask, out);
+    if (st != H2GCN_OK) return st;
+    if (!plan->has_transpose) return fail(H2GCN_ERR_NO_TRANSPOSE, "plan was created without H2GCN_PLAN_BUILD_TRANSPOSE");
+    out->n_rows = plan->n_cols;
+    out->n_cols = plan->n_rows;
+    int s = 0;
+    for (int k = 0; k < plan->n_hops; ++k) {
+        if (!(out->mask & (1u << k))) continue;
+        const HopOperand& op = plan->adj[k];
+        out->rowptr[s] = op.rowptr;
+        out->colidx[s] = op.colidx;
+        out->nnz[s] = op.nnz;
+        ++s;
+    }
+    return H2GCN_OK;
+}
 }  // namespace h2gcn
 }  // extern "C++"
 

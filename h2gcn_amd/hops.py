@@ -937,6 +937,105 @@ class HopPlan:
         _capi.check(st)
         return out
 
+    #: the widest ``d`` the recomputing attention backward serves (``h2gcn_attention_hops_heads_backward_f32``)
+    ATTENTION_RECOMPUTE_MAX_WIDTH = 256
+    _RECOMPUTE_SYMBOLS = ("h2gcn_attention_hops_heads_stats_f32", "h2gcn_attention_hops_heads_backward_f32")
+
+    def _attention_operands(self, what: str, x, l, r, hops):
+        """``x``, ``l``, ``r`` of the attention launches, checked as :meth:`attention_heads` checks them -> ``(x, l, ldl, r, ldr, K, d,
+        mask, H_sel)``."""
+        d = self._dense_inputs(x, what)
+        mask, h_sel = self._mask(hops), len(self._selected(hops))
+        l, ldl, n_heads = self._node_heads_operand("l", l, self.n_rows, h_sel)
+        r, ldr, _ = self._node_heads_operand("r", r, self.n_cols, h_sel, n_heads)
+        _require(n_heads <= self.ATTENTION_FUSED_MAX_HEADS,
+                 f"the {what} serves at most K = {self.ATTENTION_FUSED_MAX_HEADS} heads, got K = {n_heads}: run the chain "
+                 "(edge_scores_heads, row_softmax_heads, spmm_values)")
+        self._head_width(d, n_heads)
+        if (d > 1 and x.stride(1) != 1) or (self.n_cols > 1 and x.stride(0) < d):
+            x = x.contiguous()
+        return x, l, ldl, r, ldr, n_heads, d, mask, h_sel
+
+    @classmethod
+    def _recompute_symbol(cls, name: str) -> None:
+        if not _capi.has(name):
+            raise RuntimeError(f"{_capi.library_path()} predates the recomputing attention backward ({name}): rebuild it")
+
+    def attention_heads_stats(self, x: torch.Tensor, l: torch.Tensor, r: torch.Tensor, negative_slope: float = 0.2, hops=None,
+                              out: Optional[torch.Tensor] = None) -> tuple:
+        """:meth:`attention_heads` that also returns the softmax statistics -> ``(y, stats)``
+        (``h2gcn_attention_hops_heads_stats_f32``, one launch).  ``y`` has the bits of :meth:`attention_heads`; ``stats`` is float32
+        ``[n_rows, H_sel, 2, K]``: ``stats[i, s, 0, h]`` the maximum score of the segment, ``stats[i, s, 1, h]`` the reciprocal of
+        its sum of exponentials -- ``(+0, +0)`` for an empty segment.  With ``x, l, r, stats, y`` :meth:`attention_heads_backward`
+        computes the gradients without any ``[nnz_k, K]`` array.  Operands and ``out`` as in :meth:`attention_heads`."""
+        x, l, ldl, r, ldr, n_heads, d, mask, h_sel = self._attention_operands("fused attention forward", x, l, r, hops)
+        if out is not None:
+            self._dense_output(out, h_sel, d)
+            for name, t in (("the inputs", x), ("l", l), ("r", r)):
+                _require(not self._overlap(out, t), f"out overlaps {name}: the launch gathers rows of x and r while it stores rows of out")
+        self._recompute_symbol(self._RECOMPUTE_SYMBOLS[0])
+        if out is None:
+            out = torch.empty((self.n_rows, h_sel, d), dtype=torch.float32, device=self.device)
+        stats = torch.empty((self.n_rows, h_sel, 2, n_heads), dtype=torch.float32, device=self.device)
+        if self.n_rows == 0:
+            return out, stats
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            st = _capi.lib().h2gcn_attention_hops_heads_stats_f32(
+                self._handle, mask, C.c_void_p(l.data_ptr()), ldl, C.c_void_p(r.data_ptr()), ldr, n_heads, float(negative_slope),
+                C.c_void_p(x.data_ptr()), x.stride(0) if self.n_cols > 1 else d, d, C.c_void_p(out.data_ptr()),
+                out.stride(0) if self.n_rows > 1 else h_sel * d, out.stride(1) if h_sel > 1 else d, C.c_void_p(stats.data_ptr()),
+                h_sel * 2 * n_heads, C.c_void_p(stream))
+        _capi.check(st)
+        return out, stats
+
+    def attention_heads_backward(self, x: torch.Tensor, l: torch.Tensor, r: torch.Tensor, stats: torch.Tensor, y: torch.Tensor,
+                                 grad: torch.Tensor, negative_slope: float = 0.2, hops=None, need_dl: bool = True, need_dr: bool = True,
+                                 need_dx: bool = True) -> tuple:
+        """The backward of :meth:`attention_heads_stats` -> ``(dl, dr, dx)``, ``[n_rows, H_sel, K]``, ``[n_cols, H_sel, K]`` and
+        ``[n_cols, d]`` (``h2gcn_attention_hops_heads_backward_f32``): every per-entry quantity is computed again from the node
+        operands and ``stats``, so nothing of size ``nnz`` is read, written or allocated -- the launch allocates its results and one
+        ``[n_rows, H_sel, K]`` buffer.  ``x``, ``l``, ``r``, ``stats``, ``y`` are the forward's operands and results, ``grad`` the
+        gradient of ``y`` (float32 ``[n_rows, H_sel, d]``; row and hop strides pass through).  An unwanted side is ``None``.
+
+        The gradients are deterministic; they are NOT the chain's bits (include/h2gcn_hip.h has the orders).  ``dr`` and ``dx`` walk
+        the plan's transposed operands WITHOUT their permutation: ``build_transpose=True`` (or ``symmetric_pattern=True``) is
+        enough.  ``d <= 256``."""
+        x, l, ldl, r, ldr, n_heads, d, mask, h_sel = self._attention_operands("recomputing attention backward", x, l, r, hops)
+        _require(need_dl or need_dr or need_dx, "need_dl, need_dr and need_dx are all False: nothing to compute")
+        _require(d <= self.ATTENTION_RECOMPUTE_MAX_WIDTH,
+                 f"the recomputing attention backward serves at most d = {self.ATTENTION_RECOMPUTE_MAX_WIDTH} columns, got d = {d}: run the chain")
+        for name, t, shape in (("stats", stats, (self.n_rows, h_sel, 2, n_heads)), ("y", y, (self.n_rows, h_sel, d)),
+                               ("grad", grad, (self.n_rows, h_sel, d))):
+            _require(isinstance(t, torch.Tensor) and tuple(t.shape) == shape, f"{name} must be {list(shape)}, got {tuple(getattr(t, 'shape', ()))}")
+            _require(t.dtype == torch.float32, f"{name} must be float32 (the recomputing attention backward is fp32 only), got {t.dtype}")
+            _require(t.device == self.device, f"{name} on {t.device}, plan on {self.device}")
+        stats = stats.contiguous()
+        if (d > 1 and y.stride(2) != 1) or (self.n_rows > 1 and y.stride(0) < d) or (h_sel > 1 and y.stride(1) < d):
+            y = y.contiguous()
+        if (d > 1 and grad.stride(2) != 1) or (self.n_rows > 1 and grad.stride(0) < d) or (h_sel > 1 and grad.stride(1) < d):
+            grad = grad.contiguous()
+        _require(not (need_dr or need_dx) or self.has_transpose,
+                 "the gradients wrt r and the inputs sum over the COLUMNS of the hop matrices: they walk the plan's transposed operands "
+                 "(no permutation is needed).  Build the plan with HopPlan(..., build_transpose=True)")
+        self._recompute_symbol(self._RECOMPUTE_SYMBOLS[1])
+        dl = torch.empty((self.n_rows, h_sel, n_heads), dtype=torch.float32, device=self.device) if need_dl else None
+        dr = torch.empty((self.n_cols, h_sel, n_heads), dtype=torch.float32, device=self.device) if need_dr else None
+        dx = torch.empty((self.n_cols, d), dtype=torch.float32, device=self.device) if need_dx else None
+        if all(t is None or t.numel() == 0 for t in (dl, dr, dx)):   # (no node on the requested sides: nothing to write)
+            return dl, dr, dx
+        delta = torch.empty((self.n_rows, h_sel, n_heads), dtype=torch.float32, device=self.device) if need_dr or need_dx else None
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # noqa: E731
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            st = _capi.lib().h2gcn_attention_hops_heads_backward_f32(
+                self._handle, mask, ptr(l), ldl, ptr(r), ldr, n_heads, float(negative_slope), ptr(x), x.stride(0) if self.n_cols > 1 else d, d,
+                ptr(stats), h_sel * 2 * n_heads, ptr(y), y.stride(0) if self.n_rows > 1 else h_sel * d, y.stride(1) if h_sel > 1 else d,
+                ptr(grad), grad.stride(0) if self.n_rows > 1 else h_sel * d, grad.stride(1) if h_sel > 1 else d,
+                ptr(delta), h_sel * n_heads, ptr(dl), h_sel * n_heads, ptr(dr), h_sel * n_heads, ptr(dx), d, C.c_void_p(stream))
+        _capi.check(st)
+        return dl, dr, dx
+
     def __del__(self):
         h = getattr(self, "_handle", None)
         if h is not None and h.value:

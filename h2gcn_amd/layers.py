@@ -411,6 +411,65 @@ def hop_attention_heads(adjhops: HopPlan, inputs: torch.Tensor, l: torch.Tensor,
     return adjhops.attention_heads(inputs, l, r, negative_slope, hops=sel)
 
 
+class _HopAttentionRecompute(torch.autograd.Function):
+    """The attention over the hop pattern as TWO launches that keep no per-entry array: the forward stores ``y`` and the softmax
+    statistics (``HopPlan.attention_heads_stats``), the backward computes every per-entry quantity again from ``x, l, r, stats, y``
+    (``HopPlan.attention_heads_backward``)."""
+
+    @staticmethod
+    def forward(ctx, plan: HopPlan, hops, negative_slope: float, inputs: torch.Tensor, l: torch.Tensor, r: torch.Tensor):
+        y, stats = plan.attention_heads_stats(inputs, l, r, negative_slope, hops=hops)
+        ctx.plan, ctx.hops, ctx.negative_slope = plan, hops, negative_slope
+        ctx.save_for_backward(inputs, l, r, stats, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad):
+        need_dx, need_dl, need_dr = ctx.needs_input_grad[3:6]
+        if not (need_dx or need_dl or need_dr):
+            return None, None, None, None, None, None
+        inputs, l, r, stats, y = ctx.saved_tensors
+        dl, dr, dx = ctx.plan.attention_heads_backward(inputs, l, r, stats, y, grad, ctx.negative_slope, hops=ctx.hops, need_dl=need_dl,
+                                                       need_dr=need_dr, need_dx=need_dx)
+        return None, None, None, dx, dl, dr
+
+
+def hop_attention_recompute(adjhops: HopPlan, inputs: torch.Tensor, l: torch.Tensor, r: torch.Tensor, negative_slope: float = 0.2,
+                            hops: Optional[Iterable[int]] = None) -> torch.Tensor:
+    """:func:`hop_attention_heads` whose TRAINING step keeps no per-entry array: what that function computes, ``[n_cols, d] ->
+    [n_rows, H_sel, d]``, differentiable wrt ``inputs``, ``l`` and ``r``.
+
+    With a gradient the forward is ONE launch that stores the result and the softmax statistics ``[n_rows, H_sel, 2, K]``
+    (:meth:`HopPlan.attention_heads_stats`), the backward ONE call that computes the scores, coefficients and their gradients again
+    per entry (:meth:`HopPlan.attention_heads_backward`): no ``[nnz_k, K]`` array is written, read or allocated in either.  The
+    forward has the chain's bits; the gradients are deterministic but have summation orders of their own (include/h2gcn_hip.h), so
+    they agree with the chain's to rounding, not bit for bit.  Without a gradient this is :meth:`HopPlan.attention_heads`.
+
+    A gradient for ``inputs`` or ``r`` sums over the columns of the hop matrices: the plan needs ``build_transpose=True`` (no
+    permutation: ``keep_permutation`` is not needed; a ``symmetric_pattern=True`` plan serves too).  ``K > 16``, ``d > 256`` and a
+    library that predates the two launches take :func:`hop_attention_heads`, the chain.  fp32 only.  Row-partitioned operands
+    (``ShardedHops``) are not covered."""
+    if hasattr(adjhops, "aggregate"):
+        raise ValueError("hop_attention_recompute is not supported on row-partitioned operands (ShardedHops): pass a single-GPU HopPlan")
+    if not isinstance(adjhops, HopPlan):
+        raise TypeError(f"adjhops must be a HopPlan, got {type(adjhops).__name__}")
+    sel = None if hops is None else tuple(sorted(set(int(h) for h in hops)))
+    grads = [torch.is_grad_enabled() and isinstance(t, torch.Tensor) and t.requires_grad for t in (inputs, l, r)]
+    n_heads = int(l.shape[2]) if isinstance(l, torch.Tensor) and l.dim() == 3 else 1
+    d = int(inputs.shape[1]) if isinstance(inputs, torch.Tensor) and inputs.dim() == 2 else 1
+    if (n_heads > HopPlan.ATTENTION_FUSED_MAX_HEADS or d > HopPlan.ATTENTION_RECOMPUTE_MAX_WIDTH
+            or not all(_capi.has(s) for s in HopPlan._RECOMPUTE_SYMBOLS)):
+        return hop_attention_heads(adjhops, inputs, l, r, negative_slope, sel)
+    if not any(grads):
+        return adjhops.attention_heads(inputs, l, r, negative_slope, hops=sel)
+    if (grads[0] or grads[2]) and not adjhops.has_transpose:
+        raise ValueError("hop_attention_recompute with inputs or an r that require a gradient: those gradients sum over the columns of the "
+                         "hop matrices, on the plan's transposed operands (their permutation is not needed).  Build the plan with "
+                         "HopPlan(..., build_transpose=True)")
+    # (the argument checks of the launch run first either way: HopPlan.attention_heads_stats refuses before any device work)
+    return _HopAttentionRecompute.apply(adjhops, sel, float(negative_slope), inputs, l, r)
+
+
 class _StackHeads(torch.autograd.Function):
     """``torch.stack(per_head, dim=2)`` of ``K`` ``[N, H_sel]`` projections; the backward hands every head a CONTIGUOUS ``[N, H_sel]``
     gradient, the operand the per-head chain gave the projection's GEMMs (so they run as before, on the same bits)."""
@@ -554,6 +613,43 @@ class MultiHeadHopAttention(torch.nn.Module):
     def extra_repr(self) -> str:
         return (f"in_dim={self.in_dim}, heads={self.heads}, hops={None if self.hops is None else list(self.hops)}, "
                 f"negative_slope={self.negative_slope}")
+
+
+class RecomputeMultiHeadHopAttention(MultiHeadHopAttention):
+    """:class:`MultiHeadHopAttention` -- the same constructor, parameters and ``state_dict`` -- whose training step keeps no
+    per-entry array: ``l`` and ``r`` are built exactly as the parent class builds them (per-head projections, stacked to ``[N, H_sel,
+    K]``) and go to :func:`hop_attention_recompute`, one launch forward and one call backward.  The output has the parent's bits;
+    the parameter gradients agree with the parent's to rounding (their summation orders differ) and are as deterministic.  Peak
+    memory no longer grows with ``nnz * K``.  Training needs a square plan built with ``build_transpose=True`` (``keep_permutation``
+    is not needed); such layers can be stacked on one plan, share it with a ``GCNLayer``, and their training step can be captured
+    in a hipGraph after one eager warm-up.  ``heads > 16`` or ``in_dim > 256`` run the parent's chain."""
+
+    def forward(self, adjhops: HopPlan, inputs: torch.Tensor) -> torch.Tensor:
+        if hasattr(adjhops, "aggregate"):
+            raise ValueError("RecomputeMultiHeadHopAttention is not supported on row-partitioned operands (ShardedHops): pass a single-GPU "
+                             "HopPlan")
+        if not isinstance(adjhops, HopPlan):
+            raise TypeError(f"adjhops must be a HopPlan, got {type(adjhops).__name__}")
+        h_sel = self.a_l.shape[0]
+        if adjhops.n_selected(self.hops) != h_sel:
+            raise ValueError(f"RecomputeMultiHeadHopAttention holds attention vectors for {h_sel} hops, the plan has {adjhops.n_hops}: pass "
+                             "hops= or n_hops=")
+        if adjhops.n_rows != adjhops.n_cols:
+            raise ValueError("RecomputeMultiHeadHopAttention needs a square plan (the same nodes attend and are attended to), got "
+                             f"{adjhops.n_rows} x {adjhops.n_cols}")
+        if inputs.dim() != 2 or inputs.shape[1] != self.in_dim:
+            raise ValueError(f"inputs must be [{adjhops.n_cols}, {self.in_dim}], got {tuple(inputs.shape)}")
+        n_heads, w = self.heads, self.in_dim // self.heads
+        if (n_heads > HopPlan.ATTENTION_FUSED_MAX_HEADS or self.in_dim > HopPlan.ATTENTION_RECOMPUTE_MAX_WIDTH
+                or not all(_capi.has(s) for s in HopPlan._RECOMPUTE_SYMBOLS)):
+            return super().forward(adjhops, inputs)
+        ls, rs = [], []
+        for h in range(n_heads):
+            x_h = inputs if n_heads == 1 else inputs[:, h * w:(h + 1) * w]
+            l, r = x_h @ self.a_l[:, h, :].t(), x_h @ self.a_r[:, h, :].t()
+            ls.append(l)
+            rs.append(r)
+        return hop_attention_recompute(adjhops, inputs, _StackHeads.apply(*ls), _StackHeads.apply(*rs), self.negative_slope, self.hops)
 
 
 class GCNLayer(torch.nn.Module):

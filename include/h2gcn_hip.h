@@ -706,6 +706,71 @@ int h2gcn_attention_hops_heads_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, 
                                    float* Y_dev, int64_t ldy_row, int64_t ldy_hop, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * Training attention without per-entry arrays (added within ABI 5; found by symbol like the launches above): the forward above
+ * that ALSO STORES THE SOFTMAX STATISTICS, and a RECOMPUTING BACKWARD that reads them.  Nothing of size nnz is read, written or
+ * allocated by either; no workspace, no atomics; all offsets 64-bit; fp32 only.
+ *
+ * h2gcn_attention_hops_heads_stats_f32: the arguments of h2gcn_attention_hops_heads_f32 plus stats_dev [n_rows, H_sel, 2, K]
+ * through ldstats >= H_sel*2*K: element (i, s, 0, h) at i*ldstats + s*2*K + h is m, the maximum score of the segment, element
+ * (i, s, 1, h) at i*ldstats + s*2*K + K + h is 1/S -- the values the walk holds anyway.  Y is bit for bit what
+ * h2gcn_attention_hops_heads_f32 stores (hence the chain's bits); an empty segment stores (+0, +0); a segment whose maximum is NaN
+ * stores NaN.  The same validation, plus: ldstats too small, a NULL stats, a stats that IS Y, X, l or r.  K <= 16.
+ *
+ * h2gcn_attention_hops_heads_backward_f32: given G = dLoss/dY [n_rows, H_sel, d] (through ldg_row / ldg_hop), the forward's l, r,
+ * X, stats and Y, for every entry e = (i, j) of selected hop s and head h (columns c of head h):
+ *
+ *     pre = l[i,s,h] + r[j,s,h]       alpha[e,h] = exp2((leaky(pre) - m[i,s,h]) * log2e) * rinv[i,s,h]      (the forward's operations)
+ *     dalpha[e,h] = sum_c G[i,s,c] * X[j,c]                delta[i,s,h] = sum_c G[i,s,c] * Y[i,s,c]
+ *     dscore = alpha * (dalpha - delta)                    dpre = pre > 0 ? dscore : dscore * negative_slope   (a NaN pre: the slope branch)
+ *     dl[i,s,h] = sum_{e in row i} dpre      dr[j,s,h] = sum_{e in column j} dpre      dX[j,c] = sum_s sum_{e in column j} alpha[e,h(c)] * G[i,s,c]
+ *
+ * Outputs, each optional (NULL: not wanted; at least one must be wanted): dl_dev [n_rows, H_sel, K] through lddl, dr_dev [n_cols,
+ * H_sel, K] through lddr, dX_dev [n_cols, d] through lddx; delta_dev [n_rows, H_sel, K] through lddelta is a caller-provided buffer
+ * that the ROW SIDE fills and the COLUMN SIDE reads (it may be NULL when only dl is wanted).  Two launches: the row side (always)
+ * walks A_s and gathers X[j], r[j,s]; the column side (when dr or dX is wanted) walks A_s^T and gathers G[i,s] and the 4 K node
+ * floats l, m, 1/S, delta of row i.  THE COLUMN SIDE READS t_rowptr / t_colidx ONLY, never the permutation: a plan created with
+ * H2GCN_PLAN_BUILD_TRANSPOSE but without H2GCN_PLAN_KEEP_PERMUTATION is served, and so is a symmetric plan on its forward arrays;
+ * a plan without transposes gets H2GCN_ERR_NO_TRANSPOSE when dr or dX is wanted (dl alone needs none).
+ * Widths: K == 1 takes any d up to 256; K > 1 needs d % K == 0 and (d / K) % 4 == 0; d > 256 is refused with a message naming the
+ * limit (run the chain), as is K > 16.
+ *
+ * THE GRADIENTS ARE DETERMINISTIC BUT NOT THE CHAIN'S BITS: two launches on the same operands give the same bits, yet delta comes
+ * from <G, Y> over the head's columns, not from the chain's sum of alpha * dalpha over the segment (the two are equal in exact
+ * arithmetic because Y is the alpha-weighted sum of the X[j]), and the sums below have orders of their own.  THE SUMMATION ORDERS:
+ *   per-entry dot products (dalpha, delta): the SDDMM's order on the head's column slice -- per quad of 4 columns t = g0*x0, then
+ *            fma(g1, x1, t), fma(g2, x2, t), fma(g3, x3, t); the 16 quads of a 64-column block by the xor butterfly over quad
+ *            distances 1, 2, 4, 8; block totals added in ascending order from +0;
+ *   dl / dr: the row-softmax tree over the WALKED segment (row i of A_s for dl, row j of A_s^T for dr): 256 partials P[t mod 256], each
+ *            from +0, accumulated in ascending position t; W_w the xor butterfly over index distances 1..32 of P[64w .. 64w+63];
+ *            the element is (W_0 + W_1) + (W_2 + W_3);
+ *   dX:      per selected hop the canonical aggregation tree over row j of A_s^T -- the 64-entry chunks of the segment are dealt to
+ *            four sets, chunk t to set t mod 4; within a set entry jj of a chunk goes into P[jj & 3] with one fmaf from +0, chunks in
+ *            ascending order, T_u = (P0 + P1) + (P2 + P3); the hop's total is ((T0 + T1) + T2) + T3; the element is the sum of the hop
+ *            totals in ascending hop order.
+ * One tree per output element: the bits do not depend on long_row_threshold, rows_per_wave or the kernel geometry; dl / dr of a hop
+ * do not depend on which other hops are selected.  A non-finite operand reaches exactly the elements whose sums touch it.
+ *
+ * hipGraph capture: the rule of the forward launch -- both long-segment lists of the selection (the forward's and the adjoint's)
+ * are built by the first launch of that selection, so a training step can be captured after one eager warm-up.  A selection
+ * without nonzeros is a memset of the outputs.
+ *
+ * Validation, all before the device is touched, each H2GCN_ERR_INVALID_ARGUMENT with a message naming the argument unless noted: a
+ * NULL plan ("plan is NULL"), a hop mask outside the plan, d < 1, n_heads < 1, n_heads > 16, d % n_heads, (d / n_heads) % 4 with
+ * heads, d > 256, no output wanted, a leading dimension too small, hop strides that overlap, a NULL delta when dr or dX is
+ * wanted, a plan without transposes when dr or dX is wanted (H2GCN_ERR_NO_TRANSPOSE), a NULL input when the selection has
+ * nonzeros, an output that IS an input or another output.
+ */
+int h2gcn_attention_hops_heads_stats_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* l_dev, int64_t ldl, const float* r_dev,
+                                         int64_t ldr, int32_t n_heads, float negative_slope, const float* X_dev, int64_t ldx, int32_t d,
+                                         float* Y_dev, int64_t ldy_row, int64_t ldy_hop, float* stats_dev, int64_t ldstats, void* stream);
+int h2gcn_attention_hops_heads_backward_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* l_dev, int64_t ldl, const float* r_dev,
+                                            int64_t ldr, int32_t n_heads, float negative_slope, const float* X_dev, int64_t ldx, int32_t d,
+                                            const float* stats_dev, int64_t ldstats, const float* Y_dev, int64_t ldy_row, int64_t ldy_hop,
+                                            const float* G_dev, int64_t ldg_row, int64_t ldg_hop, float* delta_dev, int64_t lddelta,
+                                            float* dl_dev, int64_t lddl, float* dr_dev, int64_t lddr, float* dX_dev, int64_t lddx,
+                                            void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * Operand construction on the device: exact-k-hop neighbourhood rings and their normalisation -- the step that
  * FEEDS the aggregation.  Stands in for TransformSPAdj.nhoodSplit (reference h2gcn/datasets/_dataset.py:138-158:
  * `mt <- bin(mt @ (A + I))`, ring_k = mt_k - mt_{k-1}, a host SpGEMM in scipy) and TransformSPAdj.normalize

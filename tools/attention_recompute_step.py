@@ -1,0 +1,105 @@
+"""One attention training step (forward + backward, device events), the chain against the recomputing path, in ONE process:
+MultiHeadHopAttention and RecomputeMultiHeadHopAttention (the same parameters) take turns on the synthetic operands of
+h2gcn_amd/synth.py, d = 128, K = 8 heads, both hops; operands built as tools/attention_heads_step.py builds them.
+usage: python tools/attention_recompute_step.py [--shapes arxiv,products] [--d D] [--heads K] [--reps R] [--rounds Q]
+The measuring loop is tools/_launch_timing.py: a figure is the median of R steps (default 12); Q rounds (default 2), whose spread
+is the noise.  Peak memory: torch.cuda.max_memory_allocated over one step of each layer, above what is allocated before it.
+
+Then the three launches of the recomputing step one by one.  "of 8 TB/s": the byte model below over the time, as a fraction of
+8e12 B/s (the node terms: the rows a launch reads or writes once):
+    forward + stats     sum_k nnz_k * (4 + 4K + 4d)     colidx, the gathered r and x rows     + n * H * (d + 3K) * 4 + n * d * 4
+    backward, row side  sum_k nnz_k * (4 + 4K + 4d)     colidx, the gathered r and x rows     + n * H * (2d + 5K) * 4
+    backward, col side  sum_k nnz_k * (4 + 16K + 4d)    t_colidx, the gathered g row and l, m, 1/S, delta of row i
+                                                                                              + n * d * 8 + n * H * K * 8
+every one + (n + 1) * 8 * H for the row pointers.  The row side alone is the backward with need_dl only; the column side is the
+full backward minus the row side."""
+import argparse
+import sys
+from pathlib import Path
+
+import torch
+
+sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
+from _launch_timing import print_bandwidth, round_medians, warm_up
+from h2gcn_amd import HopPlan, MultiHeadHopAttention, RecomputeMultiHeadHopAttention, synth
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--shapes", default="arxiv,products")
+ap.add_argument("--d", type=int, default=128)
+ap.add_argument("--heads", type=int, default=8)
+ap.add_argument("--reps", type=int, default=12)
+ap.add_argument("--rounds", type=int, default=2)
+a = ap.parse_args()
+dev = torch.device("cuda:0")
+d, K = a.d, a.heads
+
+for shape in a.shapes.split(","):
+    cfg = synth.SHAPES[shape]
+    n = cfg["n"]
+    degs = synth.hop_degrees(cfg)
+    csr = [synth.synth_hop_rows(degs[k], n, (synth.SEED_A1, synth.SEED_A2)[k], 0, n, dev) for k in range(2)]
+    plan = HopPlan([c[0] for c in csr], [c[1] for c in csr], [c[2].clone() for c in csr], n, build_transpose=True, keep_permutation=True)
+    H, nnz = plan.n_hops, plan.nnz
+    gen = torch.Generator(device=dev).manual_seed(21)
+    x = (torch.rand((n, d), device=dev, generator=gen) * 2 - 1).requires_grad_(True)
+    weight = torch.rand((n, H, d), device=dev, generator=gen) * 2 - 1
+    torch.manual_seed(22)
+    layers = {"chain": MultiHeadHopAttention(d, K).to(dev), "recompute": RecomputeMultiHeadHopAttention(d, K).to(dev)}
+    layers["recompute"].load_state_dict(layers["chain"].state_dict())
+
+    def step_of(layer):
+        def step():
+            x.grad = None
+            for p in layer.parameters():
+                p.grad = None
+            (layer(plan, x) * weight).sum().backward()
+        return step
+
+    print(f"== {shape}: n = {n}, d = {d}, K = {K}, nonzeros per hop {nnz}")
+    fns = {name: step_of(layer) for name, layer in layers.items()}
+    warm_up(fns)
+    med = round_medians(fns, a.reps, a.rounds)
+    for name in fns:
+        print(f"   step, {name:9s} " + "  ".join(f"round {r}: {t:9.4f} ms" for r, t in enumerate(med[name])))
+    print("   chain / recompute: " + "  ".join(f"{u / v:.2f}" for u, v in zip(med["chain"], med["recompute"])))
+    for name, fn in fns.items():
+        torch.cuda.synchronize()
+        x.grad = None
+        for p in layers[name].parameters():
+            p.grad = None
+        torch.cuda.empty_cache()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        fn()
+        torch.cuda.synchronize()
+        print(f"   peak memory of one step above its start, {name:9s} {(torch.cuda.max_memory_allocated() - base) / 2 ** 20:10.1f} MiB   "
+              f"checksum dx {float(x.grad.double().sum()):.9e}  da_l {float(layers[name].a_l.grad.double().sum()):.9e}")
+    x.grad = None
+    with torch.no_grad():
+        xd = x.detach()
+        l, r = torch.rand((n, H, K), device=dev, generator=gen) * 2 - 1, torch.rand((n, H, K), device=dev, generator=gen) * 2 - 1
+        y, stats = plan.attention_heads_stats(xd, l, r)
+        out = torch.empty_like(y)
+        S, rows = sum(nnz), (n + 1) * 8 * H
+        gather = S * (4 + 4 * K + 4 * d)
+        fns = {
+            "forward + stats": lambda: plan.attention_heads_stats(xd, l, r, out=out),
+            "forward (no stats)": lambda: plan.attention_heads(xd, l, r, out=out),
+            "backward, row side (dl only)": lambda: plan.attention_heads_backward(xd, l, r, stats, y, weight, need_dr=False, need_dx=False),
+            "backward, both sides": lambda: plan.attention_heads_backward(xd, l, r, stats, y, weight),
+        }
+        row_bytes = gather + n * H * (2 * d + 5 * K) * 4 + rows
+        col_bytes = S * (4 + 16 * K + 4 * d) + n * d * 8 + n * H * K * 8 + rows
+        nbytes = {"forward + stats": gather + n * H * (d + 3 * K) * 4 + n * d * 4 + rows,
+                  "forward (no stats)": gather + n * H * (d + K) * 4 + n * d * 4 + rows,
+                  "backward, row side (dl only)": row_bytes, "backward, both sides": row_bytes + col_bytes}
+        warm_up(fns)
+        med = round_medians(fns, a.reps, a.rounds)
+        width = max(len(k) for k in fns) + 2
+        for k in fns:
+            print_bandwidth(k, width, med[k], nbytes[k])
+        col = [b - c for b, c in zip(med["backward, both sides"], med["backward, row side (dl only)"])]
+        print_bandwidth("backward, column side (both - row)", width, col, col_bytes)
+        del l, r, y, stats, out, fns
+    del plan, csr, x, weight, layers
+    torch.cuda.empty_cache()
