@@ -18,7 +18,9 @@ C ABI of ``include/h2gcn_hip.h``).  It mirrors the reference's operator interfac
 * :func:`h2gcn_amd.layers.hop_attention_heads` -- scores, softmax and aggregation of all heads in ONE launch for every forward
   that needs no gradient (the chain's bits, no per-entry array) (new);
 * :func:`h2gcn_amd.layers.hop_attention_recompute` / :class:`h2gcn_amd.layers.RecomputeMultiHeadHopAttention` -- the attention
-  TRAINING step without per-entry arrays: a forward that stores the softmax statistics and a backward that recomputes per entry (new);
+  TRAINING step without per-entry arrays: a forward that stores the softmax statistics and a backward that recomputes per entry;
+  :func:`h2gcn_amd.layers.hop_attention_recompute_dropout` / ``layer.set_attention_dropout(p)``: dropout on the attention
+  coefficients, the mask drawn inside those kernels (new);
 * :class:`h2gcn_amd.hops.HopPlan` -- the device-resident ``adj_hops`` operand list
   (reference ``h2gcn/datasets/_dataset.py:559-576``);
 * :mod:`h2gcn_amd.operands` -- construction of the normalised exact-k-hop matrices: on the device with the HIP ring
@@ -46,5 +48,5 @@ __version__ = "0.6.0"
 from . import _capi  # noqa: F401  (does not load the library until first use)
 from .hops import HopPlan, RowSelection  # noqa: F401
 from .layers import (ConcatLayer, DropoutDense, GCNLayer, HopAttention, MultiHeadHopAttention, RecomputeMultiHeadHopAttention,  # noqa: F401
-                     SliceLayer, SparseDense, SparseDropout, hop_attention_heads, hop_attention_recompute, hop_edge_scores,
+                     SliceLayer, SparseDense, SparseDropout, hop_attention_heads, hop_attention_recompute, hop_attention_recompute_dropout, hop_edge_scores,
                      hop_edge_scores_heads, hop_softmax, hop_softmax_heads, hop_spmm, hop_spmm_values)

@@ -74,6 +74,9 @@ EXPORTED_SYMBOLS = (
     "h2gcn_attention_hops_heads_f32",
     "h2gcn_attention_hops_heads_stats_f32",
     "h2gcn_attention_hops_heads_backward_f32",
+    "h2gcn_attention_hops_heads_stats_dropout_f32",
+    "h2gcn_attention_hops_heads_backward_dropout_f32",
+    "h2gcn_attention_dropout_factors_hops_f32",
     "h2gcn_ring_scratch_bytes",
     "h2gcn_ring_count",
     "h2gcn_ring_fill",
@@ -288,6 +291,17 @@ def lib() -> C.CDLL:
         L.h2gcn_attention_hops_heads_backward_f32.argtypes = node_args + [
             C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
             C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+    if hasattr(L, "h2gcn_attention_hops_heads_stats_dropout_f32"):   # (attention dropout, added within ABI 5: the arguments of the pair
+        mask_args = [C.c_float, C.c_uint64, C.c_void_p]              # above + keep_prob, seed, step_dev in front of the stream)
+        L.h2gcn_attention_hops_heads_stats_dropout_f32.restype = C.c_int
+        L.h2gcn_attention_hops_heads_stats_dropout_f32.argtypes = (list(L.h2gcn_attention_hops_heads_stats_f32.argtypes[:-1]) + mask_args
+                                                                   + [C.c_void_p])
+        L.h2gcn_attention_hops_heads_backward_dropout_f32.restype = C.c_int
+        L.h2gcn_attention_hops_heads_backward_dropout_f32.argtypes = (list(L.h2gcn_attention_hops_heads_backward_f32.argtypes[:-1])
+                                                                      + mask_args + [C.c_void_p])
+        L.h2gcn_attention_dropout_factors_hops_f32.restype = C.c_int
+        L.h2gcn_attention_dropout_factors_hops_f32.argtypes = [C.c_void_p, C.c_uint32, C.c_int32] + mask_args + [
+            C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p]
     L.h2gcn_ring_scratch_bytes.restype = C.c_size_t
     L.h2gcn_ring_scratch_bytes.argtypes = [C.c_int64]
     ring_common = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -175,9 +175,10 @@ static void launch_forward(const Params& p, float*, int64_t, dim3 grid, hipStrea
 // (attention_stats.hip: its launcher, and stats [n_rows, H_sel, 2, K] through ldstats).
 int run(Launcher stats_launcher, float* stats, int64_t ldstats, const h2gcn_plan_t* plan, uint32_t hop_mask, const float* l, int64_t ldl,
         const float* r, int64_t ldr, int32_t n_heads, float slope, const float* X, int64_t ldx, int32_t d, float* Y, int64_t ldy_row,
-        int64_t ldy_hop, void* stream_v) {
+        int64_t ldy_hop, void* stream_v, ViewLauncher view_launcher, const void* ctx) {
     try {
         // every check below comes before the device is touched
+        const bool with_stats = stats_launcher || view_launcher;
         PatternView v;
         int st = pattern_view(plan, hop_mask, &v);
         if (st != H2GCN_OK) return st;
@@ -205,7 +206,7 @@ int run(Launcher stats_launcher, float* stats, int64_t ldstats, const h2gcn_plan
         if (Y == X) return fail(H2GCN_ERR_INVALID_ARGUMENT, "Y aliases X");
         if (Y == l) return fail(H2GCN_ERR_INVALID_ARGUMENT, "Y aliases l");
         if (Y == r) return fail(H2GCN_ERR_INVALID_ARGUMENT, "Y aliases r");
-        if (stats_launcher) {
+        if (with_stats) {
             if (ldstats < 2 * need)
                 return fail(H2GCN_ERR_INVALID_ARGUMENT, "ldstats = %lld < H_sel * 2 * n_heads = %lld", (long long)ldstats, (long long)(2 * need));
             if (!stats) return fail(H2GCN_ERR_INVALID_ARGUMENT, "stats is NULL");
@@ -223,7 +224,7 @@ int run(Launcher stats_launcher, float* stats, int64_t ldstats, const h2gcn_plan
             for (int s = 0; s < v.n_sel; ++s)
                 H2GCN_HIP_TRY(hipMemset2DAsync(Y + (int64_t)s * ldy_hop, (size_t)ldy_row * sizeof(float), 0, (size_t)d * sizeof(float),
                                                (size_t)v.n_rows, stream));
-            if (stats_launcher)   // every segment is empty: (+0, +0)
+            if (with_stats)   // every segment is empty: (+0, +0)
                 H2GCN_HIP_TRY(hipMemset2DAsync(stats, (size_t)ldstats * sizeof(float), 0, (size_t)(2 * need) * sizeof(float), (size_t)v.n_rows,
                                                stream));
             return H2GCN_OK;
@@ -235,11 +236,12 @@ int run(Launcher stats_launcher, float* stats, int64_t ldstats, const h2gcn_plan
         p.y = Y, p.ldy_row = ldy_row, p.ldy_hop = ldy_hop;
         p.d = d, p.K = n_heads, p.head_cols = d / n_heads;
         p.slope = slope;
-        (stats_launcher ? stats_launcher : launch_forward)(p, stats, ldstats, dim3((unsigned)n_blocks), stream);
+        if (view_launcher) view_launcher(p, stats, ldstats, v, ctx, dim3((unsigned)n_blocks), stream);
+        else (stats_launcher ? stats_launcher : launch_forward)(p, stats, ldstats, dim3((unsigned)n_blocks), stream);
         H2GCN_HIP_TRY(hipGetLastError());
         return H2GCN_OK;
     } catch (...) {
-        return fail(H2GCN_ERR_INTERNAL, "unexpected exception in attention_hops_heads%s_f32", stats_launcher ? "_stats" : "");
+        return fail(H2GCN_ERR_INTERNAL, "unexpected exception in attention_hops_heads%s_f32", view_launcher ? "_stats_dropout" : (stats_launcher ? "_stats" : ""));
     }
 }
 

@@ -340,11 +340,87 @@ __device__ __forceinline__ void segment_stats(const Params& p, int s, const floa
     }
 }
 
+// ---- the tile writers of the statistics kernels (attention_stats.hip, attention_dropout.hip)
+// A segment of `len` in 1..64 entries, lane = entry (col: its column, clamped): the coefficients of all heads into `tile`.
+// single_chunk_tile that also stores (m, 1/S) of every head to `st` (head h at st[h] and st[K + h]).
+__device__ __forceinline__ void single_chunk_tile_stats(const Params& p, int s, const float* lrow, int col, int len, int lane, float* tile,
+                                                        float* st) {
+    const bool ok = lane < len;
+    for (int h0 = 0; h0 < p.K; h0 += 4) {
+        const int nh = p.K - h0 < 4 ? p.K - h0 : 4;   // (wave-uniform)
+        float lv[4], sc[4];
+        load_heads(lrow, h0, nh, lv);
+        group_scores(p, s, col, h0, nh, lv, sc);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (k >= nh) continue;   // (wave-uniform)
+            const float x = ok ? sc[k] : neg_inf();
+            float m = bfly64_max(x);
+            if (__ballot(x != x) != 0ull) m = quiet_nan();
+            const float e = ok ? exp_t(x - m) : 0.f;   // P[lane] = +0 + e, the partials 64 .. 255 are +0
+            const float S = bfly64_add(e);             // = (W_0 + 0) + (0 + 0)
+            const float rinv = 1.0f / S;
+            const float a = e * rinv;
+            if (ok) tile[lane * p.K + h0 + k] = a;
+            if (lane == 0) st[h0 + k] = m, st[p.K + h0 + k] = rinv;
+        }
+    }
+}
+
+// Up to FOUR segments of at most 16 entries at once, lane group gi the segment of row `row` (per lane: its group's), lane q its
+// entry q: `len` in 0..16 entries from `beg` (0: the group has no such segment).  The reductions stay inside the 16-lane group --
+// the partials 16 .. 255 are +0, and W_0 + 0 adds no bit -- and the coefficients of group gi go to the entries 16 gi .. of `tile`.
+// Returns the column of the lane's entry.
+// short_tiles that also stores (m, 1/S) of the group's segment to `st` (per lane: its group's row; head h at st[h] and st[K + h]).
+__device__ __forceinline__ int short_tiles_stats(const Params& p, int s, int64_t row, int64_t beg, int len, int lane, float* tile, float* st) {
+    const bool ok = (lane & (kGroup - 1)) < len;
+    int col = 0;
+    if (ok) col = p.colidx[s][beg + (lane & (kGroup - 1))];
+    const float* lrow = p.l + row * p.ldl + (int64_t)s * p.K;
+    const float* rrow = p.r + (int64_t)col * p.ldr + (int64_t)s * p.K;
+    for (int h0 = 0; h0 < p.K; h0 += 4) {
+        const int nh = p.K - h0 < 4 ? p.K - h0 : 4;   // (wave-uniform)
+        float lv[4] = {0.f, 0.f, 0.f, 0.f}, rv[4] = {0.f, 0.f, 0.f, 0.f};
+        if (ok) {
+            load_heads(lrow, h0, nh, lv);
+            load_heads(rrow, h0, nh, rv);
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            if (k >= nh) continue;   // (wave-uniform)
+            const float x = ok ? leaky(lv[k] + rv[k], p.slope) : neg_inf();
+            const unsigned long long nan_lanes = __ballot(x != x);
+            float m = bfly16<Max>(x);
+            if ((nan_lanes >> (lane & 48)) & 0xffffull) m = quiet_nan();
+            const float e = ok ? exp_t(x - m) : 0.f;   // P[q] = +0 + e
+            const float S = bfly16<Add>(e);            // = W_0
+            const float rinv = 1.0f / S;
+            const float a = e * rinv;
+            if (ok) tile[lane * p.K + h0 + k] = a;
+            if (ok && (lane & (kGroup - 1)) == 0) st[h0 + k] = m, st[p.K + h0 + k] = rinv;
+        }
+    }
+    return col;
+}
+
+// The statistics of (row, selected hop s): m of head h at [h], 1/S at [K + h].
+__device__ __forceinline__ float* stat_row(const Params& p, float* stats, int64_t ldstats, int64_t row, int s) {
+    return stats + row * ldstats + (int64_t)s * 2 * p.K;
+}
+// `stat` (m at [h], 1/S at [kMaxHeads + h], written by this wave or behind a barrier) to the statistics row `st`.
+__device__ __forceinline__ void store_stats(const Params& p, const float* stat, float* st, int t) {
+    if (t < p.K) st[t] = stat[t], st[p.K + t] = stat[kMaxHeads + t];
+}
+
 // ---- host: the launch path both entry points share (attention_fused.hip)
 using Launcher = void (*)(const Params& p, float* stats, int64_t ldstats, dim3 grid, hipStream_t stream);
+// A launcher of another unit's statistics kernel (attention_dropout.hip): it also gets the view of the selection and `ctx`, and the
+// path checks `stats` as for a stats_launcher.
+using ViewLauncher = void (*)(const Params& p, float* stats, int64_t ldstats, const PatternView& v, const void* ctx, dim3 grid,
+                              hipStream_t stream);
 int run(Launcher stats_launcher, float* stats, int64_t ldstats, const h2gcn_plan_t* plan, uint32_t hop_mask, const float* l, int64_t ldl,
         const float* r, int64_t ldr, int32_t n_heads, float slope, const float* X, int64_t ldx, int32_t d, float* Y, int64_t ldy_row,
-        int64_t ldy_hop, void* stream_v);
+        int64_t ldy_hop, void* stream_v, ViewLauncher view_launcher = nullptr, const void* ctx = nullptr);
 
 }  // namespace attention_fused
 }  // namespace h2gcn

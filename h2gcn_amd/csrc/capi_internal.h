@@ -55,6 +55,10 @@ int adjoint_view(const h2gcn_plan* plan, uint32_t hop_mask, PatternView* out, co
 // permutation asked for -- a plan created without H2GCN_PLAN_KEEP_PERMUTATION is served.  H2GCN_ERR_NO_TRANSPOSE as above.
 int adjoint_pattern_view(const h2gcn_plan* plan, uint32_t hop_mask, PatternView* out);
 
+// The number of hops the plan was created with (a view's `mask` has a bit per hop of the plan): what the attention dropout generator
+// (attention_dropout.hip) keys an entry by, together with the plan's hop index.  `plan` must not be NULL.
+int plan_hop_count(const h2gcn_plan* plan);
+
 }  // namespace h2gcn
 
 #define H2GCN_HIP_TRY(expr)                                                                          \

@@ -1369,6 +1369,8 @@ int adjoint_pattern_view(const h2gcn_plan* plan, uint32_t hop_mask, PatternView*
     }
     return H2GCN_OK;
 }
+
+int plan_hop_count(const h2gcn_plan* plan) { return plan->n_hops; }
 }  // namespace h2gcn
 }  // extern "C++"
 

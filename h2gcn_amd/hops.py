@@ -961,6 +961,46 @@ class HopPlan:
         if not _capi.has(name):
             raise RuntimeError(f"{_capi.library_path()} predates the recomputing attention backward ({name}): rebuild it")
 
+    _DROPOUT_SYMBOLS = ("h2gcn_attention_hops_heads_stats_dropout_f32", "h2gcn_attention_hops_heads_backward_dropout_f32",
+                        "h2gcn_attention_dropout_factors_hops_f32")
+
+    def _mask_args(self, keep_prob, seed, step, symbol: str):
+        """``keep_prob``, ``seed``, ``step`` of an attention-dropout launch, checked -> the C ABI's ``(keep_prob, seed, step_dev)``, or
+        ``None`` for ``keep_prob == 1`` (today's call, argument for argument)."""
+        keep_prob = float(keep_prob)
+        _require(0.0 < keep_prob <= 1.0, f"keep_prob = {keep_prob} outside (0, 1]")
+        if keep_prob == 1.0:
+            return None
+        if step is not None:
+            _require(isinstance(step, torch.Tensor) and step.dtype == torch.int64 and step.numel() == 1 and step.device == self.device,
+                     f"step must be a 1-element int64 tensor on {self.device} (the device counter the kernels read), or None for step 0")
+        if not _capi.has(symbol):
+            raise RuntimeError(f"{_capi.library_path()} predates the attention dropout ({symbol}): rebuild it")
+        return (C.c_float(keep_prob), C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), C.c_void_p(step.data_ptr()) if step is not None else None)
+
+    def attention_dropout_factors(self, n_heads: int, keep_prob: float, seed: int, step: Optional[torch.Tensor] = None, hops=None) -> list:
+        """The dropout factors of the attention coefficients, per selected hop float32 ``[nnz_k, n_heads]`` with elements in
+        ``{0, 1 / keep_prob}`` (``h2gcn_attention_dropout_factors_hops_f32``): the mask :meth:`attention_heads_stats_dropout` and
+        :meth:`attention_heads_backward_dropout` draw inside their kernels for the same ``(keep_prob, seed, step)``, a function of the
+        entry's hop, row, column and head alone (include/h2gcn_hip.h).  For a chain that multiplies its ``alpha`` by them, and for
+        tests; ``1 <= n_heads <= 16``.  ``step``: a 1-element int64 tensor on the plan's device, or ``None`` for step 0."""
+        n_heads = int(n_heads)
+        _require(1 <= n_heads <= self.ATTENTION_FUSED_MAX_HEADS, f"n_heads = {n_heads} outside 1..{self.ATTENTION_FUSED_MAX_HEADS}")
+        mask, sel = self._mask(hops), self._selected(hops)
+        keep_prob = float(keep_prob)
+        margs = self._mask_args(keep_prob, seed, step, self._DROPOUT_SYMBOLS[2])
+        nnz = self.nnz
+        if margs is None:
+            return [torch.ones((nnz[k], n_heads), dtype=torch.float32, device=self.device) for k in sel]
+        out = [torch.empty((nnz[k], n_heads), dtype=torch.float32, device=self.device) for k in sel]
+        ld = (C.c_int64 * len(sel))(*[n_heads] * len(sel))
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            st = _capi.lib().h2gcn_attention_dropout_factors_hops_f32(self._handle, mask, n_heads, *margs, *self._segment_ptrs(out), ld,
+                                                                      C.c_void_p(stream))
+        _capi.check(st)
+        return out
+
     def attention_heads_stats(self, x: torch.Tensor, l: torch.Tensor, r: torch.Tensor, negative_slope: float = 0.2, hops=None,
                               out: Optional[torch.Tensor] = None) -> tuple:
         """:meth:`attention_heads` that also returns the softmax statistics -> ``(y, stats)``
@@ -968,7 +1008,21 @@ class HopPlan:
         ``[n_rows, H_sel, 2, K]``: ``stats[i, s, 0, h]`` the maximum score of the segment, ``stats[i, s, 1, h]`` the reciprocal of
         its sum of exponentials -- ``(+0, +0)`` for an empty segment.  With ``x, l, r, stats, y`` :meth:`attention_heads_backward`
         computes the gradients without any ``[nnz_k, K]`` array.  Operands and ``out`` as in :meth:`attention_heads`."""
+        return self._attention_heads_stats(x, l, r, negative_slope, hops, out, 1.0, 0, None)
+
+    def attention_heads_stats_dropout(self, x: torch.Tensor, l: torch.Tensor, r: torch.Tensor, keep_prob: float, seed: int,
+                                      step: Optional[torch.Tensor] = None, negative_slope: float = 0.2, hops=None,
+                                      out: Optional[torch.Tensor] = None) -> tuple:
+        """:meth:`attention_heads_stats` with dropout on the coefficients, the mask drawn inside the kernel from ``(seed, step)``
+        (``h2gcn_attention_hops_heads_stats_dropout_f32``; :meth:`attention_dropout_factors` returns the factors) -> ``(y, stats)``:
+        ``y`` has the bits of ``spmm_values(x, [alpha_k * f_k])``, ``stats`` are those without dropout.  ``keep_prob`` in ``(0, 1]``
+        (1: the launch without dropout); ``step``: a 1-element int64 tensor on the plan's device, read when the kernel runs, or
+        ``None`` for step 0.  :meth:`attention_heads_backward_dropout` with the same three computes the gradients."""
+        return self._attention_heads_stats(x, l, r, negative_slope, hops, out, keep_prob, seed, step)
+
+    def _attention_heads_stats(self, x, l, r, negative_slope, hops, out, keep_prob, seed, step) -> tuple:
         x, l, ldl, r, ldr, n_heads, d, mask, h_sel = self._attention_operands("fused attention forward", x, l, r, hops)
+        margs = self._mask_args(keep_prob, seed, step, self._DROPOUT_SYMBOLS[0])
         if out is not None:
             self._dense_output(out, h_sel, d)
             for name, t in (("the inputs", x), ("l", l), ("r", r)):
@@ -981,11 +1035,12 @@ class HopPlan:
             return out, stats
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            st = _capi.lib().h2gcn_attention_hops_heads_stats_f32(
+            fn = _capi.lib().h2gcn_attention_hops_heads_stats_f32 if margs is None else _capi.lib().h2gcn_attention_hops_heads_stats_dropout_f32
+            st = fn(
                 self._handle, mask, C.c_void_p(l.data_ptr()), ldl, C.c_void_p(r.data_ptr()), ldr, n_heads, float(negative_slope),
                 C.c_void_p(x.data_ptr()), x.stride(0) if self.n_cols > 1 else d, d, C.c_void_p(out.data_ptr()),
                 out.stride(0) if self.n_rows > 1 else h_sel * d, out.stride(1) if h_sel > 1 else d, C.c_void_p(stats.data_ptr()),
-                h_sel * 2 * n_heads, C.c_void_p(stream))
+                h_sel * 2 * n_heads, *(margs or ()), C.c_void_p(stream))
         _capi.check(st)
         return out, stats
 
@@ -1001,7 +1056,20 @@ class HopPlan:
         The gradients are deterministic; they are NOT the chain's bits (include/h2gcn_hip.h has the orders).  ``dr`` and ``dx`` walk
         the plan's transposed operands WITHOUT their permutation: ``build_transpose=True`` (or ``symmetric_pattern=True``) is
         enough.  ``d <= 256``."""
+        return self._attention_heads_backward(x, l, r, stats, y, grad, negative_slope, hops, need_dl, need_dr, need_dx, 1.0, 0, None)
+
+    def attention_heads_backward_dropout(self, x: torch.Tensor, l: torch.Tensor, r: torch.Tensor, stats: torch.Tensor, y: torch.Tensor,
+                                         grad: torch.Tensor, keep_prob: float, seed: int, step: Optional[torch.Tensor] = None,
+                                         negative_slope: float = 0.2, hops=None, need_dl: bool = True, need_dr: bool = True,
+                                         need_dx: bool = True) -> tuple:
+        """The backward of :meth:`attention_heads_stats_dropout` (``h2gcn_attention_hops_heads_backward_dropout_f32``):
+        :meth:`attention_heads_backward` whose kernels draw the forward's mask again from the forward's ``(keep_prob, seed, step)``
+        -- still nothing of size ``nnz``, and no permutation: the factor is keyed by the entry's row and column."""
+        return self._attention_heads_backward(x, l, r, stats, y, grad, negative_slope, hops, need_dl, need_dr, need_dx, keep_prob, seed, step)
+
+    def _attention_heads_backward(self, x, l, r, stats, y, grad, negative_slope, hops, need_dl, need_dr, need_dx, keep_prob, seed, step) -> tuple:
         x, l, ldl, r, ldr, n_heads, d, mask, h_sel = self._attention_operands("recomputing attention backward", x, l, r, hops)
+        margs = self._mask_args(keep_prob, seed, step, self._DROPOUT_SYMBOLS[1])
         _require(need_dl or need_dr or need_dx, "need_dl, need_dr and need_dx are all False: nothing to compute")
         _require(d <= self.ATTENTION_RECOMPUTE_MAX_WIDTH,
                  f"the recomputing attention backward serves at most d = {self.ATTENTION_RECOMPUTE_MAX_WIDTH} columns, got d = {d}: run the chain")
@@ -1028,11 +1096,13 @@ class HopPlan:
         ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # noqa: E731
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream(self.device).cuda_stream
-            st = _capi.lib().h2gcn_attention_hops_heads_backward_f32(
+            fn = (_capi.lib().h2gcn_attention_hops_heads_backward_f32 if margs is None
+                  else _capi.lib().h2gcn_attention_hops_heads_backward_dropout_f32)
+            st = fn(
                 self._handle, mask, ptr(l), ldl, ptr(r), ldr, n_heads, float(negative_slope), ptr(x), x.stride(0) if self.n_cols > 1 else d, d,
                 ptr(stats), h_sel * 2 * n_heads, ptr(y), y.stride(0) if self.n_rows > 1 else h_sel * d, y.stride(1) if h_sel > 1 else d,
                 ptr(grad), grad.stride(0) if self.n_rows > 1 else h_sel * d, grad.stride(1) if h_sel > 1 else d,
-                ptr(delta), h_sel * n_heads, ptr(dl), h_sel * n_heads, ptr(dr), h_sel * n_heads, ptr(dx), d, C.c_void_p(stream))
+                ptr(delta), h_sel * n_heads, ptr(dl), h_sel * n_heads, ptr(dr), h_sel * n_heads, ptr(dx), d, *(margs or ()), C.c_void_p(stream))
         _capi.check(st)
         return dl, dr, dx
 

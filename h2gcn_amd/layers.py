@@ -417,21 +417,45 @@ class _HopAttentionRecompute(torch.autograd.Function):
     (``HopPlan.attention_heads_backward``)."""
 
     @staticmethod
-    def forward(ctx, plan: HopPlan, hops, negative_slope: float, inputs: torch.Tensor, l: torch.Tensor, r: torch.Tensor):
-        y, stats = plan.attention_heads_stats(inputs, l, r, negative_slope, hops=hops)
+    def forward(ctx, plan: HopPlan, hops, negative_slope: float, inputs: torch.Tensor, l: torch.Tensor, r: torch.Tensor,
+                keep_prob: float = 1.0, seed: int = 0, step_dev: Optional[torch.Tensor] = None):
+        if keep_prob >= 1.0:   # (without dropout: today's calls, argument for argument)
+            y, stats = plan.attention_heads_stats(inputs, l, r, negative_slope, hops=hops)
+        else:
+            y, stats = plan.attention_heads_stats_dropout(inputs, l, r, float(keep_prob), int(seed), step_dev, negative_slope, hops=hops)
         ctx.plan, ctx.hops, ctx.negative_slope = plan, hops, negative_slope
-        ctx.save_for_backward(inputs, l, r, stats, y)
+        ctx.keep_prob, ctx.seed, ctx.has_step = float(keep_prob), int(seed), step_dev is not None
+        # (the mask is not stored: the backward draws it again from the same (seed, step))
+        ctx.save_for_backward(inputs, l, r, stats, y, _saved_step(step_dev, inputs.device))
         return y
 
     @staticmethod
     def backward(ctx, grad):
         need_dx, need_dl, need_dr = ctx.needs_input_grad[3:6]
         if not (need_dx or need_dl or need_dr):
-            return None, None, None, None, None, None
-        inputs, l, r, stats, y = ctx.saved_tensors
-        dl, dr, dx = ctx.plan.attention_heads_backward(inputs, l, r, stats, y, grad, ctx.negative_slope, hops=ctx.hops, need_dl=need_dl,
-                                                       need_dr=need_dr, need_dx=need_dx)
-        return None, None, None, dx, dl, dr
+            return None, None, None, None, None, None, None, None, None
+        inputs, l, r, stats, y, step = ctx.saved_tensors
+        if ctx.keep_prob >= 1.0:
+            dl, dr, dx = ctx.plan.attention_heads_backward(inputs, l, r, stats, y, grad, ctx.negative_slope, hops=ctx.hops, need_dl=need_dl,
+                                                           need_dr=need_dr, need_dx=need_dx)
+        else:
+            dl, dr, dx = ctx.plan.attention_heads_backward_dropout(inputs, l, r, stats, y, grad, ctx.keep_prob, ctx.seed,
+                                                                   step if ctx.has_step else None, ctx.negative_slope, hops=ctx.hops,
+                                                                   need_dl=need_dl, need_dr=need_dr, need_dx=need_dx)
+        return None, None, None, dx, dl, dr, None, None, None
+
+
+def _dropped_chain(adjhops: HopPlan, inputs: torch.Tensor, l: torch.Tensor, r: torch.Tensor, negative_slope: float, sel, keep_prob: float,
+                   seed: int, step) -> torch.Tensor:
+    """The chain of :func:`hop_attention_heads` with dropout on its coefficients: ``alpha_k * f_k``, ``f_k`` the factor arrays of
+    :meth:`HopPlan.attention_dropout_factors` -- the mask the fused launches draw, and the forward bits of the fused launch."""
+    n_heads = int(l.shape[2]) if isinstance(l, torch.Tensor) and l.dim() == 3 else 1
+    if n_heads > HopPlan.ATTENTION_FUSED_MAX_HEADS:
+        raise ValueError(f"attention dropout serves at most K = {HopPlan.ATTENTION_FUSED_MAX_HEADS} heads (the generator has one word per "
+                         f"pair of heads, eight per entry), got K = {n_heads}")
+    alpha = hop_softmax_heads(adjhops, hop_edge_scores_heads(adjhops, l, r, negative_slope, sel), sel)
+    factors = adjhops.attention_dropout_factors(n_heads, keep_prob, seed, step, hops=sel)
+    return hop_spmm_values(adjhops, inputs, [a * f for a, f in zip(alpha, factors)], sel)
 
 
 def hop_attention_recompute(adjhops: HopPlan, inputs: torch.Tensor, l: torch.Tensor, r: torch.Tensor, negative_slope: float = 0.2,
@@ -448,7 +472,33 @@ def hop_attention_recompute(adjhops: HopPlan, inputs: torch.Tensor, l: torch.Ten
     A gradient for ``inputs`` or ``r`` sums over the columns of the hop matrices: the plan needs ``build_transpose=True`` (no
     permutation: ``keep_permutation`` is not needed; a ``symmetric_pattern=True`` plan serves too).  ``K > 16``, ``d > 256`` and a
     library that predates the two launches take :func:`hop_attention_heads`, the chain.  fp32 only.  Row-partitioned operands
-    (``ShardedHops``) are not covered."""
+    (``ShardedHops``) are not covered.
+
+    :func:`hop_attention_recompute_dropout` is this step with dropout on the attention coefficients."""
+    return _hop_attention_recompute(adjhops, inputs, l, r, negative_slope, hops, 0.0, 0, None)
+
+
+def hop_attention_recompute_dropout(adjhops: HopPlan, inputs: torch.Tensor, l: torch.Tensor, r: torch.Tensor, dropout: float, seed: int = 0,
+                                    step: Optional[torch.Tensor] = None, negative_slope: float = 0.2,
+                                    hops: Optional[Iterable[int]] = None) -> torch.Tensor:
+    """:func:`hop_attention_recompute` with dropout on the attention coefficients; operands and limits as there.
+
+    ``dropout`` in ``[0, 1)``: dropout on the attention coefficients (GAT's ``attn_drop``) -- every coefficient is kept with
+    probability ``1 - dropout`` and scaled by ``1 / (1 - dropout)``.  The mask is a counter-based function of ``(seed, step, hop, row,
+    column, head)`` drawn INSIDE the forward and backward kernels (include/h2gcn_hip.h): still no ``[nnz_k, K]`` array, and the
+    backward redraws the forward's mask from the same ``(seed, step)``.  ``step``: a 1-element int64 tensor on the plan's device (read
+    when the kernels run, so a replayed hipGraph that bumps it draws a fresh mask; it must not change between a forward and its
+    backward -- pass a clone), or ``None`` for step 0.  It is applied whenever ``dropout > 0``, with or without a gradient: switching it
+    off for evaluation is the caller's (the layers do it).  ``d > 256`` and a library that predates the fused launches run the chain on
+    ``alpha_k * f_k`` with the factor arrays of :meth:`HopPlan.attention_dropout_factors`: the same mask, and the fused launch's forward
+    bits; ``K > 16`` with dropout is refused.  ``dropout = 0`` is :func:`hop_attention_recompute`, call for call."""
+    return _hop_attention_recompute(adjhops, inputs, l, r, negative_slope, hops, dropout, seed, step)
+
+
+def _hop_attention_recompute(adjhops, inputs, l, r, negative_slope, hops, dropout, seed, step) -> torch.Tensor:
+    dropout = float(dropout)
+    if not 0.0 <= dropout < 1.0:
+        raise ValueError(f"dropout = {dropout} outside [0, 1)")
     if hasattr(adjhops, "aggregate"):
         raise ValueError("hop_attention_recompute is not supported on row-partitioned operands (ShardedHops): pass a single-GPU HopPlan")
     if not isinstance(adjhops, HopPlan):
@@ -459,14 +509,20 @@ def hop_attention_recompute(adjhops: HopPlan, inputs: torch.Tensor, l: torch.Ten
     d = int(inputs.shape[1]) if isinstance(inputs, torch.Tensor) and inputs.dim() == 2 else 1
     if (n_heads > HopPlan.ATTENTION_FUSED_MAX_HEADS or d > HopPlan.ATTENTION_RECOMPUTE_MAX_WIDTH
             or not all(_capi.has(s) for s in HopPlan._RECOMPUTE_SYMBOLS)):
+        if dropout > 0.0:
+            return _dropped_chain(adjhops, inputs, l, r, negative_slope, sel, 1.0 - dropout, seed, step)
         return hop_attention_heads(adjhops, inputs, l, r, negative_slope, sel)
     if not any(grads):
+        if dropout > 0.0:   # (the mask applies without a gradient too: the statistics launch, its statistics dropped)
+            return adjhops.attention_heads_stats_dropout(inputs, l, r, 1.0 - dropout, seed, step, negative_slope, hops=sel)[0]
         return adjhops.attention_heads(inputs, l, r, negative_slope, hops=sel)
     if (grads[0] or grads[2]) and not adjhops.has_transpose:
         raise ValueError("hop_attention_recompute with inputs or an r that require a gradient: those gradients sum over the columns of the "
                          "hop matrices, on the plan's transposed operands (their permutation is not needed).  Build the plan with "
                          "HopPlan(..., build_transpose=True)")
     # (the argument checks of the launch run first either way: HopPlan.attention_heads_stats refuses before any device work)
+    if dropout > 0.0:
+        return _HopAttentionRecompute.apply(adjhops, sel, float(negative_slope), inputs, l, r, 1.0 - dropout, int(seed), step)
     return _HopAttentionRecompute.apply(adjhops, sel, float(negative_slope), inputs, l, r)
 
 
@@ -578,6 +634,42 @@ class MultiHeadHopAttention(torch.nn.Module):
         self.a_r = torch.nn.Parameter(torch.empty(h_sel, self.heads, self.in_dim // self.heads))
         torch.nn.init.xavier_uniform_(self.a_l)
         torch.nn.init.xavier_uniform_(self.a_r)
+        self.attn_dropout, self.seed = 0.0, None   # (see set_attention_dropout)
+
+    def set_attention_dropout(self, attn_dropout: float, seed: Optional[int] = None) -> "MultiHeadHopAttention":
+        """Dropout on the attention coefficients (GAT's ``attn_drop``) with rate ``attn_dropout`` in ``[0, 1)``, active in ``train()``
+        only; returns ``self``: ``layer = RecomputeMultiHeadHopAttention(d, 8).set_attention_dropout(0.6)``.  (A method, not a
+        constructor argument: the constructor, and with it the random numbers a model's construction consumes, stay as they are.)
+
+        The mask is a pure function of ``(seed, step, hop, row, column, head)`` (include/h2gcn_hip.h): ``step`` lives in a
+        non-persistent buffer ``_step`` bumped by a stream-ordered op per training forward (as :class:`DropoutDense` does), so the
+        ``state_dict`` is unchanged and a replayed hipGraph draws a fresh mask per replay.  The step counters of a model's layers
+        advance in lock step: a per-layer salt keeps two layers from drawing identical masks -- ``seed=None`` draws it from torch's
+        generator HERE (and only for ``attn_dropout > 0``), an integer sets it.  :class:`RecomputeMultiHeadHopAttention` draws the
+        mask inside its kernels; this class multiplies ``alpha`` by the factor arrays of :meth:`HopPlan.attention_dropout_factors`:
+        with equal seeds and steps the two give ``torch.equal`` outputs.  At most 16 heads."""
+        attn_dropout = float(attn_dropout)
+        if not 0.0 <= attn_dropout < 1.0:
+            raise ValueError(f"set_attention_dropout(attn_dropout={attn_dropout}) outside [0, 1)")
+        if attn_dropout > 0.0 and self.heads > HopPlan.ATTENTION_FUSED_MAX_HEADS:
+            raise ValueError(f"set_attention_dropout(attn_dropout={attn_dropout}) serves at most {HopPlan.ATTENTION_FUSED_MAX_HEADS} heads, "
+                             f"got heads = {self.heads}")
+        self.attn_dropout = attn_dropout
+        if attn_dropout > 0.0:
+            if seed is None:
+                seed = int(torch.randint(0, 2 ** 62, (1,)).item())
+            self.seed = int(seed) & 0x7FFFFFFFFFFFFFFF
+            if "_step" not in self._buffers:
+                self.register_buffer("_step", torch.zeros(1, dtype=torch.int64, device=self.a_l.device), persistent=False)
+        return self
+
+    def _draw_step(self):
+        """``(keep_prob, step)`` of one forward: in training with ``attn_dropout > 0`` the step counter advances (stream-ordered: a
+        captured graph bumps it on every replay) and ``step`` is the value this forward and its backward use; else ``(1.0, None)``."""
+        if not (self.training and self.attn_dropout > 0.0):
+            return 1.0, None
+        self._step += 1
+        return 1.0 - self.attn_dropout, self._step.clone()
 
     def forward(self, adjhops: HopPlan, inputs: torch.Tensor) -> torch.Tensor:
         if hasattr(adjhops, "aggregate"):
@@ -592,6 +684,9 @@ class MultiHeadHopAttention(torch.nn.Module):
         if inputs.dim() != 2 or inputs.shape[1] != self.in_dim:
             raise ValueError(f"inputs must be [{adjhops.n_cols}, {self.in_dim}], got {tuple(inputs.shape)}")
         n_heads, w = self.heads, self.in_dim // self.heads
+        keep_prob, step = self._draw_step()
+        # (dropout: alpha times the factor arrays -- the mask RecomputeMultiHeadHopAttention draws inside its kernels for this seed and step)
+        factors = None if step is None else adjhops.attention_dropout_factors(n_heads, keep_prob, self.seed, step, hops=self.hops)
         if n_heads > 1 and _capi.has("h2gcn_edge_scores_hops_heads_f32"):
             # one launch per link: the per-head projections as before, stacked to [N, H_sel, K]; entry-major [nnz_k, K] from there on
             ls, rs = [], []
@@ -601,18 +696,23 @@ class MultiHeadHopAttention(torch.nn.Module):
                 ls.append(l)
                 rs.append(r)
             scores = hop_edge_scores_heads(adjhops, _StackHeads.apply(*ls), _StackHeads.apply(*rs), self.negative_slope, self.hops)
-            return hop_spmm_values(adjhops, inputs, hop_softmax_heads(adjhops, scores, self.hops), self.hops)
+            alpha = hop_softmax_heads(adjhops, scores, self.hops)
+            if factors is not None:
+                alpha = [a * f for a, f in zip(alpha, factors)]
+            return hop_spmm_values(adjhops, inputs, alpha, self.hops)
         alpha = []
         for h in range(n_heads):
             x_h = inputs if n_heads == 1 else inputs[:, h * w:(h + 1) * w]
             l, r = x_h @ self.a_l[:, h, :].t(), x_h @ self.a_r[:, h, :].t()
             alpha.append(hop_softmax(adjhops, hop_edge_scores(adjhops, l, r, self.negative_slope, self.hops), self.hops))
         values = [torch.stack([alpha[h][s] for h in range(n_heads)], dim=0).t() for s in range(h_sel)]
+        if factors is not None:
+            values = [v * f for v, f in zip(values, factors)]
         return hop_spmm_values(adjhops, inputs, values, self.hops)
 
     def extra_repr(self) -> str:
         return (f"in_dim={self.in_dim}, heads={self.heads}, hops={None if self.hops is None else list(self.hops)}, "
-                f"negative_slope={self.negative_slope}")
+                f"negative_slope={self.negative_slope}" + (f", attn_dropout={self.attn_dropout}" if self.attn_dropout > 0.0 else ""))
 
 
 class RecomputeMultiHeadHopAttention(MultiHeadHopAttention):
@@ -642,14 +742,18 @@ class RecomputeMultiHeadHopAttention(MultiHeadHopAttention):
         n_heads, w = self.heads, self.in_dim // self.heads
         if (n_heads > HopPlan.ATTENTION_FUSED_MAX_HEADS or self.in_dim > HopPlan.ATTENTION_RECOMPUTE_MAX_WIDTH
                 or not all(_capi.has(s) for s in HopPlan._RECOMPUTE_SYMBOLS)):
-            return super().forward(adjhops, inputs)
+            return super().forward(adjhops, inputs)   # (the chain, on alpha * f under dropout: the same mask)
         ls, rs = [], []
         for h in range(n_heads):
             x_h = inputs if n_heads == 1 else inputs[:, h * w:(h + 1) * w]
             l, r = x_h @ self.a_l[:, h, :].t(), x_h @ self.a_r[:, h, :].t()
             ls.append(l)
             rs.append(r)
-        return hop_attention_recompute(adjhops, inputs, _StackHeads.apply(*ls), _StackHeads.apply(*rs), self.negative_slope, self.hops)
+        keep_prob, step = self._draw_step()
+        if step is None:
+            return hop_attention_recompute(adjhops, inputs, _StackHeads.apply(*ls), _StackHeads.apply(*rs), self.negative_slope, self.hops)
+        return hop_attention_recompute_dropout(adjhops, inputs, _StackHeads.apply(*ls), _StackHeads.apply(*rs), self.attn_dropout, self.seed,
+                                               step, self.negative_slope, self.hops)
 
 
 class GCNLayer(torch.nn.Module):

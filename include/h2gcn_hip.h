@@ -770,6 +770,60 @@ int h2gcn_attention_hops_heads_backward_f32(const h2gcn_plan_t* plan, uint32_t h
                                             float* dl_dev, int64_t lddl, float* dr_dev, int64_t lddr, float* dX_dev, int64_t lddx,
                                             void* stream);
 
+/* ATTENTION DROPOUT: dropout on the attention coefficients (GAT's attn_drop) of the recomputing pair above, with the mask DRAWN IN
+ * THE KERNELS (h2gcn_amd/csrc/attention_dropout.hip, attention_dropout_backward.hip).  Added within ABI 5: find the entry points by
+ * symbol.  Every (entry, head) has a factor f[e,h] in {+0, 1/keep_prob}; nothing of size nnz holds it, forward or backward.
+ *
+ * THE GENERATOR.  f is a pure function of (seed, step, k, i, j, h): k the PLAN's hop index (not the position in the selection), (i, j)
+ * the row and column of the stored entry in the plan's forward operand, h the head.  It does not depend on the entry's position in
+ * colidx or t_colidx, on the segment classes, long_row_threshold or rows_per_wave, on which hops are selected, or on whether the
+ * column side walks a built transpose or a symmetric plan's forward arrays.  With all integer arithmetic modulo 2^32 unless noted:
+ *     mix32(x):  x ^= x >> 16;  x *= 0x7FEB352D;  x ^= x >> 15;  x *= 0x846CA68B;  x ^= x >> 16
+ *     step = step_dev ? *step_dev : 0   (64 bits, read on the device when the kernel runs)
+ *     k0 = mix32(lo32(seed) ^ mix32(lo32(step) + 0x9E3779B9))       k1 = mix32(hi32(seed) ^ hi32(step) ^ k0 ^ 0x85EBCA6B)
+ *       (the key derivation of the classifier's dropout, the same constants)
+ *     gid = ((uint64(i) * n_cols + j) * n_hops_of_plan + k) * 8 + (h >> 1)       (modulo 2^64; one word per PAIR of heads)
+ *     w = lo32(gid) ^ rot16(hi32(gid)) ^ k0;  w ^= w >> 16;  w *= 0x7FEB352D;  w ^= k1;  w ^= w >> 15;  w *= 0x846CA68B;  w ^= w >> 16
+ *     field = (w >> 16 * (h & 1)) & 0xFFFF        kept iff field < thr,  thr = floor(keep_prob * 65536) computed in double (65536 at 1)
+ *     f = kept ? inv_keep : +0,   inv_keep = 1.f / keep_prob, one fp32 division on the host
+ * Any keep_prob in (0, 1] is served by this single mode; the realised keep probability is thr / 65536.
+ *
+ * WHERE f ENTERS (each time ONE fp32 multiply, never contracted into a neighbour):
+ *   forward       Y[i,s,c] = sum_e (alpha[e,h] * f[e,h]) * X[j_e,c]: the coefficient alpha * f is formed before it enters the aggregation
+ *                 tree of h2gcn_attention_hops_heads_f32, so Y has the bits of h2gcn_spmm_hops_values_f32 on the values alpha_k * f_k.  A
+ *                 dropped entry STILL multiplies: (alpha * 0) * inf is NaN, as in the chain.  stats are those of the launch without
+ *                 dropout, bit for bit (the dropout comes after the softmax);
+ *   row side      dalpha[e,h] = f[e,h] * <G[i,s], X[j]>_h;  delta = <G, Y>_h unchanged (Y carries f, so delta is still sum_e alpha * dalpha);
+ *   column side   dalpha the same;  dscore = alpha * (dalpha - delta) with the UNDROPPED alpha;  dX[j,c] += (alpha * f) * G[i,s,c], alpha * f
+ *                 one multiply as the forward forms it.
+ * dpre, dl, dr, the summation orders and every limit (K <= 16; backward d <= 256) are those of the pair above.
+ *
+ * h2gcn_attention_hops_heads_stats_dropout_f32 / h2gcn_attention_hops_heads_backward_dropout_f32: the arguments of
+ * h2gcn_attention_hops_heads_stats_f32 / h2gcn_attention_hops_heads_backward_f32 plus keep_prob, seed and step_dev (a device pointer to
+ * one int64, or NULL for step 0); the backward must be given the forward's (keep_prob, seed, *step_dev).  keep_prob == 1 dispatches to
+ * the launches without dropout: their bits.  keep_prob outside (0, 1] (NaN included) is refused FIRST, "keep_prob = ... outside (0, 1]";
+ * then the validation of the entry point without dropout, in its order, all before the device is touched.  hipGraph capture: the rule
+ * of those launches; step_dev is read when the kernel runs, so a replay after a stream-ordered bump of the counter draws a fresh mask.
+ *
+ * h2gcn_attention_dropout_factors_hops_f32: the factors themselves, for a chain that multiplies its alpha by them and for tests --
+ * f_dev[s][e * ldf_entry[s] + h] = f[e,h] for the entries e of selected hop s (ascending hop order) and h < n_heads; reads rowptr /
+ * colidx only.  Refused: a NULL plan, a hop mask outside the plan, n_heads < 1 or > 16, keep_prob outside (0, 1], and -- when the
+ * selection has nonzeros -- a NULL f_dev or f_dev[s], a NULL ldf_entry, ldf_entry[s] < n_heads.
+ */
+int h2gcn_attention_hops_heads_stats_dropout_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* l_dev, int64_t ldl,
+                                                 const float* r_dev, int64_t ldr, int32_t n_heads, float negative_slope, const float* X_dev,
+                                                 int64_t ldx, int32_t d, float* Y_dev, int64_t ldy_row, int64_t ldy_hop, float* stats_dev,
+                                                 int64_t ldstats, float keep_prob, uint64_t seed, const int64_t* step_dev, void* stream);
+int h2gcn_attention_hops_heads_backward_dropout_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* l_dev, int64_t ldl,
+                                                    const float* r_dev, int64_t ldr, int32_t n_heads, float negative_slope,
+                                                    const float* X_dev, int64_t ldx, int32_t d, const float* stats_dev, int64_t ldstats,
+                                                    const float* Y_dev, int64_t ldy_row, int64_t ldy_hop, const float* G_dev, int64_t ldg_row,
+                                                    int64_t ldg_hop, float* delta_dev, int64_t lddelta, float* dl_dev, int64_t lddl,
+                                                    float* dr_dev, int64_t lddr, float* dX_dev, int64_t lddx, float keep_prob, uint64_t seed,
+                                                    const int64_t* step_dev, void* stream);
+int h2gcn_attention_dropout_factors_hops_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, int32_t n_heads, float keep_prob, uint64_t seed,
+                                             const int64_t* step_dev, float* const* f_dev, const int64_t* ldf_entry, void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Operand construction on the device: exact-k-hop neighbourhood rings and their normalisation -- the step that
  * FEEDS the aggregation.  Stands in for TransformSPAdj.nhoodSplit (reference h2gcn/datasets/_dataset.py:138-158:

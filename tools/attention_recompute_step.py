@@ -1,7 +1,7 @@
 """One attention training step (forward + backward, device events), the chain against the recomputing path, in ONE process:
 MultiHeadHopAttention and RecomputeMultiHeadHopAttention (the same parameters) take turns on the synthetic operands of
 h2gcn_amd/synth.py, d = 128, K = 8 heads, both hops; operands built as tools/attention_heads_step.py builds them.
-usage: python tools/attention_recompute_step.py [--shapes arxiv,products] [--d D] [--heads K] [--reps R] [--rounds Q]
+usage: python tools/attention_recompute_step.py [--shapes arxiv,products] [--d D] [--heads K] [--reps R] [--rounds Q] [--attn_dropout P]
 The measuring loop is tools/_launch_timing.py: a figure is the median of R steps (default 12); Q rounds (default 2), whose spread
 is the noise.  Peak memory: torch.cuda.max_memory_allocated over one step of each layer, above what is allocated before it.
 
@@ -12,7 +12,12 @@ Then the three launches of the recomputing step one by one.  "of 8 TB/s": the by
     backward, col side  sum_k nnz_k * (4 + 16K + 4d)    t_colidx, the gathered g row and l, m, 1/S, delta of row i
                                                                                               + n * d * 8 + n * H * K * 8
 every one + (n + 1) * 8 * H for the row pointers.  The row side alone is the backward with need_dl only; the column side is the
-full backward minus the row side."""
+full backward minus the row side.
+
+--attn_dropout P (P > 0): the layers that take turns are instead (a) the recomputing layer WITHOUT dropout -- the kernels of the
+line above, the baseline -- (b) the recomputing layer with attention dropout P, its mask drawn inside the kernels, and (c) the chain
+layer with the same dropout, on alpha * f with the factor arrays; and the launches one by one are timed with and without the mask
+(the byte model is unchanged: the factor costs no bytes).  (b) and (c) draw the same mask per step (equal seeds)."""
 import argparse
 import sys
 from pathlib import Path
@@ -29,6 +34,7 @@ ap.add_argument("--d", type=int, default=128)
 ap.add_argument("--heads", type=int, default=8)
 ap.add_argument("--reps", type=int, default=12)
 ap.add_argument("--rounds", type=int, default=2)
+ap.add_argument("--attn_dropout", type=float, default=0.0)
 a = ap.parse_args()
 dev = torch.device("cuda:0")
 d, K = a.d, a.heads
@@ -44,8 +50,16 @@ for shape in a.shapes.split(","):
     x = (torch.rand((n, d), device=dev, generator=gen) * 2 - 1).requires_grad_(True)
     weight = torch.rand((n, H, d), device=dev, generator=gen) * 2 - 1
     torch.manual_seed(22)
-    layers = {"chain": MultiHeadHopAttention(d, K).to(dev), "recompute": RecomputeMultiHeadHopAttention(d, K).to(dev)}
-    layers["recompute"].load_state_dict(layers["chain"].state_dict())
+    P = a.attn_dropout
+    if P > 0:
+        layers = {"recompute, P = 0": RecomputeMultiHeadHopAttention(d, K).to(dev),
+                  "recompute, dropout": RecomputeMultiHeadHopAttention(d, K).set_attention_dropout(P, seed=23).to(dev),
+                  "chain, dropout": MultiHeadHopAttention(d, K).set_attention_dropout(P, seed=23).to(dev)}
+    else:
+        layers = {"chain": MultiHeadHopAttention(d, K).to(dev), "recompute": RecomputeMultiHeadHopAttention(d, K).to(dev)}
+    first = next(iter(layers.values()))
+    for layer in layers.values():
+        layer.load_state_dict(first.state_dict())
 
     def step_of(layer):
         def step():
@@ -55,13 +69,17 @@ for shape in a.shapes.split(","):
             (layer(plan, x) * weight).sum().backward()
         return step
 
-    print(f"== {shape}: n = {n}, d = {d}, K = {K}, nonzeros per hop {nnz}")
+    print(f"== {shape}: n = {n}, d = {d}, K = {K}, nonzeros per hop {nnz}" + (f", attention dropout {P}" if P > 0 else ""))
     fns = {name: step_of(layer) for name, layer in layers.items()}
     warm_up(fns)
     med = round_medians(fns, a.reps, a.rounds)
     for name in fns:
-        print(f"   step, {name:9s} " + "  ".join(f"round {r}: {t:9.4f} ms" for r, t in enumerate(med[name])))
-    print("   chain / recompute: " + "  ".join(f"{u / v:.2f}" for u, v in zip(med["chain"], med["recompute"])))
+        print(f"   step, {name:18s} " + "  ".join(f"round {r}: {t:9.4f} ms" for r, t in enumerate(med[name])))
+    if P > 0:
+        for name in ("recompute, P = 0", "chain, dropout"):
+            print(f"   {name} / recompute, dropout: " + "  ".join(f"{u / v:.3f}" for u, v in zip(med[name], med["recompute, dropout"])))
+    else:
+        print("   chain / recompute: " + "  ".join(f"{u / v:.2f}" for u, v in zip(med["chain"], med["recompute"])))
     for name, fn in fns.items():
         torch.cuda.synchronize()
         x.grad = None
@@ -72,7 +90,7 @@ for shape in a.shapes.split(","):
         base = torch.cuda.memory_allocated()
         fn()
         torch.cuda.synchronize()
-        print(f"   peak memory of one step above its start, {name:9s} {(torch.cuda.max_memory_allocated() - base) / 2 ** 20:10.1f} MiB   "
+        print(f"   peak memory of one step above its start, {name:18s} {(torch.cuda.max_memory_allocated() - base) / 2 ** 20:10.1f} MiB   "
               f"checksum dx {float(x.grad.double().sum()):.9e}  da_l {float(layers[name].a_l.grad.double().sum()):.9e}")
     x.grad = None
     with torch.no_grad():
@@ -88,11 +106,21 @@ for shape in a.shapes.split(","):
             "backward, row side (dl only)": lambda: plan.attention_heads_backward(xd, l, r, stats, y, weight, need_dr=False, need_dx=False),
             "backward, both sides": lambda: plan.attention_heads_backward(xd, l, r, stats, y, weight),
         }
+        if P > 0:
+            mask = (1.0 - P, 23, torch.ones(1, dtype=torch.int64, device=dev))   # keep_prob, seed, step
+            yd = plan.attention_heads_stats_dropout(xd, l, r, *mask)[0]
+            fns["forward + stats, dropout"] = lambda: plan.attention_heads_stats_dropout(xd, l, r, *mask, out=out)
+            fns["backward, row side, dropout"] = lambda: plan.attention_heads_backward_dropout(xd, l, r, stats, yd, weight, *mask,
+                                                                                               need_dr=False, need_dx=False)
+            fns["backward, both sides, dropout"] = lambda: plan.attention_heads_backward_dropout(xd, l, r, stats, yd, weight, *mask)
+            fns["the factor arrays"] = lambda: plan.attention_dropout_factors(K, *mask)
         row_bytes = gather + n * H * (2 * d + 5 * K) * 4 + rows
         col_bytes = S * (4 + 16 * K + 4 * d) + n * d * 8 + n * H * K * 8 + rows
         nbytes = {"forward + stats": gather + n * H * (d + 3 * K) * 4 + n * d * 4 + rows,
                   "forward (no stats)": gather + n * H * (d + K) * 4 + n * d * 4 + rows,
                   "backward, row side (dl only)": row_bytes, "backward, both sides": row_bytes + col_bytes}
+        nbytes.update({"forward + stats, dropout": nbytes["forward + stats"], "backward, row side, dropout": row_bytes,
+                       "backward, both sides, dropout": row_bytes + col_bytes, "the factor arrays": S * (4 + 4 * K) + rows})
         warm_up(fns)
         med = round_medians(fns, a.reps, a.rounds)
         width = max(len(k) for k in fns) + 2
