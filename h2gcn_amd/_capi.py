@@ -77,6 +77,9 @@ EXPORTED_SYMBOLS = (
     "h2gcn_attention_hops_heads_stats_dropout_f32",
     "h2gcn_attention_hops_heads_backward_dropout_f32",
     "h2gcn_attention_dropout_factors_hops_f32",
+    "h2gcn_attention_hops_heads_bf16",
+    "h2gcn_attention_hops_heads_stats_bf16",
+    "h2gcn_attention_hops_heads_backward_bf16",
     "h2gcn_ring_scratch_bytes",
     "h2gcn_ring_count",
     "h2gcn_ring_fill",
@@ -302,6 +305,18 @@ def lib() -> C.CDLL:
         L.h2gcn_attention_dropout_factors_hops_f32.restype = C.c_int
         L.h2gcn_attention_dropout_factors_hops_f32.argtypes = [C.c_void_p, C.c_uint32, C.c_int32] + mask_args + [
             C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.c_void_p]
+    if hasattr(L, "h2gcn_attention_hops_heads_bf16"):   # (the recomputing attention on bf16 embeddings, added within ABI 5: the
+        node_args = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_float,   # fp32 argument
+                     C.c_void_p, C.c_int64, C.c_int32]                              # orders with a dtype code in front of Y / dX)
+        L.h2gcn_attention_hops_heads_bf16.restype = C.c_int
+        L.h2gcn_attention_hops_heads_bf16.argtypes = node_args + [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p]
+        L.h2gcn_attention_hops_heads_stats_bf16.restype = C.c_int
+        L.h2gcn_attention_hops_heads_stats_bf16.argtypes = node_args + [C.c_int, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+                                                                        C.c_void_p]
+        L.h2gcn_attention_hops_heads_backward_bf16.restype = C.c_int
+        L.h2gcn_attention_hops_heads_backward_bf16.argtypes = node_args + [
+            C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_void_p, C.c_int64,
+            C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
     L.h2gcn_ring_scratch_bytes.restype = C.c_size_t
     L.h2gcn_ring_scratch_bytes.argtypes = [C.c_int64]
     ring_common = [C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -23,15 +23,23 @@ constexpr int kMaxBlocks = 4;    // 64-column blocks per row: d <= 256
 constexpr int kMaxHeads = 16;    // the tiles are 64 x kMaxHeads floats per wave
 constexpr int kSets = 4;         // chunk t of a segment belongs to set t mod 4
 
-struct Params {
+// E: the element type of the wide inputs x, y, g; TD: of dx (float, or bf16_t: attention_bf16.hip).  l, r, stats, delta, dl and dr
+// are fp32 whatever they are.
+template <typename E = float, typename TD = E>
+struct ParamsT {
     Geom geom;                             // of the walked operand: A_s (row side) or A_s^T (column side)
     const int32_t* idx[H2GCN_MAX_HOPS];    // its colidx: the OTHER node of every walked entry (the selected hops, packed)
-    const float *l, *r, *x, *stats, *y, *g;
-    float *delta, *dl, *dr, *dx;
+    const float *l, *r;
+    const E* x;
+    const float* stats;
+    const E *y, *g;
+    float *delta, *dl, *dr;
+    TD* dx;
     int64_t ldl, ldr, ldx, ldstats, ldy_row, ldy_hop, ldg_row, ldg_hop, lddelta, lddl, lddr, lddx;
     int d, K, w;                           // w = d / K
     float slope;
 };
+using Params = ParamsT<>;
 
 // COL: the column side (the row side has no alpha tile and no dx totals).
 template <int NB, bool COL>
@@ -76,16 +84,16 @@ __device__ __forceinline__ void clear(Quad (&acc)[NB]) {
 }
 
 // The held row of the packed geometry: columns 64 b + 4 q .. of `row`.
-template <int NB>
-__device__ __forceinline__ void load_row(const Params& p, const float* row, int q, Quad (&a)[NB]) {
+template <int NB, typename P, typename E>
+__device__ __forceinline__ void load_row(const P& p, const E* row, int q, Quad (&a)[NB]) {
 #pragma unroll
     for (int b = 0; b < NB; ++b) a[b] = load_quad<false>(row, b * kBlockCols + 4 * q, p.d);
 }
 
 // The per-head dot products of the held row (`a`: packed; `arow`: its address) with ONE other row `brow`, the same on every lane
 // group: head h to dst[h].  The order is the SDDMM's on the head's column slice.  All 64 lanes must be active.
-template <int L, int NB>
-__device__ __forceinline__ void row_dots(const Params& p, const Quad (&a)[NB], const float* arow, const float* brow, int lane, float* dst) {
+template <int L, int NB, typename P, typename E>
+__device__ __forceinline__ void row_dots(const P& p, const Quad (&a)[NB], const E* arow, const E* brow, int lane, float* dst) {
     const int q = lane & 15, gi = lane >> 4;
     if constexpr (L > 0) {
 #pragma unroll
@@ -110,28 +118,30 @@ __device__ __forceinline__ void row_dots(const Params& p, const Quad (&a)[NB], c
 // `count` (1..64) consecutive walked entries, their other nodes in `ecol` of lane n (clamped): dalpha of entry n, head h, to
 // dtile[n * K + h] -- the held row (`a` / `arow`) against row ecol[n] of `src` (ld_src apart).  COL: the same loads also go into
 // the dx accumulators, entry n into the partial of lane group n & 3 with one fmaf on atile[n * K + head].  All lanes active.
-template <int L, int NB, bool COL>
-__device__ __forceinline__ void chunk_dots(const Params& p, const Quad (&a)[NB], const float* arow, const float* src, int64_t ld_src, int ecol,
+template <int L, int NB, bool COL, typename P, typename E>
+__device__ __forceinline__ void chunk_dots(const P& p, const Quad (&a)[NB], const E* arow, const E* src, int64_t ld_src, int ecol,
                                            int count, int lane, float* dtile, const float* atile, const int (&head)[NB], Quad (&accx)[NB]) {
-    constexpr int U = 8 / NB;   // rounds per batch: 8 load instructions (8 KiB per wave) in flight
+    // rounds per batch: 8 load instructions (8 KiB per wave) in flight; 16 of a bf16 row, 8 KiB again
+    constexpr int U = (sizeof(E) == 2 ? 16 : 8) / NB;
+    using XV = typename Gathered<E>::type;   // (bf16: packed until the operation that consumes it)
     const int q = lane & 15, gi = lane >> 4;
     const int rounds = (count + 3) >> 2;
     if constexpr (L > 0 || COL) {
         for (int r0 = 0; r0 < rounds; r0 += U) {   // (wave-uniform)
-            Quad xv[U][NB];
+            XV xv[U][NB];
             float av[U][NB];
 #pragma unroll
             for (int u = 0; u < U; ++u)
                 if (r0 + u < rounds) {
                     const int n = 4 * (r0 + u) + gi < count ? 4 * (r0 + u) + gi : count - 1;
                     const int c = __builtin_amdgcn_ds_bpermute(n << 2, ecol);
-                    const float* row = src + (int64_t)c * ld_src;
+                    const E* row = src + (int64_t)c * ld_src;
                     if (COL) {
 #pragma unroll
                         for (int b = 0; b < NB; ++b) av[u][b] = atile[n * p.K + head[b]];
                     }
 #pragma unroll
-                    for (int b = 0; b < NB; ++b) xv[u][b] = load_quad<(L == 0)>(row, b * kBlockCols + 4 * q, p.d);
+                    for (int b = 0; b < NB; ++b) xv[u][b] = load_gathered<(L == 0)>(row, b * kBlockCols + 4 * q, p.d);
                 }
 #pragma unroll
             for (int u = 0; u < U; ++u)
@@ -140,16 +150,18 @@ __device__ __forceinline__ void chunk_dots(const Params& p, const Quad (&a)[NB],
                     if constexpr (L > 0) {
 #pragma unroll
                         for (int b = 0; b < NB; ++b) {
-                            const float t = bfly_head<L>(dot_quad(a[b], xv[u][b]));
+                            const float t = bfly_head<L>(dot_quad(a[b], widen(xv[u][b])));
                             const int hd = b * (16 / L) + q / L;
                             if (n < count && (q & (L - 1)) == 0 && hd < p.K) dtile[n * p.K + hd] = 0.f + t;   // element = +0 + B_0
                         }
                     }
                     if (COL && n < count) {
 #pragma unroll
-                        for (int b = 0; b < NB; ++b)
+                        for (int b = 0; b < NB; ++b) {
+                            const Quad& xq = widen(xv[u][b]);
 #pragma unroll
-                            for (int k = 0; k < 4; ++k) accx[b].v[k] = __builtin_fmaf(av[u][b], xv[u][b].v[k], accx[b].v[k]);
+                            for (int k = 0; k < 4; ++k) accx[b].v[k] = __builtin_fmaf(av[u][b], xq.v[k], accx[b].v[k]);
+                        }
                     }
                 }
         }
@@ -161,15 +173,15 @@ __device__ __forceinline__ void chunk_dots(const Params& p, const Quad (&a)[NB],
 #pragma unroll
             for (int b = 0; b < NB; ++b) ah[b] = load_quad(arow + h * p.w, b * kBlockCols + 4 * q, p.w);
             for (int r0 = 0; r0 < rounds; r0 += U) {
-                Quad xv[U][NB];
+                XV xv[U][NB];
 #pragma unroll
                 for (int u = 0; u < U; ++u)
                     if (r0 + u < rounds) {
                         const int n = 4 * (r0 + u) + gi < count ? 4 * (r0 + u) + gi : count - 1;
                         const int c = __builtin_amdgcn_ds_bpermute(n << 2, ecol);
-                        const float* row = src + (int64_t)c * ld_src + h * p.w;
+                        const E* row = src + (int64_t)c * ld_src + h * p.w;
 #pragma unroll
-                        for (int b = 0; b < NB; ++b) xv[u][b] = load_quad(row, b * kBlockCols + 4 * q, p.w);
+                        for (int b = 0; b < NB; ++b) xv[u][b] = load_gathered(row, b * kBlockCols + 4 * q, p.w);
                     }
 #pragma unroll
                 for (int u = 0; u < U; ++u)
@@ -177,7 +189,7 @@ __device__ __forceinline__ void chunk_dots(const Params& p, const Quad (&a)[NB],
                         const int n = 4 * (r0 + u) + gi;
                         float res = 0.f;
 #pragma unroll
-                        for (int b = 0; b < NB; ++b) res = res + bfly16<Add>(dot_quad(ah[b], xv[u][b]));   // block totals, ascending
+                        for (int b = 0; b < NB; ++b) res = res + bfly16<Add>(dot_quad(ah[b], widen(xv[u][b])));   // block totals, ascending
                         if (n < count && q == 0) dtile[n * p.K + h] = res;
                     }
             }

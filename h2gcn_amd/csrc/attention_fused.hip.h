@@ -16,17 +16,28 @@ constexpr int kMaxBlocks = 4;    // 64-column blocks of accumulators a lane keep
 constexpr int kLoads = 8;        // gather instructions in flight per batch of rounds (8 KiB per wave)
 constexpr int kMaxHeads = 16;    // K beyond it is refused: the tile is 64 x kMaxHeads floats per wave
 
-struct Params {
+// Gather instructions in flight per batch on a bf16 x (attention_bf16.hip).  A bf16 quad is 8 bytes, so 16 would keep the fp32
+// kernel's 8 KiB per wave in flight -- and did, at 177 VGPRs and 2 waves per SIMD in the 128-column geometry against 115 and 4 (the
+// row addresses and the coefficients of twice the rounds), 1.5x the fp32 launch's time at the products shape.  8 keeps the fp32
+// kernel's registers and occupancy, and the launch then runs in 0.84x the fp32 time (profiles/r24_attention_bf16_step.txt).
+constexpr int kLoadsBf16 = 8;
+
+// TX / TY: the element types of the wide operands (float, or bf16_t: attention_bf16.hip).  l, r and everything walk A touches
+// are fp32 whatever they are.
+template <typename TX = float, typename TY = TX>
+struct ParamsT {
+    using X = TX;
     Geom geom;
     const int32_t* colidx[H2GCN_MAX_HOPS];   // the selected hops, packed as geom.rowptr
     const float* l;                          // [n_rows, n_sel, K]: element (i, s, h) at i * ldl + s * K + h
     const float* r;                          // [n_cols, n_sel, K]
-    const float* x;                          // [n_cols, d] through ldx
-    float* y;                                // [n_rows, n_sel, d] through ldy_row / ldy_hop
+    const TX* x;                             // [n_cols, d] through ldx
+    TY* y;                                   // [n_rows, n_sel, d] through ldy_row / ldy_hop
     int64_t ldl, ldr, ldx, ldy_row, ldy_hop;
     int d, K, head_cols;                     // head_cols = d / K
     float slope;
 };
+using Params = ParamsT<>;
 
 // The LDS of a block.  NB: 64-column blocks of a column pass.
 template <int NB>
@@ -77,7 +88,8 @@ __device__ __forceinline__ void load_heads(const float* row, int h0, int nh, flo
 }
 
 // The scores of the head group of the entry whose column is `col`: lv = l[i, s, h0 ..].
-__device__ __forceinline__ void group_scores(const Params& p, int s, int col, int h0, int nh, const float (&lv)[4], float (&sc)[4]) {
+template <typename P>
+__device__ __forceinline__ void group_scores(const P& p, int s, int col, int h0, int nh, const float (&lv)[4], float (&sc)[4]) {
     float rv[4];
     load_heads(p.r + (int64_t)col * p.ldr + (int64_t)s * p.K, h0, nh, rv);
 #pragma unroll
@@ -87,8 +99,8 @@ __device__ __forceinline__ void group_scores(const Params& p, int s, int col, in
 // (m, 1/S) of heads h0 .. h0 + nh - 1 of a segment of `len` >= 1 entries whose column ids start at `cols`, on NW waves: NW = 1 the
 // calling wave alone; NW = 4 every thread of the block must call, wave w takes the chunks = w (mod 4) and `red` is free again on
 // return.  All lanes return the same values.
-template <int NW>
-__device__ __forceinline__ void group_stats(const Params& p, int s, const int32_t* cols, int64_t len, int h0, int nh, const float (&lv)[4],
+template <int NW, typename P>
+__device__ __forceinline__ void group_stats(const P& p, int s, const int32_t* cols, int64_t len, int h0, int nh, const float (&lv)[4],
                                             int lane, int wave, float (*red)[kWavesPerBlock][4], float (&m)[4], float (&rinv)[4]) {
     constexpr int NA = 4 / NW;   // partials a lane keeps per head
     const int64_t first = NW == 1 ? 0 : (int64_t)wave * kWave;
@@ -169,7 +181,8 @@ __device__ __forceinline__ void group_stats(const Params& p, int s, const int32_
 }
 
 // A segment of `len` in 1..64 entries, lane = entry (col: its column, clamped): the coefficients of all heads into `tile`.
-__device__ __forceinline__ void single_chunk_tile(const Params& p, int s, const float* lrow, int col, int len, int lane, float* tile) {
+template <typename P>
+__device__ __forceinline__ void single_chunk_tile(const P& p, int s, const float* lrow, int col, int len, int lane, float* tile) {
     const bool ok = lane < len;
     for (int h0 = 0; h0 < p.K; h0 += 4) {
         const int nh = p.K - h0 < 4 ? p.K - h0 : 4;   // (wave-uniform)
@@ -194,7 +207,8 @@ __device__ __forceinline__ void single_chunk_tile(const Params& p, int s, const 
 // entry q: `len` in 0..16 entries from `beg` (0: the group has no such segment).  The reductions stay inside the 16-lane group --
 // the partials 16 .. 255 are +0, and W_0 + 0 adds no bit -- and the coefficients of group gi go to the entries 16 gi .. of `tile`.
 // Returns the column of the lane's entry.
-__device__ __forceinline__ int short_tiles(const Params& p, int s, int64_t row, int64_t beg, int len, int lane, float* tile) {
+template <typename P>
+__device__ __forceinline__ int short_tiles(const P& p, int s, int64_t row, int64_t beg, int len, int lane, float* tile) {
     const bool ok = (lane & (kGroup - 1)) < len;
     int col = 0;
     if (ok) col = p.colidx[s][beg + (lane & (kGroup - 1))];
@@ -225,7 +239,8 @@ __device__ __forceinline__ int short_tiles(const Params& p, int s, int64_t row, 
 
 // The coefficients of `count` (1..64) entries of a longer segment, lane = entry (col: its column, clamped), from the segment's
 // statistics `stat`: e and alpha by the operations that produced S.
-__device__ __forceinline__ void chunk_tile(const Params& p, int s, const float* lrow, int col, int count, int lane, const float* stat,
+template <typename P>
+__device__ __forceinline__ void chunk_tile(const P& p, int s, const float* lrow, int col, int count, int lane, const float* stat,
                                            float* tile) {
     const bool ok = lane < count;
     for (int h0 = 0; h0 < p.K; h0 += 4) {
@@ -247,22 +262,22 @@ __device__ __forceinline__ float fold_groups(float v) { return bfly_groups<Add>(
 
 // One batch of U rounds of a chunk: group gi serves entry 4r + gi in round r.  FULL: every round of the batch exists.  All the
 // gathers of the batch go out before its first FMA; an entry beyond `count` loads (a clamped, valid address) and adds nothing.
-template <int NB, int U, bool FULL>
-__device__ __forceinline__ void batch(const Params& p, const float* tile, const int (&head)[NB], int cbase, int r0, int rounds, int count,
+template <int NB, int U, bool FULL, typename P>
+__device__ __forceinline__ void batch(const P& p, const float* tile, const int (&head)[NB], int cbase, int r0, int rounds, int count,
                                       int ecol, int lane0, int lane, Quad (&acc)[NB]) {
     const int q = lane & 15, gi = lane >> 4;
-    Quad xv[U][NB];
+    typename Gathered<typename P::X>::type xv[U][NB];   // (bf16: packed until the FMA below)
     float vv[U][NB];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         if (FULL || r0 + u < rounds) {
             const int n = 4 * (r0 + u) + gi < count ? 4 * (r0 + u) + gi : count - 1;
             const int c = __builtin_amdgcn_ds_bpermute((lane0 + n) << 2, ecol);
-            const float* xrow = p.x + (int64_t)c * p.ldx;
+            const typename P::X* xrow = p.x + (int64_t)c * p.ldx;
 #pragma unroll
             for (int b = 0; b < NB; ++b) vv[u][b] = tile[n * p.K + head[b]];
 #pragma unroll
-            for (int b = 0; b < NB; ++b) xv[u][b] = load_quad(xrow, cbase + b * kBlockCols + 4 * q, p.d);
+            for (int b = 0; b < NB; ++b) xv[u][b] = load_gathered(xrow, cbase + b * kBlockCols + 4 * q, p.d);
         }
     }
 #pragma unroll
@@ -270,9 +285,11 @@ __device__ __forceinline__ void batch(const Params& p, const float* tile, const 
         if (FULL || r0 + u < rounds) {
             if (4 * (r0 + u) + gi < count) {
 #pragma unroll
-                for (int b = 0; b < NB; ++b)
+                for (int b = 0; b < NB; ++b) {
+                    const Quad& xq = widen(xv[u][b]);
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) acc[b].v[k] = __builtin_fmaf(vv[u][b], xv[u][b].v[k], acc[b].v[k]);
+                    for (int k = 0; k < 4; ++k) acc[b].v[k] = __builtin_fmaf(vv[u][b], xq.v[k], acc[b].v[k]);
+                }
             }
         }
     }
@@ -280,8 +297,8 @@ __device__ __forceinline__ void batch(const Params& p, const float* tile, const 
 
 // `count` (1..64) consecutive entries whose coefficients are in `tile` (entry n at n * K) and whose columns are in `ecol` of the
 // lanes lane0 + n: every entry goes into the partial of its group, in ascending order.  All 64 lanes must be active.
-template <int NB, int U>
-__device__ __forceinline__ void gather_chunk(const Params& p, const float* tile, const int (&head)[NB], int cbase, int count, int ecol,
+template <int NB, int U, typename P>
+__device__ __forceinline__ void gather_chunk(const P& p, const float* tile, const int (&head)[NB], int cbase, int count, int ecol,
                                              int lane0, int lane, Quad (&acc)[NB]) {
     const int rounds = (count + 3) >> 2;
     int r0 = 0;
@@ -290,8 +307,8 @@ __device__ __forceinline__ void gather_chunk(const Params& p, const float* tile,
 }
 
 // The head of every block of the pass for this lane's quad (a quad beyond d: the last head, its sums are never stored).
-template <int NB>
-__device__ __forceinline__ void pass_heads(const Params& p, int cbase, int q, int (&head)[NB]) {
+template <int NB, typename P>
+__device__ __forceinline__ void pass_heads(const P& p, int cbase, int q, int (&head)[NB]) {
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
         const int h = (cbase + b * kBlockCols + 4 * q) / p.head_cols;
@@ -324,8 +341,8 @@ __device__ __forceinline__ Quad fold_blocks(const Quad (&acc)[NB], int gi) {
 }
 
 // The statistics of all heads of a segment of `len` >= 1 entries into `stat` (see group_stats for NW).
-template <int NW>
-__device__ __forceinline__ void segment_stats(const Params& p, int s, const float* lrow, const int32_t* cols, int64_t len, int lane,
+template <int NW, typename P>
+__device__ __forceinline__ void segment_stats(const P& p, int s, const float* lrow, const int32_t* cols, int64_t len, int lane,
                                               int wave, float (*red)[kWavesPerBlock][4], float* stat) {
     for (int h0 = 0; h0 < p.K; h0 += 4) {
         const int nh = p.K - h0 < 4 ? p.K - h0 : 4;   // (wave-uniform)
@@ -343,7 +360,8 @@ __device__ __forceinline__ void segment_stats(const Params& p, int s, const floa
 // ---- the tile writers of the statistics kernels (attention_stats.hip, attention_dropout.hip)
 // A segment of `len` in 1..64 entries, lane = entry (col: its column, clamped): the coefficients of all heads into `tile`.
 // single_chunk_tile that also stores (m, 1/S) of every head to `st` (head h at st[h] and st[K + h]).
-__device__ __forceinline__ void single_chunk_tile_stats(const Params& p, int s, const float* lrow, int col, int len, int lane, float* tile,
+template <typename P>
+__device__ __forceinline__ void single_chunk_tile_stats(const P& p, int s, const float* lrow, int col, int len, int lane, float* tile,
                                                         float* st) {
     const bool ok = lane < len;
     for (int h0 = 0; h0 < p.K; h0 += 4) {
@@ -372,7 +390,8 @@ __device__ __forceinline__ void single_chunk_tile_stats(const Params& p, int s, 
 // the partials 16 .. 255 are +0, and W_0 + 0 adds no bit -- and the coefficients of group gi go to the entries 16 gi .. of `tile`.
 // Returns the column of the lane's entry.
 // short_tiles that also stores (m, 1/S) of the group's segment to `st` (per lane: its group's row; head h at st[h] and st[K + h]).
-__device__ __forceinline__ int short_tiles_stats(const Params& p, int s, int64_t row, int64_t beg, int len, int lane, float* tile, float* st) {
+template <typename P>
+__device__ __forceinline__ int short_tiles_stats(const P& p, int s, int64_t row, int64_t beg, int len, int lane, float* tile, float* st) {
     const bool ok = (lane & (kGroup - 1)) < len;
     int col = 0;
     if (ok) col = p.colidx[s][beg + (lane & (kGroup - 1))];
@@ -404,11 +423,13 @@ __device__ __forceinline__ int short_tiles_stats(const Params& p, int s, int64_t
 }
 
 // The statistics of (row, selected hop s): m of head h at [h], 1/S at [K + h].
-__device__ __forceinline__ float* stat_row(const Params& p, float* stats, int64_t ldstats, int64_t row, int s) {
+template <typename P>
+__device__ __forceinline__ float* stat_row(const P& p, float* stats, int64_t ldstats, int64_t row, int s) {
     return stats + row * ldstats + (int64_t)s * 2 * p.K;
 }
 // `stat` (m at [h], 1/S at [kMaxHeads + h], written by this wave or behind a barrier) to the statistics row `st`.
-__device__ __forceinline__ void store_stats(const Params& p, const float* stat, float* st, int t) {
+template <typename P>
+__device__ __forceinline__ void store_stats(const P& p, const float* stat, float* st, int t) {
     if (t < p.K) st[t] = stat[t], st[p.K + t] = stat[kMaxHeads + t];
 }
 

@@ -275,6 +275,73 @@ __device__ __forceinline__ void store_quad(float* row, int c0, int d, const Quad
     }
 }
 
+// ---- bf16 feature quads (attention_bf16.hip).  A bf16 element is the upper half of an fp32: widening is exact (a shift or a mask),
+// so every operation after it is the fp32 kernel's; an output is rounded ONCE, to nearest even, where it is stored.  d is even and
+// every row starts on a dword (checked on the host), so a quad holds 4, 2 or 0 valid columns.
+struct bf16_t {
+    uint16_t bits;
+};
+typedef uint32_t uint2a __attribute__((ext_vector_type(2), aligned(4)));   // 8-byte accesses need only dword alignment on gfx950
+
+// Four bf16 as they were loaded: they stay packed until the FMA that consumes them.
+struct PackedQuad {
+    uint32_t lo, hi;
+};
+// What a gather of four columns of element type E keeps in registers.
+template <typename E>
+struct Gathered {
+    using type = Quad;
+};
+template <>
+struct Gathered<bf16_t> {
+    using type = PackedQuad;
+};
+
+template <bool TAIL = true>
+__device__ __forceinline__ Quad load_gathered(const float* row, int c0, int d) { return load_quad<TAIL>(row, c0, d); }
+template <bool TAIL = true>
+__device__ __forceinline__ PackedQuad load_gathered(const bf16_t* row, int c0, int d) {
+    PackedQuad r;
+    r.lo = r.hi = 0;
+    if (TAIL ? c0 + 3 < d : c0 < d) {
+        const uint2a t = *reinterpret_cast<const uint2a*>(row + c0);
+        r.lo = t.x; r.hi = t.y;
+    } else if (TAIL && c0 + 1 < d) {
+        r.lo = *reinterpret_cast<const uint32_t*>(row + c0);
+    }
+    return r;
+}
+__device__ __forceinline__ const Quad& widen(const Quad& q) { return q; }
+__device__ __forceinline__ Quad widen(const PackedQuad& w) {
+    Quad r;
+    r.v[0] = __uint_as_float(w.lo << 16); r.v[1] = __uint_as_float(w.lo & 0xffff0000u);
+    r.v[2] = __uint_as_float(w.hi << 16); r.v[3] = __uint_as_float(w.hi & 0xffff0000u);
+    return r;
+}
+template <bool TAIL = true>
+__device__ __forceinline__ Quad load_quad(const bf16_t* row, int c0, int d) { return widen(load_gathered<TAIL>(row, c0, d)); }
+
+// round to nearest even, two at a time: v_cvt_pk_bf16_f32 (torch's .to(torch.bfloat16), ties and overflow to inf included)
+__device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
+    typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
+    const bf16x2 v = {(__bf16)lo, (__bf16)hi};
+    return __builtin_bit_cast(uint32_t, v);
+}
+__device__ __forceinline__ void store_quad(bf16_t* row, int c0, int d, const Quad& r) {
+    if (c0 + 3 < d) {
+        uint2a t;
+        t.x = pack_bf16x2(r.v[0], r.v[1]); t.y = pack_bf16x2(r.v[2], r.v[3]);
+        *reinterpret_cast<uint2a*>(row + c0) = t;
+    } else if (c0 + 1 < d) {
+        *reinterpret_cast<uint32_t*>(row + c0) = pack_bf16x2(r.v[0], r.v[1]);
+    }
+}
+// Columns c, c + 1 (c even, c + 1 < d) of a row: one dword for a bf16 row, so that no 2-byte store has a neighbour to race with.
+__device__ __forceinline__ void store_pair(float* row, int c, float a, float b) { row[c] = a, row[c + 1] = b; }
+__device__ __forceinline__ void store_pair(bf16_t* row, int c, float a, float b) {
+    *reinterpret_cast<uint32_t*>(row + c) = pack_bf16x2(a, b);
+}
+
 // The quad value of the SDDMM's documented order: t = g0*x0, then fma(g1, x1, t), fma(g2, x2, t), fma(g3, x3, t).
 __device__ __forceinline__ float dot_quad(const Quad& g, const Quad& x) {
     float t = g.v[0] * x.v[0];

@@ -1106,6 +1106,140 @@ class HopPlan:
         _capi.check(st)
         return dl, dr, dx
 
+    # ---- the recomputing attention on bf16 embeddings (csrc/attention_bf16.hip): widen exactly, the fp32 kernels' operations in
+    # their order, one rounding to nearest even at the store.  l, r, stats and the K-wide gradients stay float32.
+    BF16_ATTENTION_SYMBOLS = ("h2gcn_attention_hops_heads_bf16", "h2gcn_attention_hops_heads_stats_bf16",
+                              "h2gcn_attention_hops_heads_backward_bf16")
+
+    @classmethod
+    def _bf16_attention_symbol(cls, name: str) -> None:
+        _require(_capi.has(name), f"{_capi.library_path()} predates the bf16 attention launches ({name}): rebuild it "
+                 "(bfloat16 embeddings are never run in float32 instead)")
+
+    def _attention_operands_bf16(self, what: str, x, l, r, hops):
+        """``x`` (bfloat16), ``l``, ``r`` (float32) of the bf16 attention launches -> what :meth:`_attention_operands` returns."""
+        _require(isinstance(x, torch.Tensor) and x.dim() == 2, f"inputs must be [n_cols, d], got shape {tuple(getattr(x, 'shape', ()))}")
+        _require(x.dtype == torch.bfloat16, f"inputs must be bfloat16 (the {what} takes bf16 embeddings), got {x.dtype}")
+        _require(x.device == self.device, f"inputs on {x.device}, plan on {self.device}")
+        _require(x.shape[0] == self.n_cols, f"inputs have {x.shape[0]} rows, hop matrices have {self.n_cols} columns")
+        _require(x.shape[1] >= 1, "inputs need at least one column")
+        d = int(x.shape[1])
+        mask, h_sel = self._mask(hops), len(self._selected(hops))
+        l, ldl, n_heads = self._node_heads_operand("l", l, self.n_rows, h_sel)
+        r, ldr, _ = self._node_heads_operand("r", r, self.n_cols, h_sel, n_heads)
+        _require(n_heads <= self.ATTENTION_FUSED_MAX_HEADS,
+                 f"the {what} serves at most K = {self.ATTENTION_FUSED_MAX_HEADS} heads, got K = {n_heads} (the chain is float32 only)")
+        self._head_width(d, n_heads)
+        if x.stride(1) != 1 or (self.n_cols > 1 and x.stride(0) < d):
+            x = x.contiguous()
+        _bf16_layout("inputs", x, d, (x.stride(0),) if self.n_cols > 1 else ())
+        return x, l, ldl, r, ldr, n_heads, d, mask, h_sel
+
+    def _dense_output_bf16(self, out, out_dtype, h_sel: int, d: int, inputs):
+        """The result dtype (``out.dtype``, else ``out_dtype``, else bfloat16) and the caller's ``out``, checked."""
+        if out_dtype is None:
+            out_dtype = out.dtype if out is not None else torch.bfloat16
+        _require(out_dtype in (torch.float32, torch.bfloat16), f"outputs must be float32 or bfloat16, got {out_dtype}")
+        if out is not None:
+            _require(isinstance(out, torch.Tensor) and out.dtype == out_dtype and out.device == self.device,
+                     f"out must be {out_dtype} on the plan's device")
+            _require(tuple(out.shape) == (self.n_rows, h_sel, d), f"out has shape {tuple(out.shape)}, expected {(self.n_rows, h_sel, d)}")
+            _require(d == 1 or out.stride(2) == 1, "out's last dimension must be contiguous")
+            _require((self.n_rows <= 1 or out.stride(0) >= d) and (h_sel == 1 or out.stride(1) >= d), "out's rows / hop slots overlap")
+            if out_dtype == torch.bfloat16:
+                _bf16_layout("out", out, d, [out.stride(i) for i, n in ((0, self.n_rows), (1, h_sel)) if n > 1])
+            for name, t in inputs:
+                _require(not self._overlap(out, t), f"out overlaps {name}: the launch gathers rows of x and r while it stores rows of out")
+        return out_dtype
+
+    def attention_heads_bf16(self, x: torch.Tensor, l: torch.Tensor, r: torch.Tensor, negative_slope: float = 0.2, hops=None,
+                             out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None) -> torch.Tensor:
+        """:meth:`attention_heads` on bfloat16 ``x`` (``h2gcn_attention_hops_heads_bf16``): every element of ``x`` is widened
+        exactly, the fp32 launch's operations run in fp32 in its order, and the result is rounded once, to nearest even, where it is
+        stored.  A float32 result has the bits of ``attention_heads(x.float(), l, r)``, a bfloat16 result is that
+        ``.to(torch.bfloat16)``.  ``l``, ``r``: float32.  The result's dtype is ``out.dtype``, else ``out_dtype``, else bfloat16 (as
+        in :meth:`spmm`).  ``d`` even; the other limits are :meth:`attention_heads`'s."""
+        return self._attention_heads_bf16(False, x, l, r, negative_slope, hops, out, out_dtype)[0]
+
+    def attention_heads_stats_bf16(self, x: torch.Tensor, l: torch.Tensor, r: torch.Tensor, negative_slope: float = 0.2, hops=None,
+                                   out: Optional[torch.Tensor] = None, out_dtype: Optional[torch.dtype] = None) -> tuple:
+        """:meth:`attention_heads_stats` on bfloat16 ``x`` -> ``(y, stats)`` (``h2gcn_attention_hops_heads_stats_bf16``): ``y`` as
+        :meth:`attention_heads_bf16` gives it, ``stats`` float32 with the bits of ``attention_heads_stats(x.float(), l, r)``."""
+        return self._attention_heads_bf16(True, x, l, r, negative_slope, hops, out, out_dtype)
+
+    def _attention_heads_bf16(self, with_stats, x, l, r, negative_slope, hops, out, out_dtype) -> tuple:
+        x, l, ldl, r, ldr, n_heads, d, mask, h_sel = self._attention_operands_bf16("bf16 fused attention forward", x, l, r, hops)
+        out_dtype = self._dense_output_bf16(out, out_dtype, h_sel, d, (("the inputs", x), ("l", l), ("r", r)))
+        self._bf16_attention_symbol(self.BF16_ATTENTION_SYMBOLS[1 if with_stats else 0])
+        if out is None:
+            out = torch.empty((self.n_rows, h_sel, d), dtype=out_dtype, device=self.device)
+        stats = torch.empty((self.n_rows, h_sel, 2, n_heads), dtype=torch.float32, device=self.device) if with_stats else None
+        if self.n_rows == 0:
+            return out, stats
+        y_dtype = _capi.DTYPE_BF16 if out_dtype == torch.bfloat16 else _capi.DTYPE_F32
+        args = (self._handle, mask, C.c_void_p(l.data_ptr()), ldl, C.c_void_p(r.data_ptr()), ldr, n_heads, float(negative_slope),
+                C.c_void_p(x.data_ptr()), x.stride(0) if self.n_cols > 1 else d, d, y_dtype, C.c_void_p(out.data_ptr()),
+                out.stride(0) if self.n_rows > 1 else h_sel * d, out.stride(1) if h_sel > 1 else d)
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            if with_stats:
+                st = _capi.lib().h2gcn_attention_hops_heads_stats_bf16(*args, C.c_void_p(stats.data_ptr()), h_sel * 2 * n_heads,
+                                                                       C.c_void_p(stream))
+            else:
+                st = _capi.lib().h2gcn_attention_hops_heads_bf16(*args, C.c_void_p(stream))
+        _capi.check(st)
+        return out, stats
+
+    def attention_heads_backward_bf16(self, x: torch.Tensor, l: torch.Tensor, r: torch.Tensor, stats: torch.Tensor, y: torch.Tensor,
+                                      grad: torch.Tensor, negative_slope: float = 0.2, hops=None, need_dl: bool = True,
+                                      need_dr: bool = True, need_dx: bool = True, dx_dtype: Optional[torch.dtype] = None) -> tuple:
+        """:meth:`attention_heads_backward` on bfloat16 ``x``, ``y`` and ``grad`` -> ``(dl, dr, dx)``
+        (``h2gcn_attention_hops_heads_backward_bf16``).  ``y`` is the bfloat16 result of :meth:`attention_heads_stats_bf16`: ``delta =
+        <grad, y>`` is taken on it.  ``dl``, ``dr`` (float32) and a float32 ``dx`` have the bits of ``attention_heads_backward(x.float(),
+        l, r, stats, y.float(), grad.float())``; a bfloat16 ``dx`` (``dx_dtype``, the default) is that rounded once, after the sum
+        over the hops.  ``d`` even and ``<= 256``."""
+        x, l, ldl, r, ldr, n_heads, d, mask, h_sel = self._attention_operands_bf16("bf16 recomputing attention backward", x, l, r, hops)
+        _require(need_dl or need_dr or need_dx, "need_dl, need_dr and need_dx are all False: nothing to compute")
+        _require(d <= self.ATTENTION_RECOMPUTE_MAX_WIDTH,
+                 f"the bf16 recomputing attention backward serves at most d = {self.ATTENTION_RECOMPUTE_MAX_WIDTH} columns, got d = {d} "
+                 "(the chain is float32 only)")
+        if dx_dtype is None:
+            dx_dtype = torch.bfloat16
+        _require(dx_dtype in (torch.float32, torch.bfloat16), f"dx must be float32 or bfloat16, got {dx_dtype}")
+        for name, t, shape, dtype in (("stats", stats, (self.n_rows, h_sel, 2, n_heads), torch.float32),
+                                      ("y", y, (self.n_rows, h_sel, d), torch.bfloat16), ("grad", grad, (self.n_rows, h_sel, d), torch.bfloat16)):
+            _require(isinstance(t, torch.Tensor) and tuple(t.shape) == shape, f"{name} must be {list(shape)}, got {tuple(getattr(t, 'shape', ()))}")
+            _require(t.dtype == dtype, f"{name} must be {str(dtype).replace('torch.', '')} (the bf16 recomputing attention backward), got {t.dtype}")
+            _require(t.device == self.device, f"{name} on {t.device}, plan on {self.device}")
+        stats = stats.contiguous()
+
+        def wide(t):   # the layout rule of a bf16 [n_rows, H_sel, d] array; anything else is copied
+            bad = (t.stride(2) != 1 or (self.n_rows > 1 and (t.stride(0) < d or t.stride(0) % 2))
+                   or (h_sel > 1 and (t.stride(1) < d or t.stride(1) % 2)) or t.data_ptr() % 4)
+            return t.contiguous() if bad else t
+        y, grad = wide(y), wide(grad)
+        _require(not (need_dr or need_dx) or self.has_transpose,
+                 "the gradients wrt r and the inputs sum over the COLUMNS of the hop matrices: they walk the plan's transposed operands "
+                 "(no permutation is needed).  Build the plan with HopPlan(..., build_transpose=True)")
+        self._bf16_attention_symbol(self.BF16_ATTENTION_SYMBOLS[2])
+        dl = torch.empty((self.n_rows, h_sel, n_heads), dtype=torch.float32, device=self.device) if need_dl else None
+        dr = torch.empty((self.n_cols, h_sel, n_heads), dtype=torch.float32, device=self.device) if need_dr else None
+        dx = torch.empty((self.n_cols, d), dtype=dx_dtype, device=self.device) if need_dx else None
+        if all(t is None or t.numel() == 0 for t in (dl, dr, dx)):   # (no node on the requested sides: nothing to write)
+            return dl, dr, dx
+        delta = torch.empty((self.n_rows, h_sel, n_heads), dtype=torch.float32, device=self.device) if need_dr or need_dx else None
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # noqa: E731
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            st = _capi.lib().h2gcn_attention_hops_heads_backward_bf16(
+                self._handle, mask, ptr(l), ldl, ptr(r), ldr, n_heads, float(negative_slope), ptr(x), x.stride(0) if self.n_cols > 1 else d, d,
+                ptr(stats), h_sel * 2 * n_heads, ptr(y), y.stride(0) if self.n_rows > 1 else h_sel * d, y.stride(1) if h_sel > 1 else d,
+                ptr(grad), grad.stride(0) if self.n_rows > 1 else h_sel * d, grad.stride(1) if h_sel > 1 else d,
+                ptr(delta), h_sel * n_heads, ptr(dl), h_sel * n_heads, ptr(dr), h_sel * n_heads,
+                _capi.DTYPE_BF16 if dx_dtype == torch.bfloat16 else _capi.DTYPE_F32, ptr(dx), d, C.c_void_p(stream))
+        _capi.check(st)
+        return dl, dr, dx
+
     def __del__(self):
         h = getattr(self, "_handle", None)
         if h is not None and h.value:

@@ -405,6 +405,12 @@ def hop_attention_heads(adjhops: HopPlan, inputs: torch.Tensor, l: torch.Tensor,
     sel = None if hops is None else tuple(sorted(set(int(h) for h in hops)))
     wants_grad = torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (inputs, l, r))
     n_heads = int(l.shape[2]) if isinstance(l, torch.Tensor) and l.dim() == 3 else 1
+    if isinstance(inputs, torch.Tensor) and inputs.dtype == torch.bfloat16:   # (bf16 embeddings: one launch, or a refusal)
+        if wants_grad:
+            raise ValueError("hop_attention_heads with bfloat16 inputs that need a gradient: the chain is float32 only -- call "
+                             "hop_attention_recompute, whose training step has bf16 launches")
+        _bf16_attention_limits("hop_attention_heads", inputs, n_heads, False)
+        return adjhops.attention_heads_bf16(inputs, l, r, negative_slope, hops=sel)
     if wants_grad or n_heads > HopPlan.ATTENTION_FUSED_MAX_HEADS or not _capi.has("h2gcn_attention_hops_heads_f32"):
         scores = hop_edge_scores_heads(adjhops, l, r, negative_slope, sel)
         return hop_spmm_values(adjhops, inputs, hop_softmax_heads(adjhops, scores, sel), sel)
@@ -445,6 +451,48 @@ class _HopAttentionRecompute(torch.autograd.Function):
         return None, None, None, dx, dl, dr, None, None, None
 
 
+def _bf16_attention_limits(what: str, inputs: torch.Tensor, n_heads: int, wants_grad: bool) -> None:
+    """What the bf16 attention launches do not cover is refused, never run in float32 instead (the model's rule for
+    ``--embedding_dtype``): each a ``ValueError`` naming the limit."""
+    d = int(inputs.shape[1]) if inputs.dim() == 2 else 1
+    if n_heads > HopPlan.ATTENTION_FUSED_MAX_HEADS:
+        raise ValueError(f"{what} with bfloat16 inputs serves at most K = {HopPlan.ATTENTION_FUSED_MAX_HEADS} heads, got K = {n_heads}: the "
+                         "chain that serves more is float32 only")
+    if wants_grad and d > HopPlan.ATTENTION_RECOMPUTE_MAX_WIDTH:
+        raise ValueError(f"{what} with bfloat16 inputs that need a gradient serves at most d = {HopPlan.ATTENTION_RECOMPUTE_MAX_WIDTH} columns, "
+                         f"got d = {d}: the chain that serves more is float32 only")
+    if d % 2:
+        raise ValueError(f"{what} with bfloat16 inputs needs an even width (a lane stores bf16 pairs), got d = {d}")
+    missing = [s for s in HopPlan.BF16_ATTENTION_SYMBOLS if not _capi.has(s)]
+    if missing:
+        raise ValueError(f"{what} with bfloat16 inputs: {_capi.library_path()} predates the bf16 attention launches ({', '.join(missing)}): "
+                         "rebuild it")
+
+
+class _HopAttentionRecomputeBf16(torch.autograd.Function):
+    """:class:`_HopAttentionRecompute` on bfloat16 embeddings: the forward stores a bfloat16 ``y`` and the float32 statistics
+    (``HopPlan.attention_heads_stats_bf16``), the backward takes a bfloat16 ``grad`` and returns a bfloat16 ``dx`` and float32
+    ``dl``, ``dr`` (``HopPlan.attention_heads_backward_bf16``).  What is kept for the backward -- ``x`` and ``y`` -- is 2-byte."""
+
+    @staticmethod
+    def forward(ctx, plan: HopPlan, hops, negative_slope: float, inputs: torch.Tensor, l: torch.Tensor, r: torch.Tensor):
+        y, stats = plan.attention_heads_stats_bf16(inputs, l, r, negative_slope, hops=hops)
+        ctx.plan, ctx.hops, ctx.negative_slope = plan, hops, negative_slope
+        ctx.save_for_backward(inputs, l, r, stats, y)
+        return y
+
+    @staticmethod
+    def backward(ctx, grad):
+        need_dx, need_dl, need_dr = ctx.needs_input_grad[3:6]
+        if not (need_dx or need_dl or need_dr):
+            return None, None, None, None, None, None
+        inputs, l, r, stats, y = ctx.saved_tensors
+        # (a grad of another layout is copied to the bf16 layout rule by the plan method)
+        dl, dr, dx = ctx.plan.attention_heads_backward_bf16(inputs, l, r, stats, y, grad.to(torch.bfloat16), ctx.negative_slope, hops=ctx.hops,
+                                                            need_dl=need_dl, need_dr=need_dr, need_dx=need_dx, dx_dtype=torch.bfloat16)
+        return None, None, None, dx, dl, dr
+
+
 def _dropped_chain(adjhops: HopPlan, inputs: torch.Tensor, l: torch.Tensor, r: torch.Tensor, negative_slope: float, sel, keep_prob: float,
                    seed: int, step) -> torch.Tensor:
     """The chain of :func:`hop_attention_heads` with dropout on its coefficients: ``alpha_k * f_k``, ``f_k`` the factor arrays of
@@ -473,6 +521,12 @@ def hop_attention_recompute(adjhops: HopPlan, inputs: torch.Tensor, l: torch.Ten
     permutation: ``keep_permutation`` is not needed; a ``symmetric_pattern=True`` plan serves too).  ``K > 16``, ``d > 256`` and a
     library that predates the two launches take :func:`hop_attention_heads`, the chain.  fp32 only.  Row-partitioned operands
     (``ShardedHops``) are not covered.
+
+    bfloat16 ``inputs`` (``l`` and ``r`` stay float32) run the bf16 launches (:meth:`HopPlan.attention_heads_stats_bf16`,
+    :meth:`HopPlan.attention_heads_backward_bf16`; without a gradient :meth:`HopPlan.attention_heads_bf16`): the result and the
+    gradient of ``inputs`` are bfloat16, the float32 launches' values on the upcast operands rounded once to nearest even.  What those
+    launches do not cover -- ``K > 16``, ``d > 256`` under a gradient, an odd ``d``, a library without them -- is a ``ValueError``:
+    bf16 embeddings are never run in float32 instead (the chain is float32 only).
 
     :func:`hop_attention_recompute_dropout` is this step with dropout on the attention coefficients."""
     return _hop_attention_recompute(adjhops, inputs, l, r, negative_slope, hops, 0.0, 0, None)
@@ -507,6 +561,18 @@ def _hop_attention_recompute(adjhops, inputs, l, r, negative_slope, hops, dropou
     grads = [torch.is_grad_enabled() and isinstance(t, torch.Tensor) and t.requires_grad for t in (inputs, l, r)]
     n_heads = int(l.shape[2]) if isinstance(l, torch.Tensor) and l.dim() == 3 else 1
     d = int(inputs.shape[1]) if isinstance(inputs, torch.Tensor) and inputs.dim() == 2 else 1
+    if isinstance(inputs, torch.Tensor) and inputs.dtype == torch.bfloat16:   # (bf16 embeddings: the bf16 launches, or a refusal)
+        if dropout > 0.0:
+            raise ValueError(f"hop_attention_recompute_dropout(dropout={dropout}) with bfloat16 inputs: the attention dropout launches are "
+                             "float32 only")
+        _bf16_attention_limits("hop_attention_recompute", inputs, n_heads, any(grads))
+        if not any(grads):
+            return adjhops.attention_heads_bf16(inputs, l, r, negative_slope, hops=sel)
+        if (grads[0] or grads[2]) and not adjhops.has_transpose:
+            raise ValueError("hop_attention_recompute with inputs or an r that require a gradient: those gradients sum over the columns of the "
+                             "hop matrices, on the plan's transposed operands (their permutation is not needed).  Build the plan with "
+                             "HopPlan(..., build_transpose=True)")
+        return _HopAttentionRecomputeBf16.apply(adjhops, sel, float(negative_slope), inputs, l, r)
     if (n_heads > HopPlan.ATTENTION_FUSED_MAX_HEADS or d > HopPlan.ATTENTION_RECOMPUTE_MAX_WIDTH
             or not all(_capi.has(s) for s in HopPlan._RECOMPUTE_SYMBOLS)):
         if dropout > 0.0:
@@ -722,7 +788,12 @@ class RecomputeMultiHeadHopAttention(MultiHeadHopAttention):
     the parameter gradients agree with the parent's to rounding (their summation orders differ) and are as deterministic.  Peak
     memory no longer grows with ``nnz * K``.  Training needs a square plan built with ``build_transpose=True`` (``keep_permutation``
     is not needed); such layers can be stacked on one plan, share it with a ``GCNLayer``, and their training step can be captured
-    in a hipGraph after one eager warm-up.  ``heads > 16`` or ``in_dim > 256`` run the parent's chain."""
+    in a hipGraph after one eager warm-up.  ``heads > 16`` or ``in_dim > 256`` run the parent's chain.
+
+    A bfloat16 ``inputs`` (an attention layer behind a bf16 propagation) runs the bf16 launches of :func:`hop_attention_recompute`:
+    the per-head projections are computed in float32 from the upcast head slice (one ``[N, in_dim / heads]`` transient at a time),
+    the output and ``inputs.grad`` are bfloat16, the parameters and their gradients float32.  What bf16 does not cover (more than 16
+    heads, ``in_dim > 256`` under a gradient, attention dropout active in ``train()``) is a ``ValueError``."""
 
     def forward(self, adjhops: HopPlan, inputs: torch.Tensor) -> torch.Tensor:
         if hasattr(adjhops, "aggregate"):
@@ -740,6 +811,18 @@ class RecomputeMultiHeadHopAttention(MultiHeadHopAttention):
         if inputs.dim() != 2 or inputs.shape[1] != self.in_dim:
             raise ValueError(f"inputs must be [{adjhops.n_cols}, {self.in_dim}], got {tuple(inputs.shape)}")
         n_heads, w = self.heads, self.in_dim // self.heads
+        if inputs.dtype == torch.bfloat16:
+            # bf16 embeddings: the projections in fp32 from the upcast head slice (one [N, w] transient at a time), then the bf16
+            # launches.  What they do not cover is refused by hop_attention_recompute, never run in float32 instead.
+            if self.training and self.attn_dropout > 0.0:
+                raise ValueError(f"RecomputeMultiHeadHopAttention(attn_dropout={self.attn_dropout}) in train() with bfloat16 inputs: the "
+                                 "attention dropout launches are float32 only (eval(), or float32 inputs)")
+            ls, rs = [], []
+            for h in range(n_heads):
+                x_h = (inputs if n_heads == 1 else inputs[:, h * w:(h + 1) * w]).float()
+                ls.append(x_h @ self.a_l[:, h, :].t())
+                rs.append(x_h @ self.a_r[:, h, :].t())
+            return hop_attention_recompute(adjhops, inputs, _StackHeads.apply(*ls), _StackHeads.apply(*rs), self.negative_slope, self.hops)
         if (n_heads > HopPlan.ATTENTION_FUSED_MAX_HEADS or self.in_dim > HopPlan.ATTENTION_RECOMPUTE_MAX_WIDTH
                 or not all(_capi.has(s) for s in HopPlan._RECOMPUTE_SYMBOLS)):
             return super().forward(adjhops, inputs)   # (the chain, on alpha * f under dropout: the same mask)

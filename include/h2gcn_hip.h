@@ -824,6 +824,42 @@ int h2gcn_attention_hops_heads_backward_dropout_f32(const h2gcn_plan_t* plan, ui
 int h2gcn_attention_dropout_factors_hops_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, int32_t n_heads, float keep_prob, uint64_t seed,
                                              const int64_t* step_dev, float* const* f_dev, const int64_t* ldf_entry, void* stream);
 
+/* BF16 EMBEDDINGS IN THE RECOMPUTING ATTENTION (h2gcn_amd/csrc/attention_bf16.hip; added within ABI 5: find the entry points by
+ * symbol).  The three launches above -- forward, forward + statistics, recomputing backward -- on bf16 wide operands, under the
+ * contract of h2gcn_spmm_hops_bf16: every gathered bf16 element is WIDENED EXACTLY, EVERY OPERATION OF THE FP32 KERNEL RUNS IN FP32
+ * IN THE DOCUMENTED ORDER, AND AN OUTPUT IS ROUNDED ONCE, TO NEAREST EVEN, AT THE FINAL STORE.  Consequently an fp32 output of a bf16
+ * launch is bit-identical to the fp32 launch on the upcast operands, and a bf16 output is that value rounded to nearest even (ties
+ * and overflow to infinity as torch's .to(torch.bfloat16)).  l, r, stats, delta, dl and dr stay fp32: they are K wide, not d wide.
+ *
+ * THE SUMMATION ORDERS are those of the fp32 launches, word for word: the softmax tree, the aggregation tree of Y, the SDDMM order of
+ * dalpha and delta, the row-softmax tree of dl / dr and the per-hop aggregation tree of dX; dX is rounded once, after the sum over
+ * the hops.  The bits do not depend on long_row_threshold, rows_per_wave, the hop selection or the kernel geometry.
+ *
+ * Argument orders follow the fp32 calls; X_dev (and in the backward Y_dev and G_dev) are bf16 (uint16_t storage); y_dtype / dx_dtype
+ * are H2GCN_DTYPE_F32 or H2GCN_DTYPE_BF16 and give the element type behind Y_dev / dX_dev (any other value:
+ * H2GCN_ERR_INVALID_ARGUMENT); every leading dimension is in ELEMENTS of its array.  In the backward X, Y and G are all bf16:
+ * delta = <G, Y> is taken on the bf16 Y that the forward stored.  Limits are those of the fp32 calls: K <= 16; K > 1 needs d % K == 0
+ * and (d / K) % 4 == 0; the backward needs d <= 256; the forward takes any even d.
+ *
+ * Validation: that of the fp32 calls, in their order and with their messages, all before the device is touched; plus the dtype
+ * code (after the plan and the hop mask) and, after the stride checks, the layout rule of every bf16 array -- a 4-byte aligned base,
+ * even row / hop strides and an even d ("bf16 X: ...", the messages of h2gcn_spmm_hops_bf16).  A selection without nonzeros is a
+ * memset of the outputs in the element size of each.  hipGraph capture: the rule of the fp32 launches.
+ */
+int h2gcn_attention_hops_heads_bf16(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* l_dev, int64_t ldl, const float* r_dev,
+                                    int64_t ldr, int32_t n_heads, float negative_slope, const uint16_t* X_dev, int64_t ldx, int32_t d,
+                                    int y_dtype, void* Y_dev, int64_t ldy_row, int64_t ldy_hop, void* stream);
+int h2gcn_attention_hops_heads_stats_bf16(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* l_dev, int64_t ldl, const float* r_dev,
+                                          int64_t ldr, int32_t n_heads, float negative_slope, const uint16_t* X_dev, int64_t ldx, int32_t d,
+                                          int y_dtype, void* Y_dev, int64_t ldy_row, int64_t ldy_hop, float* stats_dev, int64_t ldstats,
+                                          void* stream);
+int h2gcn_attention_hops_heads_backward_bf16(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* l_dev, int64_t ldl, const float* r_dev,
+                                             int64_t ldr, int32_t n_heads, float negative_slope, const uint16_t* X_dev, int64_t ldx, int32_t d,
+                                             const float* stats_dev, int64_t ldstats, const uint16_t* Y_dev, int64_t ldy_row, int64_t ldy_hop,
+                                             const uint16_t* G_dev, int64_t ldg_row, int64_t ldg_hop, float* delta_dev, int64_t lddelta,
+                                             float* dl_dev, int64_t lddl, float* dr_dev, int64_t lddr, int dx_dtype, void* dX_dev, int64_t lddx,
+                                             void* stream);
+
 /* ------------------------------------------------------------------------------------------------------------
  * Operand construction on the device: exact-k-hop neighbourhood rings and their normalisation -- the step that
  * FEEDS the aggregation.  Stands in for TransformSPAdj.nhoodSplit (reference h2gcn/datasets/_dataset.py:138-158:
