@@ -7,8 +7,8 @@
 //   * h2gcn_attention_dropout_factors_hops_f32: the factors themselves, f_k [nnz_k, K] entry-major, for the chain and the tests.
 //
 // The factor is a function of (seed, step, hop, row, column, head) alone (attention_dropout.hip.h): no mask is stored, and the backward
-// (attention_dropout_backward.hip) draws the same one again.  A translation unit of its own, and a COPY of the statistics kernel's walk
-// over the device functions of attention_fused.hip.h: no existing kernel is compiled differently because of it.
+// (attention_dropout_backward.hip) draws the same one again.  The forward kernel keeps a copy of the walk of attention_fused.hip.h, for
+// the measured reason at the kernel.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -33,14 +33,19 @@ __device__ __forceinline__ void drop_tile(const Params& p, const Mask& mk, uint6
     }
 }
 
-// attention_fused_stats_kernel whose tiles hold alpha * f.  Three waves per SIMD are asked for: NB = 1 then keeps the statistics
+// attention_fused_stats_kernel whose tiles hold alpha * f: the walk of forward_walk<float, NB, true> (attention_fused.hip.h) with a
+// drop_tile call after each of the four places a tile is written.  It is this kernel's OWN COPY of the walk, the one kept copy of the
+// refactor that left one walk: built as a wrapper around forward_walk with a tile hook, the kernel kept its registers and occupancy
+// (NB = 2: 134 VGPRs against 136, three waves per SIMD either way) but ran the products shape (d = 128, K = 8, keep 0.5) in 44.3 ms
+// against 33.4 -- 33.5 ms, and arxiv in 0.66 -- 0.67 ms against 0.59 (profiles/r25_attention_one_walk_parent_vs_this.txt); the occupancy
+// attribute was already there.  A fix to forward_walk has to be made here too.  Three waves per SIMD are asked for: NB = 1 then keeps the statistics
 // kernel's occupancy (left alone it takes 173 VGPRs and drops to two); NB = 2 and 4 do not reach the statistics kernel's four without
 // VGPR spills (it sits at exactly 128 VGPRs) and run at three.
 template <int NB>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) void attention_fused_stats_dropout_kernel(
     const Params p, float* stats, int64_t ldstats, const Args da) {
     __shared__ Shared<NB> sh;
-    constexpr int U = kLoads / NB;
+    constexpr int U = Loads<float>::value / NB;
     constexpr int kPassCols = NB * kBlockCols;
     const int lane = threadIdx.x & (kWave - 1);
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -104,7 +109,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) voi
             int ecol = 0;
             wave_lds_sync();   // the previous segments' reads of the tile come first
             if (__ballot(is_short) != 0ull) {
-                ecol = short_tiles_stats(p, s, row0 + i0 + gi, gbeg, is_short ? (int)glen : 0, lane, tile,
+                ecol = short_tiles<true>(p, s, row0 + i0 + gi, gbeg, is_short ? (int)glen : 0, lane, tile,
                                          stat_row(p, stats, ldstats, row0 + i0 + gi, s));
                 drop_tile(p, mk, entry_base(mk, row0 + i0 + gi, ecol, da.hop[s]), is_short && q < glen, lane, tile);
             }
@@ -136,7 +141,7 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) voi
                 wave_lds_sync();   // the previous segment's reads of the tile and of the statistics come first
                 if (single) {
                     ecol = cols[lane < len ? lane : len - 1];
-                    single_chunk_tile_stats(p, s, lrow, ecol, (int)len, lane, tile, stat_row(p, stats, ldstats, row0 + i0 + k, s));
+                    single_chunk_tile<true>(p, s, lrow, ecol, (int)len, lane, tile, stat_row(p, stats, ldstats, row0 + i0 + k, s));
                     drop_tile(p, mk, entry_base(mk, row0 + i0 + k, ecol, da.hop[s]), lane < len, lane, tile);
                 } else {
                     segment_stats<1>(p, s, lrow, cols, len, lane, 0, nullptr, stat);
@@ -167,16 +172,17 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(3))) voi
     }
 }
 
-static void launch_stats_dropout(const Params& p, float* stats, int64_t ldstats, const PatternView& v, const void* ctx_v, dim3 grid,
-                                 hipStream_t stream) {
-    const Context& c = *static_cast<const Context*>(ctx_v);
-    const Args da = make_args(c.plan, v.mask, v.n_cols, c.keep_prob, c.seed, c.step_dev);
-    const dim3 block(kBlock);
-    // (the geometries of the plain forward)
-    if (p.d <= kBlockCols) hipLaunchKernelGGL((attention_fused_stats_dropout_kernel<1>), grid, block, 0, stream, p, stats, ldstats, da);
-    else if (p.d <= 2 * kBlockCols) hipLaunchKernelGGL((attention_fused_stats_dropout_kernel<2>), grid, block, 0, stream, p, stats, ldstats, da);
-    else hipLaunchKernelGGL((attention_fused_stats_dropout_kernel<kMaxBlocks>), grid, block, 0, stream, p, stats, ldstats, da);
+}  // namespace attention_dropout
+
+void attention_fused::launch_stats_dropout(const Params& p, float* stats, int64_t ldstats, const attention_dropout::Args& da, dim3 grid,
+                                           hipStream_t stream) {
+    for_blocks(p.d, [&](auto nb) {
+        hipLaunchKernelGGL((attention_dropout::attention_fused_stats_dropout_kernel<decltype(nb)::value>), grid, dim3(kBlock), 0, stream, p,
+                           stats, ldstats, da);
+    });
 }
+
+namespace attention_dropout {
 
 // ---------------------------------------------------------------------------------------------------------------- the factors
 struct FactorParams {
@@ -267,9 +273,9 @@ int h2gcn_attention_hops_heads_stats_dropout_f32(const h2gcn_plan_t* plan, uint3
     if (keep_prob == 1.f)   // nothing is dropped and 1/keep = 1: the launch without dropout, its bits
         return h2gcn_attention_hops_heads_stats_f32(plan, hop_mask, l_dev, ldl, r_dev, ldr, n_heads, negative_slope, X_dev, ldx, d, Y_dev,
                                                     ldy_row, ldy_hop, stats_dev, ldstats, stream);
-    const Context ctx = {plan, keep_prob, seed, step_dev};
-    return h2gcn::attention_fused::run(nullptr, stats_dev, ldstats, plan, hop_mask, l_dev, ldl, r_dev, ldr, n_heads, negative_slope, X_dev,
-                                       ldx, d, Y_dev, ldy_row, ldy_hop, stream, launch_stats_dropout, &ctx);
+    const h2gcn::attention_dropout::Draw dropout = {keep_prob, seed, step_dev};
+    return h2gcn::attention_fused::run({plan, hop_mask, l_dev, ldl, r_dev, ldr, n_heads, negative_slope, H2GCN_DTYPE_F32, X_dev, ldx, d,
+                                        H2GCN_DTYPE_F32, Y_dev, ldy_row, ldy_hop, true, stats_dev, ldstats, &dropout, stream});
 }
 
 int h2gcn_attention_dropout_factors_hops_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, int32_t n_heads, float keep_prob, uint64_t seed,

@@ -89,9 +89,8 @@ inline int check_keep_prob(float keep_prob) {
     if (!(keep_prob > 0.f) || keep_prob > 1.f) return fail(H2GCN_ERR_INVALID_ARGUMENT, "keep_prob = %g outside (0, 1]", (double)keep_prob);
     return H2GCN_OK;
 }
-// What an entry point hands its launcher through the launch path it shares with the entry point without dropout.
-struct Context {
-    const h2gcn_plan* plan;
+// The mask's arguments as the caller gave them: what a dropout entry point hands the launch path it shares with the entry points without.
+struct Draw {
     float keep_prob;
     uint64_t seed;
     const int64_t* step_dev;

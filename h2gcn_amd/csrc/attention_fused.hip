@@ -5,7 +5,9 @@
 //
 // what h2gcn_edge_scores_hops_heads_f32 -> h2gcn_row_softmax_hops_heads_f32 -> h2gcn_spmm_hops_values_f32 compute through two
 // entry-major [nnz_k, K] arrays, BIT FOR BIT, without those arrays: nothing of size nnz is written or allocated, the only store
-// is Y.  A translation unit of its own: no existing kernel is compiled differently because of it.
+// is Y.  The walk itself is `forward_walk` in attention_fused.hip.h, one text for this unit's kernel and for the kernels that also
+// store the softmax statistics (attention_stats.hip) or read a bf16 X (attention_bf16.hip); attention_dropout.hip keeps a copy;
+// this unit has the plain fp32 kernel and the host launch path of all five forward entry points.
 //
 // Why the bits are the chain's.  Every value the chain stores is a function of operands this kernel also has, so it is computed
 // again with the chain's own operations wherever it is needed (include/h2gcn_hip.h has the three orders):
@@ -39,6 +41,7 @@
 
 #include <cstring>
 
+#include "attention_dropout.hip.h"
 #include "attention_fused.hip.h"
 
 namespace h2gcn {
@@ -46,142 +49,69 @@ namespace attention_fused {
 
 template <int NB>
 __global__ __launch_bounds__(kBlock) void attention_fused_kernel(const Params p) {
-    constexpr int U = kLoads / NB;
-    constexpr int kPassCols = NB * kBlockCols;
     __shared__ Shared<NB> sh;
-    const int lane = threadIdx.x & (kWave - 1);
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const int q = lane & 15, gi = lane >> 4;
-    float* tile = sh.tile[wave];
-    int head[NB];
-    Quad acc[NB];
-    const bool one_pass = p.d <= kPassCols;   // the heads of the lane's blocks are then the same for every segment
-    pass_heads(p, 0, q, head);
-    int64_t row, beg, end;
-    int s;
-    if (long_segment(p.geom, blockIdx.x, &row, &s, &beg, &end)) {
-        // ---- a long segment: 64-entry chunks over the 4 waves ----
-        const int64_t len = end - beg;   // (the same for the whole block)
-        const float* lrow = p.l + row * p.ldl + (int64_t)s * p.K;
-        const int32_t* cols = p.colidx[s] + beg;
-        float* out = p.y + row * p.ldy_row + (int64_t)s * p.ldy_hop;
-        if (len > 0) segment_stats<kWavesPerBlock>(p, s, lrow, cols, len, lane, wave, sh.red, sh.stat[0]);
-        __syncthreads();
-        for (int cbase = 0; cbase < p.d; cbase += kPassCols) {
-            clear(acc);
-            if (!one_pass) pass_heads(p, cbase, q, head);
-            for (int64_t c = (int64_t)wave * kWave; c < len; c += kBlock) {
-                const int count = (int)(len - c < kWave ? len - c : kWave);
-                const int ecol = cols[c + (lane < count ? lane : count - 1)];
-                wave_lds_sync();   // the previous chunk's reads of the tile come first
-                chunk_tile(p, s, lrow, ecol, count, lane, sh.stat[0], tile);
-                wave_lds_sync();
-                gather_chunk<NB, U>(p, tile, head, cbase, count, ecol, 0, lane, acc);
-            }
-            const Quad mine = fold_blocks(acc, gi);
-            if (gi < NB) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) sh.tot[wave][gi * kBlockCols + 4 * q + k] = mine.v[k];
-            }
-            __syncthreads();
-            const int c = threadIdx.x;
-            if (c < kPassCols && cbase + c < p.d) out[cbase + c] = ((sh.tot[0][c] + sh.tot[1][c]) + sh.tot[2][c]) + sh.tot[3][c];
-            __syncthreads();
-        }
-        return;
-    }
-    // ---- the tile walk: each wave walks rows_per_wave consecutive rows ----
-    int64_t row0, rp;
-    if (!wave_rows(p.geom, blockIdx.x, wave, lane, &row0, &rp)) return;
-    float* stat = sh.stat[wave];
-    const int rpw = p.geom.rows_per_wave;
-    for (s = 0; s < p.geom.n_sel; ++s) {
-        for (int i0 = 0; i0 < rpw && row0 + i0 < p.geom.n_rows; i0 += 4) {
-            // lane group gi looks at row i0 + gi: segments of at most 16 entries get their coefficients FOUR AT A TIME
-            int64_t gbeg, glen;
-            group_segment<false>(p.geom, s, i0, row0, rp, lane, &gbeg, &glen);
-            const bool is_short = glen >= 1 && glen <= kGroup;
-            int ecol = 0;
-            wave_lds_sync();   // the previous segments' reads of the tile come first
-            if (__ballot(is_short) != 0ull) ecol = short_tiles(p, s, row0 + i0 + gi, gbeg, is_short ? (int)glen : 0, lane, tile);
-            wave_lds_sync();
-#pragma unroll 1
-            for (int k = 0; k < 4; ++k) {
-                const int64_t len = readlane64(glen, k * kGroup);
-                if (len < 0 || len > kGroup) continue;   // (wave-uniform) no such row, a long segment, or one for the loop below
-                float* out = p.y + (row0 + i0 + k) * p.ldy_row + (int64_t)s * p.ldy_hop;
-                for (int cbase = 0; cbase < p.d; cbase += kPassCols) {
-                    clear(acc);
-                    if (!one_pass) pass_heads(p, cbase, q, head);
-                    if (len > 0) gather_chunk<NB, U>(p, tile + k * kGroup * p.K, head, cbase, (int)len, ecol, k * kGroup, lane, acc);
-                    const Quad mine = fold_blocks(acc, gi);   // (an empty segment: +0)
-                    if (gi < NB) store_quad(out, cbase + gi * kBlockCols + 4 * q, p.d, mine);
-                }
-            }
-            // the longer segments of these rows, one at a time on the whole wave
-#pragma unroll 1
-            for (int k = 0; k < 4; ++k) {
-                const int64_t len = readlane64(glen, k * kGroup);
-                if (len <= kGroup) continue;   // (wave-uniform)
-                beg = readlane64(gbeg, k * kGroup);
-                const float* lrow = p.l + (row0 + i0 + k) * p.ldl + (int64_t)s * p.K;
-                const int32_t* cols = p.colidx[s] + beg;
-                float* out = p.y + (row0 + i0 + k) * p.ldy_row + (int64_t)s * p.ldy_hop;
-                const bool single = len <= kWave;   // (wave-uniform)
-                wave_lds_sync();   // the previous segment's reads of the tile and of the statistics come first
-                if (single) {
-                    ecol = cols[lane < len ? lane : len - 1];
-                    single_chunk_tile(p, s, lrow, ecol, (int)len, lane, tile);
-                } else {
-                    segment_stats<1>(p, s, lrow, cols, len, lane, 0, nullptr, stat);
-                }
-                wave_lds_sync();
-                for (int cbase = 0; cbase < p.d; cbase += kPassCols) {
-                    clear(acc);
-                    if (!one_pass) pass_heads(p, cbase, q, head);
-                    if (single) {
-                        gather_chunk<NB, U>(p, tile, head, cbase, (int)len, ecol, 0, lane, acc);
-                    } else {
-                        for (int64_t c = 0; c < len; c += kWave) {
-                            const int count = (int)(len - c < kWave ? len - c : kWave);
-                            ecol = cols[c + (lane < count ? lane : count - 1)];
-                            wave_lds_sync();
-                            chunk_tile(p, s, lrow, ecol, count, lane, stat, tile);
-                            wave_lds_sync();
-                            gather_chunk<NB, U>(p, tile, head, cbase, count, ecol, 0, lane, acc);
-                        }
-                    }
-                    const Quad mine = fold_blocks(acc, gi);
-                    if (gi < NB) store_quad(out, cbase + gi * kBlockCols + 4 * q, p.d, mine);
-                }
-            }
-        }
-    }
+    forward_walk<float, NB, false>(p, sh, nullptr, 0);
 }
 
-// the three geometries of attention_fused_kernel
-static void launch_forward(const Params& p, float*, int64_t, dim3 grid, hipStream_t stream) {
-    const dim3 block(kBlock);
-    const int d = p.d;
-    // blocks of accumulators a lane keeps: the narrowest geometry that covers d in one column pass, four blocks beyond 256 columns
-    // (the bits are the same for all three: every column has its own tree)
-    if (d <= kBlockCols) hipLaunchKernelGGL((attention_fused_kernel<1>), grid, block, 0, stream, p);
-    else if (d <= 2 * kBlockCols) hipLaunchKernelGGL((attention_fused_kernel<2>), grid, block, 0, stream, p);
-    else hipLaunchKernelGGL((attention_fused_kernel<kMaxBlocks>), grid, block, 0, stream, p);
+void launch_forward(const Params& p, dim3 grid, hipStream_t stream) {
+    for_blocks(p.d, [&](auto nb) { hipLaunchKernelGGL((attention_fused_kernel<decltype(nb)::value>), grid, dim3(kBlock), 0, stream, p); });
 }
 
 // ------------------------------------------------------------------------------------------------------------ host
-// The launch path of h2gcn_attention_hops_heads_f32 (stats_launcher NULL) and of h2gcn_attention_hops_heads_stats_f32
-// (attention_stats.hip: its launcher, and stats [n_rows, H_sel, 2, K] through ldstats).
-int run(Launcher stats_launcher, float* stats, int64_t ldstats, const h2gcn_plan_t* plan, uint32_t hop_mask, const float* l, int64_t ldl,
-        const float* r, int64_t ldr, int32_t n_heads, float slope, const float* X, int64_t ldx, int32_t d, float* Y, int64_t ldy_row,
-        int64_t ldy_hop, void* stream_v, ViewLauncher view_launcher, const void* ctx) {
+// What follows the checks: the geometry, the parameter struct of the element type of x, the launch of the unit that has the kernel.
+template <typename P>
+static int launch(const Call& c, const PatternView& v) {
+    const bool y16 = c.y_dtype == H2GCN_DTYPE_BF16;
+    const int64_t need = (int64_t)v.n_sel * c.n_heads;
+    hipStream_t stream = (hipStream_t)c.stream;
+    P p;
+    memset(&p, 0, sizeof(p));
+    int64_t n_blocks;
+    int st = launch_geometry(c.plan, v, stream, &p.geom, &n_blocks);
+    if (st != H2GCN_OK) return st;
+    if (n_blocks == 0) {   // a selection without nonzeros: every row is empty
+        const size_t elem = y16 ? sizeof(uint16_t) : sizeof(float);
+        for (int s = 0; s < v.n_sel; ++s)
+            if ((st = zero_rows((char*)c.Y + (size_t)s * (size_t)c.ldy_hop * elem, c.ldy_row, c.d, v.n_rows, elem, stream)) != H2GCN_OK) return st;
+        if (c.with_stats) return zero_rows(c.stats, c.ldstats, 2 * need, v.n_rows, sizeof(float), stream);   // every segment: (+0, +0)
+        return H2GCN_OK;
+    }
+    for (int s = 0; s < v.n_sel; ++s) p.colidx[s] = v.colidx[s];
+    p.l = c.l, p.ldl = c.ldl;
+    p.r = c.r, p.ldr = c.ldr;
+    p.x = static_cast<decltype(p.x)>(c.X), p.ldx = c.ldx;
+    p.y = static_cast<decltype(p.y)>(c.Y), p.ldy_row = c.ldy_row, p.ldy_hop = c.ldy_hop;
+    p.d = c.d, p.K = c.n_heads, p.head_cols = c.d / c.n_heads;
+    p.slope = c.slope;
+    const dim3 grid((unsigned)n_blocks);
+    if constexpr (std::is_same<P, Params16>::value) {
+        launch_bf16(p, y16, c.with_stats, c.stats, c.ldstats, grid, stream);
+    } else if (c.dropout) {
+        launch_stats_dropout(p, c.stats, c.ldstats,
+                             attention_dropout::make_args(c.plan, v.mask, v.n_cols, c.dropout->keep_prob, c.dropout->seed, c.dropout->step_dev),
+                             grid, stream);
+    } else if (c.with_stats) {
+        launch_stats(p, c.stats, c.ldstats, grid, stream);
+    } else {
+        launch_forward(p, grid, stream);
+    }
+    H2GCN_HIP_TRY(hipGetLastError());
+    return H2GCN_OK;
+}
+
+// The launch path of h2gcn_attention_hops_heads{,_stats,_stats_dropout}_f32 and h2gcn_attention_hops_heads{,_stats}_bf16.  The checks
+// of a bf16 entry point are the fp32 ones in their order, the output's element type first and the layout rule of every bf16 array
+// after the strides it speaks of.
+int run(const Call& c) {
+    const bool x16 = c.x_dtype == H2GCN_DTYPE_BF16;
     try {
         // every check below comes before the device is touched
-        const bool with_stats = stats_launcher || view_launcher;
+        const int32_t d = c.d, n_heads = c.n_heads;
         PatternView v;
-        int st = pattern_view(plan, hop_mask, &v);
+        int st = pattern_view(c.plan, c.hop_mask, &v);
         if (st != H2GCN_OK) return st;
+        if (x16 && (st = check_dtype("y_dtype", c.y_dtype)) != H2GCN_OK) return st;
+        const bool y16 = c.y_dtype == H2GCN_DTYPE_BF16;
         if (d < 1) return fail(H2GCN_ERR_INVALID_ARGUMENT, "d = %d", d);
         if (n_heads < 1) return fail(H2GCN_ERR_INVALID_ARGUMENT, "n_heads = %d < 1", n_heads);
         if (n_heads > kMaxHeads)
@@ -192,56 +122,36 @@ int run(Launcher stats_launcher, float* stats, int64_t ldstats, const h2gcn_plan
             return fail(H2GCN_ERR_INVALID_ARGUMENT, "d / n_heads = %d is not a multiple of 4 (a lane's four columns must lie in one head)",
                         d / n_heads);
         const int64_t need = (int64_t)v.n_sel * n_heads;
-        if (ldl < need) return fail(H2GCN_ERR_INVALID_ARGUMENT, "ldl = %lld < H_sel * n_heads = %lld", (long long)ldl, (long long)need);
-        if (ldr < need) return fail(H2GCN_ERR_INVALID_ARGUMENT, "ldr = %lld < H_sel * n_heads = %lld", (long long)ldr, (long long)need);
-        if (ldx < d) return fail(H2GCN_ERR_INVALID_ARGUMENT, "ldx = %lld < d = %d", (long long)ldx, d);
-        if (ldy_row < d) return fail(H2GCN_ERR_INVALID_ARGUMENT, "ldy_row = %lld < d = %d", (long long)ldy_row, d);
-        if (ldy_hop < 0 || (v.n_sel > 1 && ldy_hop < d))
-            return fail(H2GCN_ERR_INVALID_ARGUMENT, "ldy_hop = %lld < d = %d: hop outputs would overlap", (long long)ldy_hop, d);
+        if (c.ldl < need) return fail(H2GCN_ERR_INVALID_ARGUMENT, "ldl = %lld < H_sel * n_heads = %lld", (long long)c.ldl, (long long)need);
+        if (c.ldr < need) return fail(H2GCN_ERR_INVALID_ARGUMENT, "ldr = %lld < H_sel * n_heads = %lld", (long long)c.ldr, (long long)need);
+        if (c.ldx < d) return fail(H2GCN_ERR_INVALID_ARGUMENT, "ldx = %lld < d = %d", (long long)c.ldx, d);
+        if (c.ldy_row < d) return fail(H2GCN_ERR_INVALID_ARGUMENT, "ldy_row = %lld < d = %d", (long long)c.ldy_row, d);
+        if (c.ldy_hop < 0 || (v.n_sel > 1 && c.ldy_hop < d))
+            return fail(H2GCN_ERR_INVALID_ARGUMENT, "ldy_hop = %lld < d = %d: hop outputs would overlap", (long long)c.ldy_hop, d);
+        if (x16 && (st = check_bf16_layout("X", c.X, c.ldx, 0, d)) != H2GCN_OK) return st;
+        if (y16 && (st = check_bf16_layout("Y", c.Y, c.ldy_row, c.ldy_hop, d)) != H2GCN_OK) return st;
         if (v.n_rows == 0) return H2GCN_OK;   // nothing to store
-        if (!Y) return fail(H2GCN_ERR_INVALID_ARGUMENT, "Y is NULL");
-        if (selected_nnz(v) > 0 && !l) return fail(H2GCN_ERR_INVALID_ARGUMENT, "l is NULL");
-        if (selected_nnz(v) > 0 && !r) return fail(H2GCN_ERR_INVALID_ARGUMENT, "r is NULL");
-        if (selected_nnz(v) > 0 && !X) return fail(H2GCN_ERR_INVALID_ARGUMENT, "X is NULL");
-        if (Y == X) return fail(H2GCN_ERR_INVALID_ARGUMENT, "Y aliases X");
-        if (Y == l) return fail(H2GCN_ERR_INVALID_ARGUMENT, "Y aliases l");
-        if (Y == r) return fail(H2GCN_ERR_INVALID_ARGUMENT, "Y aliases r");
-        if (with_stats) {
-            if (ldstats < 2 * need)
-                return fail(H2GCN_ERR_INVALID_ARGUMENT, "ldstats = %lld < H_sel * 2 * n_heads = %lld", (long long)ldstats, (long long)(2 * need));
-            if (!stats) return fail(H2GCN_ERR_INVALID_ARGUMENT, "stats is NULL");
-            if (stats == Y) return fail(H2GCN_ERR_INVALID_ARGUMENT, "stats aliases Y");
-            if (stats == X) return fail(H2GCN_ERR_INVALID_ARGUMENT, "stats aliases X");
-            if (stats == l) return fail(H2GCN_ERR_INVALID_ARGUMENT, "stats aliases l");
-            if (stats == r) return fail(H2GCN_ERR_INVALID_ARGUMENT, "stats aliases r");
+        if (!c.Y) return fail(H2GCN_ERR_INVALID_ARGUMENT, "Y is NULL");
+        if (selected_nnz(v) > 0 && !c.l) return fail(H2GCN_ERR_INVALID_ARGUMENT, "l is NULL");
+        if (selected_nnz(v) > 0 && !c.r) return fail(H2GCN_ERR_INVALID_ARGUMENT, "r is NULL");
+        if (selected_nnz(v) > 0 && !c.X) return fail(H2GCN_ERR_INVALID_ARGUMENT, "X is NULL");
+        if (c.Y == c.X) return fail(H2GCN_ERR_INVALID_ARGUMENT, "Y aliases X");
+        if (c.Y == (const void*)c.l) return fail(H2GCN_ERR_INVALID_ARGUMENT, "Y aliases l");
+        if (c.Y == (const void*)c.r) return fail(H2GCN_ERR_INVALID_ARGUMENT, "Y aliases r");
+        if (c.with_stats) {
+            if (c.ldstats < 2 * need)
+                return fail(H2GCN_ERR_INVALID_ARGUMENT, "ldstats = %lld < H_sel * 2 * n_heads = %lld", (long long)c.ldstats,
+                            (long long)(2 * need));
+            if (!c.stats) return fail(H2GCN_ERR_INVALID_ARGUMENT, "stats is NULL");
+            if ((void*)c.stats == c.Y) return fail(H2GCN_ERR_INVALID_ARGUMENT, "stats aliases Y");
+            if ((const void*)c.stats == c.X) return fail(H2GCN_ERR_INVALID_ARGUMENT, "stats aliases X");
+            if (c.stats == c.l) return fail(H2GCN_ERR_INVALID_ARGUMENT, "stats aliases l");
+            if (c.stats == c.r) return fail(H2GCN_ERR_INVALID_ARGUMENT, "stats aliases r");
         }
-        hipStream_t stream = (hipStream_t)stream_v;
-        Params p;
-        memset(&p, 0, sizeof(p));
-        int64_t n_blocks;
-        if ((st = launch_geometry(plan, v, stream, &p.geom, &n_blocks)) != H2GCN_OK) return st;
-        if (n_blocks == 0) {   // a selection without nonzeros: every row is empty
-            for (int s = 0; s < v.n_sel; ++s)
-                H2GCN_HIP_TRY(hipMemset2DAsync(Y + (int64_t)s * ldy_hop, (size_t)ldy_row * sizeof(float), 0, (size_t)d * sizeof(float),
-                                               (size_t)v.n_rows, stream));
-            if (with_stats)   // every segment is empty: (+0, +0)
-                H2GCN_HIP_TRY(hipMemset2DAsync(stats, (size_t)ldstats * sizeof(float), 0, (size_t)(2 * need) * sizeof(float), (size_t)v.n_rows,
-                                               stream));
-            return H2GCN_OK;
-        }
-        for (int s = 0; s < v.n_sel; ++s) p.colidx[s] = v.colidx[s];
-        p.l = l, p.ldl = ldl;
-        p.r = r, p.ldr = ldr;
-        p.x = X, p.ldx = ldx;
-        p.y = Y, p.ldy_row = ldy_row, p.ldy_hop = ldy_hop;
-        p.d = d, p.K = n_heads, p.head_cols = d / n_heads;
-        p.slope = slope;
-        if (view_launcher) view_launcher(p, stats, ldstats, v, ctx, dim3((unsigned)n_blocks), stream);
-        else (stats_launcher ? stats_launcher : launch_forward)(p, stats, ldstats, dim3((unsigned)n_blocks), stream);
-        H2GCN_HIP_TRY(hipGetLastError());
-        return H2GCN_OK;
+        return x16 ? launch<Params16>(c, v) : launch<Params>(c, v);
     } catch (...) {
-        return fail(H2GCN_ERR_INTERNAL, "unexpected exception in attention_hops_heads%s_f32", view_launcher ? "_stats_dropout" : (stats_launcher ? "_stats" : ""));
+        return fail(H2GCN_ERR_INTERNAL, "unexpected exception in attention_hops_heads%s%s_%s", c.with_stats ? "_stats" : "",
+                    c.dropout ? "_dropout" : "", x16 ? "bf16" : "f32");
     }
 }
 
@@ -253,8 +163,8 @@ extern "C" {
 int h2gcn_attention_hops_heads_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* l_dev, int64_t ldl, const float* r_dev,
                                    int64_t ldr, int32_t n_heads, float negative_slope, const float* X_dev, int64_t ldx, int32_t d,
                                    float* Y_dev, int64_t ldy_row, int64_t ldy_hop, void* stream) {
-    return h2gcn::attention_fused::run(nullptr, nullptr, 0, plan, hop_mask, l_dev, ldl, r_dev, ldr, n_heads, negative_slope, X_dev, ldx, d,
-                                       Y_dev, ldy_row, ldy_hop, stream);
+    return h2gcn::attention_fused::run({plan, hop_mask, l_dev, ldl, r_dev, ldr, n_heads, negative_slope, H2GCN_DTYPE_F32, X_dev, ldx, d,
+                                        H2GCN_DTYPE_F32, Y_dev, ldy_row, ldy_hop, false, nullptr, 0, nullptr, stream});
 }
 
 }  // extern "C"

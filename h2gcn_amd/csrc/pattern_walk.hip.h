@@ -107,6 +107,30 @@ int check_hop_arrays(const PatternView& v, const char* name, T* const* ptrs) {
     return H2GCN_OK;
 }
 
+// bf16 arrays: 4-byte aligned base, even strides (elements) and an even width (the rule of the bf16 SpMM launches)
+inline int check_bf16_layout(const char* what, const void* ptr, int64_t ld_row, int64_t ld_hop, int32_t d) {
+    if (reinterpret_cast<uintptr_t>(ptr) & 3u)
+        return fail(H2GCN_ERR_INVALID_ARGUMENT, "bf16 %s: the base address must be 4-byte aligned", what);
+    if ((ld_row & 1) || (ld_hop & 1))
+        return fail(H2GCN_ERR_INVALID_ARGUMENT, "bf16 %s: row / hop strides must be even (got %lld / %lld elements)", what,
+                    (long long)ld_row, (long long)ld_hop);
+    if (d & 1) return fail(H2GCN_ERR_INVALID_ARGUMENT, "bf16 %s: the feature width d must be even (got %d)", what, d);
+    return H2GCN_OK;
+}
+
+inline int check_dtype(const char* what, int dtype) {
+    if (dtype != H2GCN_DTYPE_F32 && dtype != H2GCN_DTYPE_BF16)
+        return fail(H2GCN_ERR_INVALID_ARGUMENT, "%s = %d: must be H2GCN_DTYPE_F32 (%d) or H2GCN_DTYPE_BF16 (%d)", what, dtype,
+                    H2GCN_DTYPE_F32, H2GCN_DTYPE_BF16);
+    return H2GCN_OK;
+}
+
+// `width` elements of `elem` bytes in each of `n` rows `ld` elements apart: +0 in either format
+inline int zero_rows(void* out, int64_t ld, int64_t width, int64_t n, size_t elem, hipStream_t stream) {
+    if (out && n > 0 && width > 0) H2GCN_HIP_TRY(hipMemset2DAsync(out, (size_t)ld * elem, 0, (size_t)width * elem, (size_t)n, stream));
+    return H2GCN_OK;
+}
+
 // Fills `g` and the grid size (0: nothing to launch).  The first step that touches the device (the long list): checks come before.
 // `adjoint`: v is an adjoint_view and the list is the adjoint's -- one entry per row that is long in any selected hop, bare (no
 // `<< 4 | s`): long_segment does not read it.

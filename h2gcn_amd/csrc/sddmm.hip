@@ -160,17 +160,6 @@ __global__ __launch_bounds__(kBlock) void sddmm_hops_kernel(const Params p) {
     }
 }
 
-// bf16 arrays: 4-byte aligned base, even strides (elements) and an even width (the rule of the bf16 SpMM launches)
-int check_bf16_layout(const char* what, const void* ptr, int64_t ld_row, int64_t ld_hop, int32_t d) {
-    if (reinterpret_cast<uintptr_t>(ptr) & 3u)
-        return fail(H2GCN_ERR_INVALID_ARGUMENT, "bf16 %s: the base address must be 4-byte aligned", what);
-    if ((ld_row & 1) || (ld_hop & 1))
-        return fail(H2GCN_ERR_INVALID_ARGUMENT, "bf16 %s: row / hop strides must be even (got %lld / %lld elements)", what,
-                    (long long)ld_row, (long long)ld_hop);
-    if (d & 1) return fail(H2GCN_ERR_INVALID_ARGUMENT, "bf16 %s: the feature width d must be even (got %d)", what, d);
-    return H2GCN_OK;
-}
-
 template <typename TS>
 int sddmm_hops(const h2gcn_plan_t* plan, uint32_t hop_mask, const void* dY, int64_t ldg_row, int64_t ldg_hop, const void* X,
                int64_t ldx, int32_t d, float* const* dvals, void* stream_v) {
