@@ -21,6 +21,8 @@ C ABI of ``include/h2gcn_hip.h``).  It mirrors the reference's operator interfac
   TRAINING step without per-entry arrays: a forward that stores the softmax statistics and a backward that recomputes per entry;
   :func:`h2gcn_amd.layers.hop_attention_recompute_dropout` / ``layer.set_attention_dropout(p)``: dropout on the attention
   coefficients, the mask drawn inside those kernels (new);
+* :func:`h2gcn_amd.layers.hop_edge_scores_dynamic` / :class:`h2gcn_amd.layers.DynamicHopAttention` -- dynamic (GATv2) attention:
+  ``a . leaky_relu(u[i] + v[j])`` per head in one launch per direction, without an ``nnz x d`` array (new);
 * :class:`h2gcn_amd.hops.HopPlan` -- the device-resident ``adj_hops`` operand list
   (reference ``h2gcn/datasets/_dataset.py:559-576``);
 * :mod:`h2gcn_amd.operands` -- construction of the normalised exact-k-hop matrices: on the device with the HIP ring
@@ -47,6 +49,6 @@ __version__ = "0.6.0"
 
 from . import _capi  # noqa: F401  (does not load the library until first use)
 from .hops import HopPlan, RowSelection  # noqa: F401
-from .layers import (ConcatLayer, DropoutDense, GCNLayer, HopAttention, MultiHeadHopAttention, RecomputeMultiHeadHopAttention,  # noqa: F401
+from .layers import (ConcatLayer, DropoutDense, DynamicHopAttention, GCNLayer, HopAttention, MultiHeadHopAttention, RecomputeMultiHeadHopAttention,  # noqa: F401
                      SliceLayer, SparseDense, SparseDropout, hop_attention_heads, hop_attention_recompute, hop_attention_recompute_dropout, hop_edge_scores,
-                     hop_edge_scores_heads, hop_softmax, hop_softmax_heads, hop_spmm, hop_spmm_values)
+                     hop_edge_scores_dynamic, hop_edge_scores_heads, hop_softmax, hop_softmax_heads, hop_spmm, hop_spmm_values)

@@ -69,6 +69,9 @@ EXPORTED_SYMBOLS = (
     "h2gcn_row_softmax_backward_hops_heads_f32",
     "h2gcn_edge_scores_hops_heads_f32",
     "h2gcn_edge_scores_backward_hops_heads_f32",
+    "h2gcn_edge_scores_dynamic_workspace_bytes",
+    "h2gcn_edge_scores_dynamic_hops_f32",
+    "h2gcn_edge_scores_dynamic_backward_hops_f32",
     "h2gcn_spmm_hops_values_f32",
     "h2gcn_spmm_hops_T_values_f32",
     "h2gcn_attention_hops_heads_f32",
@@ -274,6 +277,15 @@ def lib() -> C.CDLL:
         L.h2gcn_edge_scores_hops_heads_f32.argtypes = node_heads_args + [C.c_void_p]
         L.h2gcn_edge_scores_backward_hops_heads_f32.restype = C.c_int
         L.h2gcn_edge_scores_backward_hops_heads_f32.argtypes = node_heads_args + [C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p]
+    if hasattr(L, "h2gcn_edge_scores_dynamic_hops_f32"):   # (the dynamic (GATv2) edge scores, added within ABI 5)
+        dyn_args = [C.c_void_p, C.c_uint32, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_void_p, C.c_int64, C.c_int32, C.c_int32,
+                    C.c_float, C.POINTER(C.c_void_p)]
+        L.h2gcn_edge_scores_dynamic_workspace_bytes.restype = C.c_size_t
+        L.h2gcn_edge_scores_dynamic_workspace_bytes.argtypes = [C.c_void_p, C.c_uint32, C.c_int32]
+        L.h2gcn_edge_scores_dynamic_hops_f32.restype = C.c_int
+        L.h2gcn_edge_scores_dynamic_hops_f32.argtypes = dyn_args + [C.c_void_p]
+        L.h2gcn_edge_scores_dynamic_backward_hops_f32.restype = C.c_int
+        L.h2gcn_edge_scores_dynamic_backward_hops_f32.argtypes = dyn_args + [C.c_void_p, C.c_int64] * 3 + [C.c_void_p, C.c_size_t, C.c_void_p]
     if hasattr(L, "h2gcn_spmm_hops_values_f32"):   # (the hop SpMM on per-launch values with heads, added within ABI 5)
         values_args = [C.c_void_p, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.c_int32]
         L.h2gcn_spmm_hops_values_f32.restype = C.c_int

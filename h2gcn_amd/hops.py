@@ -892,6 +892,101 @@ class HopPlan:
         _capi.check(st)
         return dl, dr
 
+    # ---- dynamic (GATv2) edge scores: the nonlinearity between the gather and the reduction over a head's columns
+    #: the widest ``u`` / ``v`` the dynamic edge scores serve (a node row stays in registers)
+    EDGE_SCORES_DYNAMIC_MAX_WIDTH = 256
+    _DYNAMIC_SYMBOLS = ("h2gcn_edge_scores_dynamic_workspace_bytes", "h2gcn_edge_scores_dynamic_hops_f32",
+                        "h2gcn_edge_scores_dynamic_backward_hops_f32")
+
+    @classmethod
+    def _dynamic_symbols(cls) -> None:
+        if not all(_capi.has(s) for s in cls._DYNAMIC_SYMBOLS):
+            raise RuntimeError(f"{_capi.library_path()} predates the dynamic edge scores ({', '.join(cls._DYNAMIC_SYMBOLS)}): rebuild it")
+
+    def _dynamic_operands(self, u, v, a, heads, h_sel: int):
+        """``u`` ``[n_rows, d]``, ``v`` ``[n_cols, d]`` and ``a`` ``[H_sel, d]`` (or ``[H_sel, K, d / K]``) of the dynamic edge scores,
+        checked -> ``(u, ldu, v, ldv, a, lda, d, K)``.  Row strides pass through; a non-unit column stride is made contiguous."""
+        for name, t in (("u", u), ("v", v), ("a", a)):
+            _require(isinstance(t, torch.Tensor), f"{name} must be a tensor, got {type(t).__name__}")
+            _require(t.dtype == torch.float32, f"{name} must be float32 (the dynamic edge scores are fp32 only), got {t.dtype}")
+            _require(t.device == self.device, f"{name} on {t.device}, plan on {self.device}")
+        _require(u.dim() == 2 and u.shape[0] == self.n_rows and u.shape[1] >= 1, f"u must be [{self.n_rows}, d], got {tuple(u.shape)}")
+        d = int(u.shape[1])
+        _require(tuple(v.shape) == (self.n_cols, d), f"v must be [{self.n_cols}, {d}], got {tuple(v.shape)}")
+        n_heads = int(heads)
+        _require(n_heads >= 1, f"heads = {heads} < 1")
+        self._head_width(d, n_heads)
+        _require(d <= self.EDGE_SCORES_DYNAMIC_MAX_WIDTH,
+                 f"the width d = {d} exceeds EDGE_SCORES_DYNAMIC_MAX_WIDTH = {self.EDGE_SCORES_DYNAMIC_MAX_WIDTH} (a node row stays in registers)")
+        if a.dim() == 3 and tuple(a.shape) == (h_sel, n_heads, d // n_heads):
+            a = a.reshape(h_sel, d)
+        _require(tuple(a.shape) == (h_sel, d),
+                 f"a must be [{h_sel}, {d}] or [{h_sel}, {n_heads}, {d // n_heads}] (one row per selected hop), got {tuple(a.shape)}")
+        out = []
+        for t, n in ((u, self.n_rows), (v, self.n_cols), (a, h_sel)):
+            if (d > 1 and t.stride(1) != 1) or (n > 1 and t.stride(0) < d):
+                t = t.contiguous()
+            out += [t, t.stride(0) if n > 1 else d]
+        return (*out, d, n_heads)
+
+    def edge_scores_dynamic(self, u: torch.Tensor, v: torch.Tensor, a: torch.Tensor, heads: int = 1, negative_slope: float = 0.2,
+                            hops=None, out: Optional[Sequence[torch.Tensor]] = None) -> list:
+        """Dynamic (GATv2) attention scores on the pattern: ``score[s][e, h] = sum_{c in head h} a[s, c] * leaky_relu(u[i, c] + v[j, c])``
+        for every stored entry ``e = (i, j)`` of selected hop ``s`` -> one contiguous float32 ``[nnz_k, K]`` tensor per selected hop
+        (``[nnz_k]`` for ``heads == 1``), in the entry order of ``colidx[k]`` (``h2gcn_edge_scores_dynamic_hops_f32``: one launch,
+        nothing of size ``nnz x d``).  Unlike :meth:`edge_scores_heads` the ranking of a row's neighbours depends on the row.
+
+        ``u`` ``[n_rows, d]``, ``v`` ``[n_cols, d]``, ``a`` ``[H_sel, d]`` (or ``[H_sel, K, d // K]``): float32; ``d <= 256``,
+        ``d % heads == 0`` and, for ``heads > 1``, ``(d // heads) % 4 == 0``.  Row strides pass through.  The bits are a function of
+        ``a[s]``, ``u[i]``, ``v[j]``, ``d``, ``K`` and the slope alone (``include/h2gcn_hip.h``).  Only the forward pattern is read."""
+        mask, sel = self._mask(hops), self._selected(hops)
+        u, ldu, v, ldv, a, lda, d, n_heads = self._dynamic_operands(u, v, a, heads, len(sel))
+        out = self._segment_outputs("dynamic edge scores", out, sel, None if n_heads == 1 else n_heads)
+        self._dynamic_symbols()
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            st = _capi.lib().h2gcn_edge_scores_dynamic_hops_f32(
+                self._handle, mask, C.c_void_p(u.data_ptr()), ldu, C.c_void_p(v.data_ptr()), ldv, C.c_void_p(a.data_ptr()), lda, d, n_heads,
+                float(negative_slope), *self._segment_ptrs(out), C.c_void_p(stream))
+        _capi.check(st)
+        return out
+
+    def edge_scores_dynamic_backward(self, u: torch.Tensor, v: torch.Tensor, a: torch.Tensor, grad: Sequence[torch.Tensor], heads: int = 1,
+                                     negative_slope: float = 0.2, hops=None, need_du: bool = True, need_dv: bool = True,
+                                     need_da: bool = True) -> tuple:
+        """The backward of :meth:`edge_scores_dynamic` -> ``(du, dv, da)``, ``[n_rows, d]``, ``[n_cols, d]`` and ``[H_sel, d]``
+        (``h2gcn_edge_scores_dynamic_backward_hops_f32``): ``u + v`` and its leaky_relu are recomputed per entry, nothing of size
+        ``nnz x d`` is stored.  No float atomics: fixed summation orders (``include/h2gcn_hip.h``), ``du`` / ``dv`` independent of
+        ``rows_per_wave`` and of which outputs were asked for.  Every element is written; a node without entries gets ``+0``.
+
+        ``grad``: ``H_sel`` contiguous float32 ``[nnz_k, K]`` tensors (``[nnz_k]`` for one head).  ``need_*``: compute only those
+        (``None`` for the others; all ``False`` is refused).  ``dv`` walks the plan's transposed operands through their permutation:
+        ``build_transpose=True, keep_permutation=True`` (``symmetric_pattern=True`` serves it on the forward arrays).  The workspace
+        of ``da`` is allocated per call."""
+        mask, sel = self._mask(hops), self._selected(hops)
+        h_sel = len(sel)
+        _require(need_du or need_dv or need_da, "need_du, need_dv and need_da are all False: nothing to compute")
+        u, ldu, v, ldv, a, lda, d, n_heads = self._dynamic_operands(u, v, a, heads, h_sel)
+        grad, _ = self._segment_tensors("dynamic edge scores", "grad", grad, sel, None if n_heads == 1 else n_heads)
+        self._column_side(need_dv)
+        self._dynamic_symbols()
+        du = torch.empty((self.n_rows, d), dtype=torch.float32, device=self.device) if need_du else None
+        dv = torch.empty((self.n_cols, d), dtype=torch.float32, device=self.device) if need_dv else None
+        da = torch.empty((h_sel, d), dtype=torch.float32, device=self.device) if need_da else None
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        with torch.cuda.device(self.device):
+            ws = None
+            if need_da:
+                nbytes = int(_capi.lib().h2gcn_edge_scores_dynamic_workspace_bytes(self._handle, mask, d))
+                ws = torch.empty(max(nbytes, 4), dtype=torch.uint8, device=self.device)
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            st = _capi.lib().h2gcn_edge_scores_dynamic_backward_hops_f32(
+                self._handle, mask, C.c_void_p(u.data_ptr()), ldu, C.c_void_p(v.data_ptr()), ldv, C.c_void_p(a.data_ptr()), lda, d, n_heads,
+                float(negative_slope), *self._segment_ptrs(grad), ptr(du), d, ptr(dv), d, ptr(da), d, ptr(ws),
+                0 if ws is None else ws.numel(), C.c_void_p(stream))
+        _capi.check(st)
+        return du, dv, da
+
     #: the largest K the fused attention forward serves (``h2gcn_attention_hops_heads_f32``); beyond it the chain is the way
     ATTENTION_FUSED_MAX_HEADS = 16
 

@@ -383,6 +383,63 @@ def hop_edge_scores_heads(adjhops: HopPlan, l: torch.Tensor, r: torch.Tensor, ne
     return tuple(adjhops.edge_scores_heads(l, r, negative_slope, hops=sel))
 
 
+class _HopEdgeScoresDynamic(torch.autograd.Function):
+    """The dynamic (GATv2) edge scores: one launch forward (``HopPlan.edge_scores_dynamic``), one call backward.  ``u``, ``v``, ``a``
+    are saved; ``u + v`` and its leaky_relu are recomputed per entry in the backward: nothing of size ``nnz x d`` is kept."""
+
+    @staticmethod
+    def forward(ctx, plan: HopPlan, hops, heads: int, negative_slope: float, u: torch.Tensor, v: torch.Tensor, a: torch.Tensor):
+        scores = plan.edge_scores_dynamic(u, v, a, heads, negative_slope, hops=hops)
+        ctx.plan, ctx.hops, ctx.heads, ctx.negative_slope = plan, hops, heads, negative_slope
+        ctx.save_for_backward(u, v, a)
+        return tuple(scores)
+
+    @staticmethod
+    def backward(ctx, *grads):
+        need_du, need_dv, need_da = ctx.needs_input_grad[4:7]
+        if not (need_du or need_dv or need_da):
+            return (None,) * 7
+        u, v, a = ctx.saved_tensors
+        plan = ctx.plan
+        shape = (lambda k: (plan.colidx[k].numel(),) + (() if ctx.heads == 1 else (ctx.heads,)))
+        # (a hop nobody differentiated through enters as zeros)
+        grads = [torch.zeros(shape(k), dtype=torch.float32, device=plan.device) if g is None else g.contiguous()
+                 for g, k in zip(grads, plan._selected(ctx.hops))]
+        du, dv, da = plan.edge_scores_dynamic_backward(u, v, a, grads, ctx.heads, ctx.negative_slope, hops=ctx.hops, need_du=need_du,
+                                                       need_dv=need_dv, need_da=need_da)
+        return None, None, None, None, du, dv, None if da is None else da.view(a.shape)
+
+
+def hop_edge_scores_dynamic(adjhops: HopPlan, u: torch.Tensor, v: torch.Tensor, a: torch.Tensor, heads: int = 1, negative_slope: float = 0.2,
+                            hops: Optional[Iterable[int]] = None) -> tuple:
+    """Dynamic (GATv2) attention scores: ``scores[s][e, h] = sum_{c in head h} a[s, c] * leaky_relu(u[i, c] + v[j, c], negative_slope)``
+    for every stored entry ``e = (i, j)`` of selected hop ``s``, as a tuple of ``H_sel`` contiguous float32 ``[nnz_k, K]`` tensors
+    (``[nnz_k]`` for ``heads == 1``: what :func:`hop_softmax_heads` / :func:`hop_softmax` take), differentiable wrt ``u``
+    ``[n_rows, d]``, ``v`` ``[n_cols, d]`` and ``a`` ``[H_sel, d]`` (or ``[H_sel, K, d // K]``).  Where :func:`hop_edge_scores_heads`
+    ranks the neighbours of every row by ``r[j]`` alone, here the ranking depends on the row.  Forward and backward are one call each
+    (:meth:`HopPlan.edge_scores_dynamic` / :meth:`HopPlan.edge_scores_dynamic_backward`): ``u + v`` is recomputed per entry and no
+    ``nnz x d`` array exists in either direction, which is why this is never run as a composite of torch operations; ``d > 256`` is
+    a ``ValueError``.  A gradient for ``v`` needs a plan built with ``build_transpose=True, keep_permutation=True``.  float32 only.
+    Row-partitioned operands (``ShardedHops``) are not covered."""
+    if hasattr(adjhops, "aggregate"):
+        raise ValueError("hop_edge_scores_dynamic is not supported on row-partitioned operands (ShardedHops): pass a single-GPU HopPlan")
+    if not isinstance(adjhops, HopPlan):
+        raise TypeError(f"adjhops must be a HopPlan, got {type(adjhops).__name__}")
+    sel = None if hops is None else tuple(sorted(set(int(h) for h in hops)))
+    if isinstance(u, torch.Tensor) and u.dim() == 2 and u.shape[1] > HopPlan.EDGE_SCORES_DYNAMIC_MAX_WIDTH:
+        raise ValueError(f"hop_edge_scores_dynamic serves widths up to EDGE_SCORES_DYNAMIC_MAX_WIDTH = {HopPlan.EDGE_SCORES_DYNAMIC_MAX_WIDTH}, "
+                         f"got d = {u.shape[1]}")
+    grads = [isinstance(t, torch.Tensor) and t.requires_grad and torch.is_grad_enabled() for t in (u, v, a)]
+    if grads[1] and not (adjhops.has_transpose and adjhops.keep_permutation):
+        raise ValueError("hop_edge_scores_dynamic with a v that requires a gradient: that gradient sums over the columns of the hop "
+                         "matrices, on the plan's transposed operands through their permutation.  Build the plan with "
+                         "HopPlan(..., build_transpose=True, keep_permutation=True)")
+    if any(grads):
+        # (the argument checks of the launch run first either way: HopPlan.edge_scores_dynamic refuses before any device work)
+        return _HopEdgeScoresDynamic.apply(adjhops, sel, int(heads), float(negative_slope), u, v, a)
+    return tuple(adjhops.edge_scores_dynamic(u, v, a, heads, negative_slope, hops=sel))
+
+
 def hop_attention_heads(adjhops: HopPlan, inputs: torch.Tensor, l: torch.Tensor, r: torch.Tensor, negative_slope: float = 0.2,
                         hops: Optional[Iterable[int]] = None) -> torch.Tensor:
     """Multi-head attention over the hop pattern, scores to aggregation: ``[n_cols, d] -> [n_rows, H_sel, d]`` with
@@ -837,6 +894,76 @@ class RecomputeMultiHeadHopAttention(MultiHeadHopAttention):
             return hop_attention_recompute(adjhops, inputs, _StackHeads.apply(*ls), _StackHeads.apply(*rs), self.negative_slope, self.hops)
         return hop_attention_recompute_dropout(adjhops, inputs, _StackHeads.apply(*ls), _StackHeads.apply(*rs), self.attn_dropout, self.seed,
                                                step, self.negative_slope, self.hops)
+
+
+class DynamicHopAttention(torch.nn.Module):
+    """``DynamicHopAttention(in_dim, heads, hops=None, n_hops=2, negative_slope=0.2, share_weights=False)(adjhops, inputs) ->
+    [N, H_sel, in_dim]``: GATv2 (Brody et al.) on the hop rings.  :class:`MultiHeadHopAttention` scores an entry with
+    ``leaky_relu(l[i] + r[j])``, which ranks the neighbours of EVERY row by ``r[j]`` alone (static attention); here
+
+        ``u = inputs @ W_l``, ``v = inputs @ W_r``, ``score[s][e, h] = sum_{c in head h} a[s, h, c] * leaky_relu(u[i, c] + v[j, c])``
+
+    so whom a node listens to depends on the node -- what heterophilous graphs ask for.  Then :func:`hop_softmax_heads`
+    (:func:`hop_softmax` for one head) and ONE aggregation launch ``hop_spmm_values(adjhops, v, alpha)``: GATv2 aggregates the
+    source projection.  Head ``h`` owns columns ``h * in_dim / K ..`` of ``u``, ``v`` and of the output.
+
+    Parameters, Glorot-uniform and drawn in this order: ``W_l`` ``[in_dim, in_dim]``, ``W_r`` ``[in_dim, in_dim]`` (absent with
+    ``share_weights=True``: ``v = u``, GATv2's ``share_weights``), ``a`` ``[H_sel, heads, in_dim // heads]``.  ``heads``: an
+    integer ``K >= 1`` with ``in_dim % K == 0``, and ``(in_dim / K) % 4 == 0`` when ``K > 1``; ``in_dim <= 256``.
+
+    The scores are one launch per direction (:func:`hop_edge_scores_dynamic`) without an ``nnz x in_dim`` array; nothing is
+    installed in the plan, so such layers stack on one plan and their training step can be captured in a hipGraph after one eager
+    warm-up.  Training needs a square plan built with ``build_transpose=True, keep_permutation=True``.  float32 only; no attention
+    dropout.  Row-partitioned operands (``ShardedHops``) are not covered."""
+
+    SIGNATURE = ["adjhops", "inputs"]
+
+    def __init__(self, in_dim: int, heads: int, hops=None, n_hops: int = 2, negative_slope: float = 0.2, share_weights: bool = False):
+        super().__init__()
+        self.hops = None if hops is None else tuple(sorted(set(int(h) for h in hops)))
+        self.in_dim, self.heads = int(in_dim), int(heads)
+        self.negative_slope = float(negative_slope)
+        self.share_weights = bool(share_weights)
+        h_sel = int(n_hops) if self.hops is None else len(self.hops)
+        if h_sel < 1 or self.in_dim < 1:
+            raise ValueError(f"DynamicHopAttention needs at least one hop and one input column, got {h_sel} hops and in_dim = {in_dim}")
+        if self.heads < 1 or self.in_dim % self.heads:
+            raise ValueError(f"DynamicHopAttention(heads={heads}) needs heads >= 1 and in_dim % heads == 0, got in_dim = {in_dim}")
+        if self.heads > 1 and (self.in_dim // self.heads) % 4:
+            raise ValueError(f"DynamicHopAttention(heads={heads}): the head width in_dim / heads = {self.in_dim // self.heads} must be "
+                             "a multiple of 4")
+        if self.in_dim > HopPlan.EDGE_SCORES_DYNAMIC_MAX_WIDTH:
+            raise ValueError(f"DynamicHopAttention(in_dim={in_dim}): the dynamic edge scores serve widths up to "
+                             f"EDGE_SCORES_DYNAMIC_MAX_WIDTH = {HopPlan.EDGE_SCORES_DYNAMIC_MAX_WIDTH}")
+        self.W_l = torch.nn.Parameter(torch.empty(self.in_dim, self.in_dim))
+        torch.nn.init.xavier_uniform_(self.W_l)
+        if not self.share_weights:
+            self.W_r = torch.nn.Parameter(torch.empty(self.in_dim, self.in_dim))
+            torch.nn.init.xavier_uniform_(self.W_r)
+        self.a = torch.nn.Parameter(torch.empty(h_sel, self.heads, self.in_dim // self.heads))
+        torch.nn.init.xavier_uniform_(self.a)
+
+    def forward(self, adjhops: HopPlan, inputs: torch.Tensor) -> torch.Tensor:
+        if hasattr(adjhops, "aggregate"):
+            raise ValueError("DynamicHopAttention is not supported on row-partitioned operands (ShardedHops): pass a single-GPU HopPlan")
+        if not isinstance(adjhops, HopPlan):
+            raise TypeError(f"adjhops must be a HopPlan, got {type(adjhops).__name__}")
+        h_sel = self.a.shape[0]
+        if adjhops.n_selected(self.hops) != h_sel:
+            raise ValueError(f"DynamicHopAttention holds attention vectors for {h_sel} hops, the plan has {adjhops.n_hops}: pass hops= or n_hops=")
+        if adjhops.n_rows != adjhops.n_cols:
+            raise ValueError(f"DynamicHopAttention needs a square plan (the same nodes attend and are attended to), got {adjhops.n_rows} x {adjhops.n_cols}")
+        if inputs.dim() != 2 or inputs.shape[1] != self.in_dim:
+            raise ValueError(f"inputs must be [{adjhops.n_cols}, {self.in_dim}], got {tuple(inputs.shape)}")
+        u = inputs @ self.W_l
+        v = u if self.share_weights else inputs @ self.W_r
+        scores = hop_edge_scores_dynamic(adjhops, u, v, self.a, self.heads, self.negative_slope, self.hops)
+        alpha = hop_softmax(adjhops, scores, self.hops) if self.heads == 1 else hop_softmax_heads(adjhops, scores, self.hops)
+        return hop_spmm_values(adjhops, v, alpha, self.hops)
+
+    def extra_repr(self) -> str:
+        return (f"in_dim={self.in_dim}, heads={self.heads}, hops={None if self.hops is None else list(self.hops)}, "
+                f"negative_slope={self.negative_slope}, share_weights={self.share_weights}")
 
 
 class GCNLayer(torch.nn.Module):

@@ -602,6 +602,86 @@ int h2gcn_edge_scores_backward_hops_heads_f32(const h2gcn_plan_t* plan, uint32_t
                                               int64_t lddr, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------
+ * DYNAMIC (GATv2, Brody et al.) edge scores on the hop pattern and their backward (added within ABI 5; found by symbol like the
+ * launches above).  leaky(l[i] + r[j]) is monotone in r[j]: inside a row every node ranks its neighbours alike.  Here the
+ * nonlinearity sits between the gather and the reduction over the columns of a head:
+ *
+ *     forward    p_c   = u[i*ldu + c] + v[j*ldv + c]                    one fp32 addition
+ *                q_c   = p_c > 0 ? p_c : p_c * negative_slope           a NaN p takes the slope branch
+ *                score[s][e*K + h] = sum_{c in head h} a[s*lda + c] * q_c            e = (i, j) a stored entry of selected hop s
+ *     backward   dq_c  = ds[s][e*K + h(c)] * a[s*lda + c]               one multiplication; p, q recomputed as above
+ *                dp_c  = p_c > 0 ? dq_c : dq_c * negative_slope
+ *                du[i*lddu + c] = sum_s sum_{e in row i of A_s}    dp_c
+ *                dv[j*lddv + c] = sum_s sum_{e in column j of A_s} dp_c
+ *                da[s*ldda + c] = sum_{e in A_s} ds[s][e*K + h(c)] * q_c
+ *
+ * with h(c) = c / w, w = d / K: head h owns the columns h*w .. (h+1)*w - 1.  Nothing of size nnz x d exists anywhere.
+ *
+ *   u_dev      [n_rows, d], row stride ldu >= d;  v_dev [n_cols, d], row stride ldv >= d (n_rows != n_cols is allowed)
+ *   a_dev      [H_sel, d], row stride lda >= d: row s belongs to the s-th selected hop
+ *   scores_dev / dscores_dev   HOST arrays of H_sel device pointers; entry s holds nnz_k * K floats, contiguous ENTRY-MAJOR (element
+ *              (e, h) at e*K + h; K = 1: [nnz_k]), in the entry order of colidx_dev[k]; dscores in FORWARD entry order
+ *   du_dev / dv_dev / da_dev   [n_rows, d] / [n_cols, d] / [H_sel, d] through lddu / lddv / ldda >= d.  Each may be NULL: not wanted
+ *              (all three NULL is an error)
+ *   workspace_dev   h2gcn_edge_scores_dynamic_workspace_bytes(plan, hop_mask, d) bytes, 4-byte aligned, used on `stream`: needed
+ *              when da_dev is given (0 is returned for arguments the launch would refuse)
+ * fp32 only.  Limits: d <= 256 (a node row stays in registers), d % n_heads == 0, w % 4 == 0 when n_heads > 1 (n_heads == 1 takes any
+ * d <= 256).  Outputs are OVERWRITTEN and must not overlap any input or each other.  A row / column without entries writes +0;
+ * a selection without nonzeros zeroes the requested outputs without a launch.  All offsets are 64-bit.  No float atomics.
+ *
+ * scores, du and da read the plan's forward rowptr / colidx only: plans without transposes serve them.  dv walks A_s^T through its
+ * permutation (i = t_colidx[e'], ds at perm[e']) exactly as the column side of h2gcn_edge_scores_backward_hops_heads_f32 does and has
+ * its two refusals -- H2GCN_ERR_NO_TRANSPOSE; H2GCN_ERR_INVALID_ARGUMENT naming H2GCN_PLAN_KEEP_PERMUTATION -- before the device is
+ * touched and before the row side runs.  A symmetric plan with the permutation kept serves it on the forward arrays, with the bits of
+ * a plan with built transposes.
+ *
+ * Arithmetic of a score: the order of h2gcn_sddmm_hops_heads_f32 (n_heads == 1: of h2gcn_sddmm_hops_f32) with g_c := a[s, c] and
+ * x_c := q_c -- quad value t = a0*q0, fma(a1, q1, t), fma(a2, q2, t), fma(a3, q3, t); the head's xor butterfly over its quads; block
+ * totals in ascending order from +0.  The bits of a score are therefore a function of a[s], u[i], v[j], d, K and the slope alone: not
+ * of the segment class, long_row_threshold, rows_per_wave, the hop selection or the strides; and with u = +0 they are the bits of
+ * h2gcn_sddmm_hops_heads_f32 on dY[i, s] = a[s], X = leaky(v).
+ * Error bound (exact: real arithmetic on the fp32 inputs, the branch taken from the fp32 p): two roundings go into q_c, then any order
+ * of a w-term dot product:  |score - exact| <= gamma_{w+2} * sum_c |a_c q_c| + (w + 2) * 2^-149,  gamma_k = k*u / (1 - k*u), u = 2^-24.
+ *
+ * Arithmetic of du / dv (contraction off: every product and every sum rounds on its own): ONE order per node, a function of the terms
+ * of the node's segments and of long_row_threshold at most -- never of rows_per_wave, of which other outputs were asked for, or of
+ * the run.  It is the canonical tree of h2gcn_spmm_hops_T_values_f32:
+ *   - entry m of a segment (m counted from the segment's first entry) adds dp_c to the partial P[m mod 4], P = P + dp_c, every partial
+ *     starting from +0 and running on across the selected hops in ascending order; the element is (P0 + P1) + (P2 + P3);
+ *   - a node whose segment has >= long_row_threshold entries in ANY selected hop: every hop's segment is dealt in 64-entry chunks to 4
+ *     waves (chunk c of a hop's segment to wave c mod 4), each wave builds that tree over its chunks, and the wave totals are added
+ *     ((T0 + T1) + T2) + T3.
+ * Error bound: |du - exact| <= gamma_{n+2} * sum |dp| + (n + 2) * 2^-149, n the entries of the row over the selected hops; dv likewise.
+ * Arithmetic of da: two stages.  G = min(2048, blocks of the forward tile walk) workgroups stride over the blocks of the forward walk
+ * hop by hop, every lane group adding its entries' ds * q_c in the order it meets them, and write ONE partial row per selected hop
+ * into the workspace ([G, H_sel, d]); a second kernel adds row g into accumulator (g / 16) mod 4 of part g mod 16, (A0 + A1) +
+ * (A2 + A3) per part, the 16 parts in ascending order from +0 -- a tree that is a function of G alone.  The bits of da depend on
+ * the launch geometry (n_rows, rows_per_wave, long_row_threshold, the hop selection) but never on the run, nor on du / dv being asked for.
+ * Error bound: |da - exact| <= gamma_{nnz_s+3} * sum |ds q| + (nnz_s + 3) * 2^-149.
+ * Non-finite inputs follow IEEE arithmetic column by column: a NaN in column c of u[i] or v[j] reaches only the scores of the entries
+ * that touch that node, in the head of c, and only column c of du / dv of the nodes whose segments hold such an entry.
+ *
+ * hipGraph capture: the rule of the SDDMM and edge-score calls -- the long-segment lists of the selection (the forward launch's for
+ * scores, du and da, the adjoint launch's for dv), built by the FIRST launch of that selection; a launch that would have to build one
+ * while its stream is being captured returns H2GCN_ERR_INVALID_ARGUMENT with the existing advice.
+ *
+ * Validation, in the order of h2gcn_sddmm_hops_heads_f32, all before the device is touched, each H2GCN_ERR_INVALID_ARGUMENT with a
+ * message naming the argument: a NULL plan, a hop mask outside the plan, d < 1, n_heads < 1, d % n_heads != 0, w % 4 != 0 with
+ * n_heads > 1, d > 256, ldu / ldv / lda (lddu / lddv / ldda of a requested output) smaller than d, a NULL u / v / a or table when the
+ * selection has nonzeros, a NULL entry of a selected hop that has nonzeros, du, dv and da all NULL, a workspace that is NULL or
+ * smaller than h2gcn_edge_scores_dynamic_workspace_bytes when da is asked for.
+ */
+size_t h2gcn_edge_scores_dynamic_workspace_bytes(const h2gcn_plan_t* plan, uint32_t hop_mask, int32_t d);
+int h2gcn_edge_scores_dynamic_hops_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* u_dev, int64_t ldu, const float* v_dev,
+                                       int64_t ldv, const float* a_dev, int64_t lda, int32_t d, int32_t n_heads, float negative_slope,
+                                       float* const* scores_dev, void* stream);
+int h2gcn_edge_scores_dynamic_backward_hops_f32(const h2gcn_plan_t* plan, uint32_t hop_mask, const float* u_dev, int64_t ldu,
+                                                const float* v_dev, int64_t ldv, const float* a_dev, int64_t lda, int32_t d, int32_t n_heads,
+                                                float negative_slope, const float* const* dscores_dev, float* du_dev, int64_t lddu,
+                                                float* dv_dev, int64_t lddv, float* da_dev, int64_t ldda, void* workspace_dev,
+                                                size_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------
  * The hop aggregation on values that are an ARGUMENT of the launch, with an optional head dimension (added within ABI 5;
  * found by symbol like the launches above) -- the last link of the attention chain without h2gcn_plan_set_values:
  *
