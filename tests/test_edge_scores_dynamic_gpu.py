@@ -19,7 +19,8 @@ from test_spmm_values_gpu import DEV, THRESHOLDS, bits, make_plan, strided_rows
 
 pytestmark = pytest.mark.gpu
 
-GRID = BACKWARD_GRID                          # packed w = 4, 8, 16, 32; head-aligned w = 64, 96; K = 1 with d = 22, 100
+GRID = BACKWARD_GRID                          # nine points: packed w = 4, 8, 16, 32 (five, one pass each); head-aligned w = 96 (192, 2) and
+#                                               w = 64 (256, 4); K = 1 with d = 22, 100.  Every geometry: test_edge_scores_dynamic_sweep_gpu
 KNOBS = tuple(zip(THRESHOLDS, (1, 3, 7)))     # (long_row_threshold, rows_per_wave)
 G = 8                                         # guard elements
 KINDS = {"forward": values_gpu.forward_hops, "adjoint": values_gpu.adjoint_hops, "square": values_gpu.square_hops}
